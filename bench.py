@@ -12,7 +12,7 @@ src/tabusearch.c:107-178) of the nearest-neighbour tour greedy(start = rank) to 
 EXECUTED, as the reference executes them: 1428 sweeps for rank 0, each evaluating all n(n-1)/2 - n = 49 985 000 non-adjacent
 pairs exactly (k_move_pos + k_exh, csrc/two_opt_exh.hpp: tour-position order, one new distance per pair), picking the
 arg-min, reversing the segment.  The tour is resident in HBM before the timed region starts; a step restores it
-device-to-device and runs the descent.  The final tour is checked against the committed golden vector after the timed region.
+device-to-device and runs the descent.  With --full the final tour is checked against the committed golden vector afterwards.
     value      = delta expressions executed per second, whole job (= sweeps x 49 985 000 x steps x ranks / elapsed)
     roofline   = that kernel pair: algorithmic operations per launch (35 per delta) over the mean launch
                  duration measured with HIP events on the engine's stream over the timed region
@@ -20,6 +20,12 @@ The product's default engines decide most pairs by bounds instead of executing t
 local optimum): those descents are reported as time_to_local_optimum (both move-selection rules, parity-checked), never as value.
 With N GPUs each rank refines its own start (weak scaling, no data-path collective); after the timed region the ranks
 run the sharded multi-start configs (BASELINE configs[3], [4]) with one RCCL all-reduce(min) + one broadcast each.
+
+A plain run sets up, warms up, times the steps and prints the line (plus the roofline of the timed kernel, which the timed
+steps measure themselves).  Everything else -- the parity check against the golden tour, the multi-start epilogue, the
+product's descents, the host-tour runs, the matrix build, the tabu list, the sharded configs and the CPU baselines -- runs
+only with --full (and --no-cpu-baseline / --no-extras / --no-variants trim that).  --dump-outputs DIR writes what the last
+timed step computed (rank 0's final tour, cost and counters; per rank when there are several) as float64 .npy files.
 """
 import argparse
 import json
@@ -381,7 +387,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip everything but the timed region and the roofline")
     ap.add_argument("--no-variants", action="store_true", help="skip the product's own descents (time_to_local_optimum): keeps a profile of the timed kernel clean")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the parity check, the multi-start epilogue, the product's descents, the extras "
+                         "and the CPU baselines (the --no-* flags trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (final tour, cost, counters) to DIR/<name>.npy as float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # --gpus N without a launcher around this process: start the N ranks here, BEFORE anything touches the GPU
     force_dist = os.environ.get("TSP_BENCH_FORCE_DIST") == "1"
@@ -427,7 +440,7 @@ def main():
     # rank takes the same branch and nobody waits in a collective the others never enter.
     comm = None
     dist_info = {}
-    if dist is not None:
+    if dist is not None and args.full:   # only the multi-start epilogue and the sharded configs use the C communicator
         import torch
 
         def all_agree(flag):   # min over the ranks of a 0 / 1 flag: every rank takes the same branch
@@ -464,8 +477,10 @@ def main():
     start_node = rank % N_NODES
     succ0, obj0, status = inst.construct(E.GREEDY, np.array([start_node], dtype=np.int32))
     assert status[0] == 0
-    tours = E.Tours(inst, 1)                 # the product's default engines (time_to_local_optimum below)
-    tours.upload(succ0[0], obj0[0])
+    tours = None
+    if args.full:
+        tours = E.Tours(inst, 1)             # the product's default engines (time_to_local_optimum below)
+        tours.upload(succ0[0], obj0[0])
     # the timed workload: the same instance with every bound off -- every delta expression of every sweep is executed
     os.environ["TSP_NO_FILTER"] = "1"
     inst_x = E.Instance(ctx, xy, wt, 1)
@@ -509,14 +524,25 @@ def main():
     value = tot["evals"] * args.steps / elapsed          # delta expressions executed per second, whole job
     launch_ms = float(np.sum(dev_ms)) / max(1, int(st["sweeps"]) * len(dev_ms))   # mean of one sweep's launches (k_move_pos + k_exh)
 
-    # multi-start epilogue of the timed workload: one RCCL all-reduce(min) of the packed (true cost, rank)
-    cost_now, _, packed = tours_x.best(true_cost=True)
-    best_cost, best_rank = int(cost_now), rank
-    if dist is not None:
-        best_cost, best_rank = MS.allreduce_best(MS.pack(int(cost_now), rank), device=device)
-        if comm is not None:   # the same reduction through the C ABI's communicator: both must agree
-            c_cost, c_rank = MS.unpack(comm.allreduce_min(MS.pack(int(cost_now), rank)))
-            dist_info["c_abi_allreduce_agrees_with_torch"] = bool((c_cost, c_rank) == (best_cost, best_rank))
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step (Tours.download): the local optimum's successor list,
+        # its cost and the descent's counters (the deterministic ones: sweeps, delta expressions, moves)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        tag = "" if world == 1 else "rank%d_" % rank
+        arrays = {"final_succ": s_fin[0], "final_cost": o_fin[:1],
+                  "counters_sweeps_evals_moves": [st["sweeps"], st["evals"], st["moves"]]}
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, tag + name + ".npy"), np.asarray(a, dtype=np.float64))
+
+    if args.full:
+        # multi-start epilogue of the timed workload: one RCCL all-reduce(min) of the packed (true cost, rank)
+        cost_now, _, packed = tours_x.best(true_cost=True)
+        best_cost, best_rank = int(cost_now), rank
+        if dist is not None:
+            best_cost, best_rank = MS.allreduce_best(MS.pack(int(cost_now), rank), device=device)
+            if comm is not None:   # the same reduction through the C ABI's communicator: both must agree
+                c_cost, c_rank = MS.unpack(comm.allreduce_min(MS.pack(int(cost_now), rank)))
+                dist_info["c_abi_allreduce_agrees_with_torch"] = bool((c_cost, c_rank) == (best_cost, best_rank))
 
     ops_per_launch = pairs_per_sweep * OPS_EXACT
     out = {
@@ -545,10 +571,6 @@ def main():
                             "49 985 000 non-adjacent pairs of every sweep gets its exact delta; nothing is decided by a bound",
         "evals": {"per_step_rank0": {"delta_expressions": int(st["evals"]), "sweeps": int(st["sweeps"]), "moves": int(st["moves"])},
                   "delta_per_s": value, "us_per_sweep_wall": 1e6 * elapsed / args.steps / max(1, int(st["sweeps"]))},
-        "multistart_best": dict({"cost": best_cost, "rank": best_rank,
-                                 "collective": ("all_reduce(min) int64 over RCCL (torch.distributed and the C ABI's "
-                                                "tsp_dev_multistart_allreduce)") if dist is not None else "none (1 GPU)"},
-                                **dist_info),
         # the dominant kernel of the timed region, measured live: HIP events on the engine's stream over the timed descents
         "roofline": {
             "kernel": "tsp::k_exh<EUC_2D integer-coordinate variant, RJ> (+ tsp::k_move_pos, 4.7 us of the pair): one launch pair = one sweep = "
@@ -585,7 +607,13 @@ def main():
     else:
         out["roofline"]["traffic"] = None
 
-    if rank == 0:
+    if args.full:
+        out["multistart_best"] = dict({"cost": best_cost, "rank": best_rank,
+                                       "collective": ("all_reduce(min) int64 over RCCL (torch.distributed and the C ABI's "
+                                                      "tsp_dev_multistart_allreduce)") if dist is not None else "none (1 GPU)"},
+                                      **dist_info)
+
+    if rank == 0 and args.full:
         big = golden("oracle_vectors_big.json")["rand10000_best"]["final"]
         out["parity"] = {"final_cost": float(o_fin[0]), "golden_cost": big["cost"], "sweeps": int(st["sweeps"]),
                          "golden_sweeps": big["stats"]["sweeps"], "moves": int(st["moves"]),
@@ -682,7 +710,7 @@ def main():
             "sweep_that_finds_nothing_us_per_call": 1e6 * float(np.mean(t_nohit[2:])),
             "note": "a chain of 2 704 dependent moves: 5.8 us per step, 3.1 of it one all-to-all exchange (DESIGN.md 4.8, 4.8c)"}
 
-    if rank == 0 and not args.no_variants:
+    if rank == 0 and args.full and not args.no_variants:
         guarded("time_to_local_optimum", product_section)
         if "error" not in out.get("time_to_local_optimum", {"error": 1}):
             guarded("time_to_local_optimum_first", first_section)
@@ -809,11 +837,11 @@ def main():
         H.tsp_host_shutdown()
         out["alg_2opt_tabu_with_a_list"] = res
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         guarded("time_to_local_optimum_host_tours", extras_section)
         guarded("alg_2opt_tabu_with_a_list", tabu_section)
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         out["other_configs"] = sharded_configs(E, MS, ctx, rank, world, device, comm)
         out["scaling_note"] = {
             "timed_region": "one start per GPU, no data-path collective: weak scaling, flat by construction",
@@ -841,10 +869,11 @@ def main():
             "others": {k: v for k, v in base.items() if k != "best_improvement"},
         }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         guarded("cpu_baseline", cpu_section)
 
-    tours.close()
+    if tours is not None:
+        tours.close()
     tours_x.close()
     inst_x.close()
     inst.close()

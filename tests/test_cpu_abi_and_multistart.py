@@ -239,6 +239,15 @@ def test_bench_self_launcher_world2_gloo():
     assert r.returncode == 3
 
 
+def test_bench_refuses_a_run_without_timed_steps():
+    """--steps sets the number of timed steps and ms_per_step divides by it: zero steps (or a negative warm-up) is an
+    argument error, raised before anything touches a GPU."""
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + bad, capture_output=True,
+                           text=True, timeout=120)
+        assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, (bad, r.stderr[-2000:])
+
+
 def test_bench_parent_never_touches_the_gpu_or_execs():
     """The self-launching parent must not initialise HIP (a later exec / fork from such a process takes the box down) and
     must not exec: checked on the source -- no os.exec*, and nothing but the standard library is imported before the

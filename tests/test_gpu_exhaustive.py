@@ -126,3 +126,32 @@ def test_exhaustive_full_descent_of_rand10000_equals_the_golden(eng, ctx, monkey
     f = g["final"]
     assert O.fnv1a(s) == f["hash"] and o == f["cost"]
     assert {k: st[k] for k in ("sweeps", "evals", "moves", "reversed")} == f["stats"]
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_descent(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the line carries the headline fields for exactly K timed steps
+    and nothing of --full, and DIR holds the last timed descent's result -- the golden local optimum of rand10000."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "outputs"
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TSP_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(dump)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["metric"] == "2opt_edge_pair_evals_per_sec" and out["unit"] == "evals/s" and out["dtype"] == "f64"
+    assert out["higher_is_better"] is True and out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0
+    assert out["ms_per_step"] > 0 and abs(out["time_to_local_optimum_s"] * 1e3 - out["ms_per_step"]) < 1e-6 * out["ms_per_step"]
+    assert not {"parity", "multistart_best", "time_to_local_optimum", "other_configs", "cpu_baseline"} & set(out)
+    f = BIG["rand10000_best"]["final"]
+    succ = np.load(dump / "final_succ.npy")
+    cost = np.load(dump / "final_cost.npy")
+    counters = np.load(dump / "counters_sweeps_evals_moves.npy")
+    assert succ.dtype == cost.dtype == counters.dtype == np.float64 and succ.shape == (10000,)
+    assert O.fnv1a(succ.astype(np.int32)) == f["hash"] and cost.tolist() == [f["cost"]]
+    assert counters.tolist() == [f["stats"]["sweeps"], f["stats"]["evals"], f["stats"]["moves"]]

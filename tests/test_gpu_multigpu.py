@@ -90,7 +90,7 @@ def test_bench_starts_its_own_ranks_and_runs_the_collectives_over_rccl():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-variants"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--full", "--no-cpu-baseline", "--no-variants"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == 1 and out["parity"]["final_tour_matches_golden"] and out["all_checks_ok"]

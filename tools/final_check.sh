@@ -9,7 +9,7 @@ for u in xchg dist2 dist3; do [ -x tools/ubench/$u ] && ./tools/ubench/$u > $O/u
 cat $O/full_gpu_tests.log
 (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2) > $O/smoke.log 2>&1
 cat $O/smoke.log
-timeout 900 python bench.py > $O/bench_final.json 2> $O/bench_final.err
+timeout 900 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
 tail -2 $O/bench_final.err
 python - <<PY
 import json

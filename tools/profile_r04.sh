@@ -12,7 +12,7 @@ O=$R/gpurun_out
 mkdir -p $O
 make -C $R/oracle >/dev/null
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-variants --no-extras"
+B="$R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-variants --no-extras"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_trace -- python3 $B > $O/${TAG}_bench_under_rocprof.json 2> $O/trace.log
 python3 $R/tools/summarize_rocprof.py stats $O/prof_trace $O/${TAG}_kernel_stats.csv > /dev/null
 for C in FETCH_SIZE WRITE_SIZE; do
