@@ -52,19 +52,18 @@ def _check(eng, ctx, monkeypatch, xy, wt, succ0, env=None):
 
 @pytest.mark.parametrize("n", [5, 6, 7, 8, 52, 63, 64, 65, 126, 127, 128, 129, 254, 255, 256, 300, 511, 777])
 def test_exhaustive_descents_equal_the_oracle_at_strip_boundaries(eng, ctx, monkeypatch, n):
-    """A strip is 64 RJ - 1 pair-columns wide (127 with the default RJ = 2): sizes around one, two, four strips, and tiny ones."""
+    """A strip is 64 RJ - 1 pair-columns wide (255 at RJ = 4): sizes around one and two strips, half strips, and tiny ones."""
     xy = rand_instance(n, seed=100 + n, hi=5000)
     rng = np.random.default_rng(n)
     _check(eng, ctx, monkeypatch, xy, O.EUC_2D, random_tour(n, rng))
 
 
-@pytest.mark.parametrize("rj,waves", [("1", "1"), ("1", "8"), ("2", "2"), ("4", "1"), ("4", "4"), ("4", "8"), ("8", "2"), ("8", "4"), ("16", "1"), ("16", "2")])
-def test_exhaustive_descents_for_every_shape_of_the_grid(eng, ctx, monkeypatch, rj, waves):
-    """Columns per lane (strip width 63 / 127 / 255) and waves per SIMD (how the row units are dealt) change no decision."""
+def test_exhaustive_descents_from_greedy_tours(eng, ctx, monkeypatch):
+    """The production grid (four columns per lane, four workgroups per CU) on whole descents from a greedy tour."""
     for n, seed in ((300, 1), (1000, 2)):
         xy = rand_instance(n, seed=seed, hi=20000)
         _, succ0, _ = O.greedy(xy, O.EUC_2D)
-        _check(eng, ctx, monkeypatch, xy, O.EUC_2D, succ0, {"TSP_EXH_RJ": rj, "TSP_EXH_WAVES": waves})
+        _check(eng, ctx, monkeypatch, xy, O.EUC_2D, succ0)
 
 
 @pytest.mark.parametrize("shares", ["0", "70,20,7,3", "10,20,30,40", "97,1,1,1"])

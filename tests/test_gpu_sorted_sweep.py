@@ -128,23 +128,20 @@ def test_sorted_and_tiled_sweeps_agree_move_for_move(eng, ctx, monkeypatch, name
 
 
 @pytest.mark.parametrize("name", ["att532", "rand2000", "d493"])
-def test_first_improvement_both_kernel_forms_agree(eng, ctx, monkeypatch, name):
-    """k_first (fixed grid, out-of-place moves, two control-block slots) against k_step<FIRST> (the first form),
-    and both against the oracle's alg_2opt counters."""
+def test_first_improvement_k_first_equals_the_oracle(eng, ctx, monkeypatch, name):
+    """k_first (fixed grid, out-of-place moves, two control-block slots) against the oracle's alg_2opt tour and counters,
+    whatever the number of tile rows of its grid."""
     xy, wt = load_instance(name)
     _, succ0, obj0 = O.greedy(xy, wt)
     _, es, eo, est, _ = O.two_opt_first(xy, wt, succ0, obj0)
-    for v1 in ("0", "1"):
-        for gy, rj in (("8", "2"), ("3", "1"), ("64", "2")):
-            monkeypatch.setenv("TSP_FIRST_V1", v1)
-            monkeypatch.setenv("TSP_FIRST_GRID_ROWS", gy)
-            monkeypatch.setenv("TSP_FIRST_RJ", rj)
-            inst = eng.Instance(ctx, xy, wt, 1)
-            rc, s, o, st = inst.two_opt(succ0, obj0, mode=eng.FIRST, engine=1)
-            inst.close()
-            assert (s == es).all() and o == eo, (v1, gy, rj)
-            assert (st["sweeps"], st["evals"], st["moves"], st["reversed"]) == \
-                (est["sweeps"], est["evals"], est["moves"], est["reversed"]), (v1, gy, rj)
+    for gy in ("8", "3", "64"):
+        monkeypatch.setenv("TSP_FIRST_GRID_ROWS", gy)
+        inst = eng.Instance(ctx, xy, wt, 1)
+        rc, s, o, st = inst.two_opt(succ0, obj0, mode=eng.FIRST, engine=1)
+        inst.close()
+        assert (s == es).all() and o == eo, gy
+        assert (st["sweeps"], st["evals"], st["moves"], st["reversed"]) == \
+            (est["sweeps"], est["evals"], est["moves"], est["reversed"]), gy
 
 
 def test_first_then_best_then_first_on_one_handle(eng, ctx):

@@ -1,7 +1,7 @@
 """Diagnostic build only (lib_diag, -DTSP_STAMPS; recipe in tools/diag_stamps.py): the timeline of one exhaustive sweep
 (k_exh, two_opt_exh.hpp) on rand10000 -- when the first / last wave starts, leaves its rows, when the last candidate is
 published and when the last block's apply is done, in microseconds after the first wave's start.
-usage: diag_exh.py [rj:waves]   (through gpurun)"""
+usage: diag_exh.py"""
 import os, sys, ctypes as C
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
@@ -11,8 +11,6 @@ from tsp_optimization_amd import build as B
 B.LIB_DIR = os.path.join(R, 'tsp_optimization_amd', 'lib_diag')
 from tsp_optimization_amd import engine as E
 from helpers import load_instance
-case = (sys.argv[1:] or ["4:4"])[0]
-os.environ["TSP_EXH_RJ"], os.environ["TSP_EXH_WAVES"] = case.split(":")
 ctx = E.Context(0)
 xy, wt = load_instance('rand10000')
 inst = E.Instance(ctx, xy, wt, 1)

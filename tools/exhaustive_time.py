@@ -1,6 +1,6 @@
 """The exhaustive best-improvement sweep (every delta expression executed, TSP_NO_FILTER=1: bench.py's timed kernel) on rand10000:
-the position-order kernel k_move_pos + k_exh (two_opt_exh.hpp) against its grid shape, and the tiled k_recs + k_step it replaced.
-usage: exhaustive_time.py [rj:waves ...]   (through gpurun)"""
+the position-order kernel k_move_pos + k_exh (two_opt_exh.hpp) against the tiled k_recs + k_step it replaced.
+usage: exhaustive_time.py [old|exh ...]"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
@@ -13,13 +13,9 @@ ctx = E.Context(0)
 xy, wt = load_instance("rand10000")
 inst = E.Instance(ctx, xy, wt, 1)
 succ, obj, _ = inst.construct(E.GREEDY, np.array([0], dtype=np.int32))
-cases = sys.argv[1:] or ["old", "1:4", "2:2", "2:4", "2:8", "4:2", "4:4", "4:8"]
+cases = sys.argv[1:] or ["old", "exh"]
 for c in cases:
-    if c == "old":
-        os.environ["TSP_EXH_POS"] = "0"
-    else:
-        os.environ["TSP_EXH_POS"] = "1"
-        os.environ["TSP_EXH_RJ"], os.environ["TSP_EXH_WAVES"] = c.split(":")
+    os.environ["TSP_EXH_POS"] = "0" if c == "old" else "1"
     inst.reload_switches()
     tours = E.Tours(inst, 1)
     tours.upload(succ[0], obj[0])

@@ -54,11 +54,9 @@ constexpr int kApplyThreads = 1024;
 #define TSP_SWITCH_LIST(X)                                                                                                  \
     X(ENGINE) X(CLUSTER_BLOCKS) X(CLUSTER_MIN_ROWS) X(CLUSTER_MAX_ROWS) X(CLUSTER_HIT_CAP) X(CLUSTER_SPIN_LIMIT)            \
     X(CLUSTER_SPIN_MS) X(CLUSTER_COPIES) X(CLUSTER_TILE_ROWS) X(CLUSTER_XCD_LOCAL) X(CLUSTER_ALLOW_OVERSUB) X(CLUSTER_DEBUG) X(CLUSTER_PROBE) X(CLUSTER_FIRST_SORTED) X(TABU_DENSE)     \
-    X(LDS_PROBE) X(LDS_PROBE2) X(LDS_MIN_ROWS) X(LDS_EDGE_CACHE) X(NO_ICOORD) X(NO_FILTER) X(NO_PRUNE) X(SORTED_MIN_N)      \
-    X(SWEEP_BLOCKS) X(SWEEP_TABLE) X(BEST_ROWS_PER_BLOCK) X(BEST_RECS) X(FIRST_V1) X(FIRST_GRID_ROWS) X(FIRST_RJ)          \
-    X(FIRST_MIN_ROWS) X(FIRST_MAX_ROWS) X(FIRST_ROWS_PER_BLOCK) X(COUNT_EVALS) X(USE_GRAPH) X(CONSTRUCT_GLOBAL)            \
-    X(CONSTRUCT_NN) X(LDS_PAIR) X(CLUSTER_FS_ROWS) X(CLUSTER_LPT) X(CLUSTER_B0) X(LDS_F32_MIN_N) X(CLUSTER_DEFER)          \
-    X(EXH_POS) X(EXH_WAVES) X(EXH_RJ) X(EXH_EVEN) X(EXH_PRIO) X(CLUSTER_COOP) X(TABU_INKERNEL)
+    X(LDS_PROBE) X(LDS_MIN_ROWS) X(LDS_EDGE_CACHE) X(NO_ICOORD) X(NO_FILTER) X(NO_PRUNE) X(SORTED_MIN_N)      \
+    X(SWEEP_BLOCKS) X(SWEEP_TABLE) X(BEST_ROWS_PER_BLOCK) X(BEST_RECS) X(FIRST_GRID_ROWS) X(FIRST_MIN_ROWS)                \
+    X(FIRST_MAX_ROWS) X(CONSTRUCT_GLOBAL) X(CONSTRUCT_NN) X(CLUSTER_FS_ROWS) X(LDS_F32_MIN_N) X(EXH_POS) X(TABU_INKERNEL)
 namespace tsp {
 enum SwitchId {
 #define TSP_SW_ENUM(name) SW_##name,
@@ -164,11 +162,10 @@ struct tsp_dev_tours {
     // exhaustive sweep in position order (two_opt_exh.hpp): the tour's coordinates, edge lengths and ids by position (padded)
     double2 *d_pxy = nullptr;
     int *d_pe = nullptr, *d_pid = nullptr;
-    bool exh_lds_granted = false;
     int exh_share[4] = {0, 0, 0, 0};   // k_exh: rows per wave of each part of the grid (0: equal shares)
     int exh_gens = 0;                  // ... parts (= workgroups per CU)
     int exh_lds = 0;                 // k_exh: dynamic LDS a workgroup asks for (unused; it pins the number of workgroups per CU)
-    int exh_blocks = 0, exh_rj = 4, exh_prio = 1;  // k_exh: workgroups per tour (0: the tiled k_step executes the exhaustive sweep), columns per lane
+    int exh_blocks = 0;              // k_exh: workgroups per tour (0: the tiled k_step executes the exhaustive sweep)
     int *d_pairtab = nullptr;        // group pairs per cluster of k_sweep blocks (host-built), or nullptr
     int *d_ticket = nullptr;         // per tour: scan blocks still to arrive in the current step
     int *d_row_ticket = nullptr;     // per tour x tile row (BEST two-level hand-off)
@@ -221,18 +218,11 @@ struct tsp_dev_tours {
     // pinned host mirror of the states, for polling
     tsp::TourState *h_state = nullptr;
     // scan geometry
-    int first_rows_per_block = 8;
     int first_grid_rows = 32;        // k_first: tile rows of its fixed grid
-    int first_rj = 1;                // k_first: columns per lane
     int first_max_rows2 = 2048;      // k_first: largest chunk
-    int first_v1 = 0;                // use k_step<FIRST> (the first form) instead of k_first
     int first_min_rows = 8;
-    int first_max_rows = 2048;
     int best_rows_per_block = 32;
-    int count_evals = 1;             // FIRST: keep the reference-equivalent evaluation counter
     int use_recs = 1;                // BEST: materialise the node records once per step (k_recs)
-    int use_graph = 0;               // replay full batches of steps from a captured hipGraph
-    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};   // per mode
     // accumulated device time
     double device_ms = 0.0;
 };

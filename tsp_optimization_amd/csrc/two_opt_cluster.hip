@@ -82,7 +82,7 @@ struct ClusterArgs {
     int copies;                  // copies in use (1 ... kClCopies)
     int xcd_local;               // block -> (tour, c) keeps a tour's workgroups on one XCD (host: the grid is a multiple of 8 C)
     int *err;
-    int n, nid, ng, ntests, C, max_iters, rmin, rmax, rcap, rbs, count_evals;
+    int n, nid, ng, ntests, C, max_iters, rmin, rmax, rcap, rbs;
     // BEST, sorted scan, with a tabu list (two_opt_tabu_list.hpp has the method): stamps, the compact list of the non-zero
     // ones, and the handle's side words {skipped pairs of the run, live tour edges of sweep number mod 3 = 0 / 1 / 2}
     int *tabu;
@@ -101,15 +101,13 @@ struct ClusterArgs {
     int *chain_pp;
     int *snap;
     int probe;              // FIRST: largest distance (pairs) of the last hit after which a step starts with the probe; 0 = never
-    int defer_moves;        // carry the swaps of a move out during the next step's exchange (TSP_CLUSTER_DEFER)
-    int use_b0;             // BEST, sorted scan: start every sweep from the bound the previous exchange yields (TSP_CLUSTER_B0)
     int fs_rows;            // FIRST on the sorted replica: a step takes the box-pruned scan when the running mean of the rows between hits is at least this
     int fs_exit;            // FIRST, plain replica: the launch ends when that mean reaches this (the host goes on with the rank-order variant); 0 = never
     int fs_leave;           // FIRST, rank-order replica: the launch ends when the mean falls below this (back to the plain variant); 0 = never
     int stage_pairs;        // sorted: group pairs whose records are staged in LDS at a time
     unsigned spin_limit;    // sweeps of the exchange area before a workgroup gives up ...
     unsigned long long spin_ticks;   // ... or this much time (100 MHz ticks) without the peers' tags, whichever comes first
-    int dbg;                // diagnostics (TSP_CLUSTER_DEBUG): 1 rebuild every group bound per step, 2 no row culling, 4 no box test
+    int dbg;                // test hook (TSP_CLUSTER_DEBUG = 2048): a workgroup stops answering in the middle of a chain
     double org_x, org_y;    // float replicas hold coordinates relative to this corner (exact: bounded integers)
     double margin, prune, sum_margin;
 };
@@ -673,7 +671,7 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
         return block_sum<long long>(cnt, s_ll);
     };
     if constexpr (!BEST) {
-        if (a.count_evals && c == 0 && !failed && (ci != 0 || cj != 0)) {
+        if (c == 0 && !failed && (ci != 0 || cj != 0)) {
             adjA0 = edges_upto(make_key(ci, cj));
             sweep_open = true;
         }
@@ -686,7 +684,7 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
     // step's exchange -- time they would spend waiting for it.  (Not with a tabu list: those waves work on the list then.  Not for
     // C == 1: no exchange to hide behind.  A move decided by the probe is carried out at once, after any pending one.)
     ClView view{0, 0, 0};
-    const bool defer_on = !TABU && C > 1 && a.defer_moves;
+    const bool defer_on = !TABU && C > 1;
     auto swaps = [&](const ClView &m, int t0, int stride) {   // the reversal itself, by the threads t0, t0 + stride, ...
         const int half = m.L >> 1;
         for (int t = t0; t < half; t += stride) {
@@ -838,7 +836,6 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                         const double gx = fmax(0.0, fmax(rb.x - cb.y, cb.x - rb.y)), gy = fmax(0.0, fmax(rb.z - cb.w, cb.z - rb.w));
                         const double T = gmax[r] + gmax[cg] + prune2 + (BEST ? b0 : 0.0);   // b0: what is known about this sweep before it starts
                         surv = T > 0.0 && gx * gx + gy * gy < (ATT10 ? 10.0 * T * T : T * T);
-                        if (a.dbg & 4) surv = true;
                     }
                     if (tests_per_wave) {   // (the list's counter was zeroed behind the arg-min barrier of the step before)
                         wave_surv = __ballot(surv);
@@ -923,7 +920,6 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                             }
                             qm |= (reach ? 1u : 0u) << k;
                         }
-                        if (a.dbg & 2) qm = vr < n ? 0xfu : 0u;
                         // units: (row, quarter) pairs, quarter-major within this wave's share of the list; a unit is the row's stage
                         // slot (10 bits), the quarter (2), "the pair is a group with itself" (1)
                         const unsigned long long m0 = __ballot(qm & 1u), m1 = __ballot(qm & 2u), m2 = __ballot(qm & 4u), m3 = __ballot(qm & 8u);
@@ -974,7 +970,7 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                                         delta = gi < gj ? pair_delta<WT, INT>(ri, rj) : pair_delta<WT, INT>(rj, ri);
                                     }
                                     if (BEST ? (delta < bd || (delta == bd && delta < 0.0)) : (delta < 0.0)) {
-                                        if constexpr (INT) { if (a.dbg & 8) { gi = ri.id; gj = rj.id; } else { gi = a.gid[ri.id]; gj = a.gid[rj.id]; } }
+                                        if constexpr (INT) { gi = a.gid[ri.id]; gj = a.gid[rj.id]; }
                                         const u64 kk = make_key(min(gi, gj), max(gi, gj));
                                         // best improvement: arg-min of (delta, pair); first improvement: the first improving pair after the cursor
                                         if (BEST ? (delta < bd || kk < key) : (kk > startkey && kk < key)) {
@@ -1309,7 +1305,7 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                 // The entries go round the workgroups 1 .. C - 1, one per thread: the first workgroup, which reads the live-edge count
                 // and (in a chain of iterations) decides the kicks, is the one the cluster waits for in every sweep -- its exchange
                 // shares the CU's memory path with whatever its other waves load (rand10000: 137.6 -> 131.3 us per iteration)
-                const bool spread = C > 1 && !(a.dbg & 64);
+                const bool spread = C > 1;
                 const int kstep = spread ? (C - 1) * (kClThreads - 64) : C * (kClThreads - 64);
                 const int k0 = spread ? (c == 0 ? m : (c - 1) + (C - 1) * (tid - 64)) : c * (kClThreads - 64) + tid - 64;
                 for (int k = k0; k < m; k += kstep) {
@@ -1325,7 +1321,7 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                     // computed from (no load at all in most sweeps: +6 us per iteration); the first round trip issued before
                     // the scan (+3 us: every wait for a load in the scan then waits for it too); the first workgroup left out of
                     // the group-pair table (no difference).
-                    const bool mine = k == k0 && !(a.dbg & 128);
+                    const bool mine = k == k0;
                     if (mine && tl_state == 1) {
 #ifdef TSP_STAMPS
                         ++tl_n_skip;
@@ -1439,7 +1435,7 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
             flush_view();   // a probe step: the reversal an exchange step left pending comes first (no-op after an exchange step)
             const int pa = pos[wi], pb = pos[wj];
             if constexpr (!BEST) {
-                if (a.count_evals && c == 0) {   // d_t of this move, on the tour as it is before the move
+                if (c == 0) {   // d_t of this move, on the tour as it is before the move
                     const int a1e = to_ext((int)order[pa + 1 == n ? 0 : pa + 1]), b1e = to_ext((int)order[pb + 1 == n ? 0 : pb + 1]);
                     const u64 hi = make_key(fi, fj);
                     auto le = [&](int u, int v) { return make_key(min(u, v), max(u, v)) <= hi ? 1 : 0; };
@@ -1447,9 +1443,8 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                 }
             }
             if constexpr (SORTED && BEST) {
-                if (a.use_b0 && wave == 0 && C > 1) {   // the bound the next sweep starts from (the exchanging wave holds the candidates)
-                    if (a.dbg & 16) { for (int q = 0; q < 4; ++q) b0_mem_d[q] = 0.0; }   // diagnostics: no memory of earlier sweeps
-                    const double nb0 = cl_next_bound(xcd, pos, n, (INT && !TABU) && !(a.dbg & 32), b0_mem_ip, b0_mem_d);
+                if (wave == 0 && C > 1) {   // the bound the next sweep starts from (the exchanging wave holds the candidates)
+                    const double nb0 = cl_next_bound(xcd, pos, n, INT && !TABU, b0_mem_ip, b0_mem_d);
                     if (lane == 0) *s_b0 = nb0;
                 }
             }
@@ -1459,32 +1454,23 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                 // b: (b, b1) becomes (a, b); b1: (b, b1) becomes (a1, b1) -- every other node keeps its two tour neighbours whatever
                 // the orientation.  So the bounds of their four groups are rebuilt from the OLD tour with those four edges patched,
                 // beside the reads of pa / pb and before the swaps: no barrier between the swaps and a rebuild.
-                if (a.dbg & 1) gmax_dirty = true;   // diagnostics: every bound rebuilt after the swaps (below)
-                else patch_bounds(wi, wj, pa, pb);
+                patch_bounds(wi, wj, pa, pb);
             }
             Lr = pb - pa; if (Lr < 0) Lr += n;
-            const bool dbg_rebuild = SORTED && BEST && gmax_dirty;
-            if (defer_on && !probe_hit && !dbg_rebuild) {
+            if (defer_on && !probe_hit) {
                 view.pa = pa; view.pb = pb; view.L = Lr;   // carried out during the next step's exchange
                 deferred_now = true;
             } else {
                 __syncthreads();   // everyone has read pa / pb (and finished the bound rebuild)
                 ClView now{pa, pb, Lr};
                 swaps(now, tid, kClThreads);
-                if constexpr (SORTED && BEST) {
-                    if (gmax_dirty) {   // TSP_CLUSTER_DEBUG & 1: every bound from the new tour
-                        __syncthreads();
-                        group_bounds(wave, kClWaves, ng);
-                        gmax_dirty = false;
-                    }
-                }
             }
         }
         // End of the step.  Nothing was written since the exchange's barrier when the move was deferred on the plain replica (no
         // swaps, no group bounds, no bound for the next sweep): the next step's first shared writes are the probe's / the arg-min's
         // per-wave slots and, behind a barrier of their own, the row records -- none of which this step still reads.
         if (!(deferred_now && !SORTED)) __syncthreads();
-        if constexpr (SORTED && BEST) b0 = (a.use_b0 && found && C > 1) ? *s_b0 : 0.0;
+        if constexpr (SORTED && BEST) b0 = (found && C > 1) ? *s_b0 : 0.0;
 
         CL_T(5);
         // ---- control block ------------------------------------------------------------------------------------------
@@ -1759,10 +1745,8 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
     if (failed || c != 0) return;
     __syncthreads();
     if constexpr (!BEST) {
-        if (a.count_evals) {
-            if (sweep_open) adj_seen += edges_upto(make_key(ci, cj)) - adjA0 - adjD;   // the sweep goes on in the next launch
-            evals -= adj_seen;
-        }
+        if (sweep_open) adj_seen += edges_upto(make_key(ci, cj)) - adjA0 - adjD;   // the sweep goes on in the next launch
+        evals -= adj_seen;
     }
     int *pos_g = a.poss + (size_t)tour * n;
     for (int p0 = tid; p0 < n; p0 += LU * kClThreads) {
@@ -1868,12 +1852,6 @@ hipError_t cl_launch_k(tsp_dev_tours *t, const ClusterArgs &a, size_t lds) {
     const long long grid = (long long)t->B * a.C;
     if (a.C > 1 && (long long)occ_blocks[dv] * std::max(1, t->inst->ctx->num_cus) < grid && !TSP_SW(t->inst, CLUSTER_ALLOW_OVERSUB, 0))
         return hipErrorCooperativeLaunchTooLarge;
-    if (TSP_SW(t->inst, CLUSTER_COOP, 0) && a.C > 1) {   // measurement switch: the same grid as a cooperative launch (the runtime checks residency itself)
-        ClusterArgs copy = a;
-        void *args[] = {&copy};
-        const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void *>(k), dim3((unsigned)grid), dim3(kClThreads), args, (unsigned)lds, s);
-        return e == hipSuccess ? hipGetLastError() : e;
-    }
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kClThreads), lds, s, a);
     return hipGetLastError();
 }
@@ -2024,7 +2002,7 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
         std::sort(pr.begin(), pr.end());
         std::vector<int> tab((size_t)C * ntests, -1);
         bool dealt = false;
-        if (C > 1 && B == 1 && TSP_SW(inst, CLUSTER_LPT, 1)) {
+        if (C > 1 && B == 1) {
             // Deal by estimated cost instead of in turn.  A step costs the time of its slowest workgroup (1.9 us of an 11.4 us
             // best-improvement step at n = 10 000 were spent waiting for it), and what a group pair costs is decided by the tour:
             // whether it survives the box test and how many of its rows survive the culling.  Both are estimated here on the
@@ -2131,7 +2109,6 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
     a.err = reinterpret_cast<int *>(t->d_cl_slots + (t->cl_slot_words - 2));
     a.n = n; a.ng = inst->ng; a.ntests = t->cl_ntests; a.C = C;
     a.xcd_local = (B > 1 && C <= 32 && (B * C) % (8 * C) == 0 && TSP_SW(inst, CLUSTER_XCD_LOCAL, 1)) ? 1 : 0;
-    a.count_evals = t->count_evals;
     a.tabu = nullptr; a.tabu_list = nullptr; a.tabu_list_n = nullptr; a.tabu_list_cap = 0; a.iter = iter; a.tenure = tenure; a.tabu_side = nullptr;
     if (tabu) {   // the caller has brought the handle's list up to date (tsp_tabu_list_prepare) and zeroed the side words
         if (mode != TSP_2OPT_BEST || !p.sorted || B != 1 || !tabu->list_valid) return TSP_DEV_E_ARG;
@@ -2145,8 +2122,6 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
         a.chain_pairs = t->cl_ik_pairs; a.chain_ab = t->d_chain + t->cl_ik_ab; a.chain_pp = t->d_chain + t->cl_ik_pp;
     }
     a.probe = TSP_SW(inst, CLUSTER_PROBE, 4096);
-    a.use_b0 = TSP_SW(inst, CLUSTER_B0, 1);
-    a.defer_moves = TSP_SW(inst, CLUSTER_DEFER, 1);
     a.fs_rows = fs_rows;
     a.fs_exit = fs_avail ? fs_rows : 0;
     a.fs_leave = fs_avail ? std::max(1, fs_rows / 4) : 0;

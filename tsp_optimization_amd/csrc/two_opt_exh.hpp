@@ -54,6 +54,7 @@ __device__ unsigned long long g_exh_t[8];
 constexpr int kExhPad = 1152;          // positions past n that k_move_pos fills (>= the widest strip + 2)
 constexpr int kExhCluster = 32;        // blocks per first-level arrival counter
 constexpr int kRowBatch = 4;           // rows whose operands one scalar load instruction fetches
+constexpr int kExhRJ = 4;              // k_exh: columns per lane (8 and 16, and 1 and 2, measured slower)
 
 template <int WT>
 constexpr bool exh_metric() { return WT == WT_EUC_2D_ICOORD || WT == WT_CEIL_2D_ICOORD || WT == WT_ATT_ICOORD; }
@@ -133,11 +134,10 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__rest
     pid[pbase + k] = u;
 }
 
-// (RJ = 8 is built for three waves per SIMD: 170 VGPRs; RJ = 16 is meant for one or two waves per SIMD -- many independent
-// distances per wave instead of many waves)
+// RJ = kExhRJ columns per lane, four workgroups of four waves per CU (the host pins that with its LDS request)
 template <int WT, bool INT, int RJ>
-__global__ __launch_bounds__(kScanThreads, (RJ == 8 ? 3 : 1)) void k_exh(const StepArgs a, const double2 *__restrict__ pxy_all, const int *__restrict__ pe_all,
-                                                      const int *__restrict__ pid_all, int waves_total, int prio_on, int4 share, int gens) {
+__global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const double2 *__restrict__ pxy_all, const int *__restrict__ pe_all,
+                                                      const int *__restrict__ pid_all, int waves_total, int4 share, int gens) {
     // the position arrays are kernel arguments of their own, restrict-qualified: the row operands are wave-uniform loads, and
     // the compiler only issues them as scalar loads (s_load: no vector-memory slot, no VGPRs) when it can prove that the
     // kernel's own stores and atomics (candidate slots, tickets) never touch them
@@ -201,7 +201,6 @@ __global__ __launch_bounds__(kScanThreads, (RJ == 8 ? 3 : 1)) void k_exh(const S
         if (u_lo >= cum + rows_s) { cum += rows_s; continue; }
         // segment of strip s: pair-rows [pa, pb)
         const int pa = (int)(u_lo - cum), pb = (int)min<long long>(rows_s, u_hi - cum);
-        const long long u_lo_now = u_lo;
         u_lo = cum + pb;
         cum += rows_s;
         const int Q0 = s * WEFF;
@@ -268,17 +267,6 @@ __global__ __launch_bounds__(kScanThreads, (RJ == 8 ? 3 : 1)) void k_exh(const S
         RowsXY nx = *reinterpret_cast<const RowsXY *>(pxy + p);
         RowsE ne = *reinterpret_cast<const RowsE *>(pe + p - 1);
         for (; p <= pb; p += kRowBatch) {
-            // A SIMD serves its oldest wave first: left alone, the four waves of a SIMD leave their rows one after the other
-            // (13, 21, 29, 36 us measured) and the last one runs alone, latency-bound, at half the issue rate.  Every wave has
-            // the same number of rows, so a wave raises its priority with the share of them it still has to do: whoever is
-            // behind goes first, and the waves of a SIMD finish together.
-            if (prio_on) {
-                const int lvl = (int)min<long long>(3, (u_hi - u_lo_now - (p - pa - 1)) * 4 / per);
-                if (lvl >= 3) __builtin_amdgcn_s_setprio(3);
-                else if (lvl == 2) __builtin_amdgcn_s_setprio(2);
-                else if (lvl == 1) __builtin_amdgcn_s_setprio(1);
-                else __builtin_amdgcn_s_setprio(0);
-            }
             const RowsXY cx4 = nx;
             const RowsE ce4 = ne;
             nx = *reinterpret_cast<const RowsXY *>(pxy + p + kRowBatch);

@@ -1,4 +1,4 @@
-// two_opt_first.hpp -- first-improvement steps, second form: k_first
+// two_opt_first.hpp -- first-improvement steps: k_first
 // Part of the GRID engine; included by two_opt_grid.hip only (one translation unit).
 #pragma once
 #include "two_opt_step.hpp"
@@ -7,9 +7,9 @@
 
 namespace tsp {
 
-// ---- first improvement (alg_2opt), second form: k_first ------------------------------------------------------
-// Same decisions as k_step<FIRST> (first improving pair after the cursor in (i<j) order, heuristics.c:452-486),
-// three things done differently, all about the latency of a step:
+// ---- first improvement (alg_2opt): k_first -------------------------------------------------------------------
+// The first improving pair after the cursor in (i<j) order (heuristics.c:452-486).  Unlike the tiled k_step, which
+// served this rule first, it is built around the latency of a step:
 //  * the grid is fixed and small (gy = 8 tile rows by 512 columns for one tour); a block takes ceil(chunk / gy) rows.
 //    No launch dispatches thousands of blocks that return at once, and -- arrivals on one word are served one
 //    after the other, ~12 ns each -- few blocks take tickets, on two levels (per tile row, then per tour);
@@ -171,19 +171,16 @@ __global__ __launch_bounds__(kScanThreads) void k_first(const StepArgs a) {
     // on the tour the scan saw: row r's adjacent columns are succ(r) and pred(r), when they are > r
     int ni = wi, nj = wj;  // new cursor
     if (!found) { ni = row_hi - 1; nj = n - 1; }
-    long long adj = 0;
-    if (a.count_evals) {
-        const u64 lo = make_key(ci, cj), hi = make_key(ni, nj);
-        long long c = 0;
-        for (int r = ci + tid; r <= ni; r += kScanThreads) {
-            const int p = mv.pos_of(r);
-            const int sc = mv.node_at(p + 1 == n ? 0 : p + 1), q = mv.node_at(p == 0 ? n - 1 : p - 1);
-            const u64 ks = make_key(r, sc), kq = make_key(r, q);
-            c += (sc > r && ks > lo && ks <= hi) ? 1 : 0;
-            c += (q > r && kq > lo && kq <= hi) ? 1 : 0;
-        }
-        adj = block_sum<long long>(c, s_ll);
+    const u64 lo = make_key(ci, cj), hi = make_key(ni, nj);
+    long long c = 0;
+    for (int r = ci + tid; r <= ni; r += kScanThreads) {
+        const int p = mv.pos_of(r);
+        const int sc = mv.node_at(p + 1 == n ? 0 : p + 1), q = mv.node_at(p == 0 ? n - 1 : p - 1);
+        const u64 ks = make_key(r, sc), kq = make_key(r, q);
+        c += (sc > r && ks > lo && ks <= hi) ? 1 : 0;
+        c += (q > r && kq > lo && kq <= hi) ? 1 : 0;
     }
+    const long long adj = block_sum<long long>(c, s_ll);
     TSP_STAMP(7);
     if (tid == 0) {
         int done = 0, n_ci = 0, n_cj = 0, n_chunk = st->chunk_rows, sweep_end = 0;

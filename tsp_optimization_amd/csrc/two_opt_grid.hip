@@ -8,7 +8,7 @@
 // implement a step (headers of the same name stem):
 //   two_opt_tiled.hpp  k_step      every pair of the scanned range visited, tile by tile; the block that arrives
 //                                  last picks the winner and reverses the segment.  Tabu runs, non-sqrt metrics,
-//                                  best improvement below TSP_SORTED_MIN_N nodes, first improvement as TSP_FIRST_V1.
+//                                  best improvement below TSP_SORTED_MIN_N nodes.
 //   two_opt_sweep.hpp  k_move_recs + k_sweep   best improvement on sqrt metrics: nodes ranked along a Hilbert
 //                                  curve, whole 64 x 64 blocks of pairs decided by the box form of the new-edge bound.
 //   two_opt_first.hpp  k_first     first improvement: small fixed grid, moves carried out of place by the next launch.
@@ -228,16 +228,13 @@ using namespace tsp;
 namespace {
 
 constexpr int kBestRJ = 2;
-constexpr int kFirstRJ = 1;
+constexpr int kFirstCols = 2;   // k_first: columns per lane
 
-template <int MODE>
-dim3 scan_grid(const tsp_dev_tours *t) {
+// the grid of k_step<BEST>
+dim3 best_grid(const tsp_dev_tours *t) {
     const int n = t->n;
-    const int RJ = MODE == TSP_2OPT_BEST ? kBestRJ : kFirstRJ;
-    const int gx = (n + kScanThreads * RJ - 1) / (kScanThreads * RJ);
-    int gy;
-    if (MODE == TSP_2OPT_BEST) gy = (n - 1 + t->best_rows_per_block - 1) / t->best_rows_per_block;
-    else gy = (std::min(t->first_max_rows, n - 1) + t->first_rows_per_block - 1) / t->first_rows_per_block;
+    const int gx = (n + kScanThreads * kBestRJ - 1) / (kScanThreads * kBestRJ);
+    const int gy = (n - 1 + t->best_rows_per_block - 1) / t->best_rows_per_block;
     return dim3(gx, gy, t->B);
 }
 
@@ -318,10 +315,9 @@ StepArgs make_args(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int
     a.recs = (mode == TSP_2OPT_BEST && t->use_recs && t->n >= 4096) ? t->d_rec : nullptr;
     a.partial_per_tour = t->partial_per_tour;
     a.n = t->n;
-    a.rows_per_block = mode == TSP_2OPT_BEST ? t->best_rows_per_block : t->first_rows_per_block;
+    a.rows_per_block = t->best_rows_per_block;
     a.first_min_rows = std::min(t->first_min_rows, std::max(1, t->n - 1));
     a.first_max_rows = 0;
-    a.count_evals = t->count_evals;
     a.iter = iter; a.tenure = tenure;
     a.margin = t->inst->filter_margin;
     a.prune = t->inst->prune_margin;
@@ -348,16 +344,8 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
             a.flat_slots = t->exh_blocks;
             const int wt_ = t->exh_blocks * (kScanThreads / 64);
             const dim3 g(t->exh_blocks, 1, t->B);
-            if (t->exh_lds > 65536 - 1024 && !t->exh_lds_granted) {   // one workgroup per CU: more than half of the CU's LDS
-                const void *f = t->exh_rj == 16 ? reinterpret_cast<const void *>(k_exh<WT, INT, 16>) : (t->exh_rj == 8 ? reinterpret_cast<const void *>(k_exh<WT, INT, 8>) : reinterpret_cast<const void *>(k_exh<WT, INT, 4>));
-                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, t->exh_lds) != hipSuccess) { (void)hipGetLastError(); t->exh_lds = 65536 - 1024; }
-                t->exh_lds_granted = true;
-            }
-            if (t->exh_rj == 16) hipLaunchKernelGGL((k_exh<WT, INT, 16>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_pxy, t->d_pe, t->d_pid, wt_, t->exh_prio, make_int4(t->exh_share[0], t->exh_share[1], t->exh_share[2], t->exh_share[3]), t->exh_gens);
-            else if (t->exh_rj == 8) hipLaunchKernelGGL((k_exh<WT, INT, 8>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_pxy, t->d_pe, t->d_pid, wt_, t->exh_prio, make_int4(t->exh_share[0], t->exh_share[1], t->exh_share[2], t->exh_share[3]), t->exh_gens);
-            else if (t->exh_rj == 2) hipLaunchKernelGGL((k_exh<WT, INT, 2>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_pxy, t->d_pe, t->d_pid, wt_, t->exh_prio, make_int4(t->exh_share[0], t->exh_share[1], t->exh_share[2], t->exh_share[3]), t->exh_gens);
-            else if (t->exh_rj == 1) hipLaunchKernelGGL((k_exh<WT, INT, 1>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_pxy, t->d_pe, t->d_pid, wt_, t->exh_prio, make_int4(t->exh_share[0], t->exh_share[1], t->exh_share[2], t->exh_share[3]), t->exh_gens);
-            else hipLaunchKernelGGL((k_exh<WT, INT, 4>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_pxy, t->d_pe, t->d_pid, wt_, t->exh_prio, make_int4(t->exh_share[0], t->exh_share[1], t->exh_share[2], t->exh_share[3]), t->exh_gens);
+            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_pxy, t->d_pe, t->d_pid, wt_,
+                               make_int4(t->exh_share[0], t->exh_share[1], t->exh_share[2], t->exh_share[3]), t->exh_gens);
             return TSP_OK;
         }
     }
@@ -376,7 +364,7 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
         }
     }
     if (mode == TSP_2OPT_BEST) {
-        const dim3 g = scan_grid<TSP_2OPT_BEST>(t);
+        const dim3 g = best_grid(t);
         if (a.recs)
             hipLaunchKernelGGL((k_recs<WT, INT>), dim3((t->n + kScanThreads - 1) / kScanThreads, t->B), dim3(kScanThreads), 0, s,
                                t->inst->d_coord, t->d_order, t->d_pos, t->d_state, t->d_rec, t->n);
@@ -388,19 +376,14 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
             hipLaunchKernelGGL((k_step<WT, INT, TSP_2OPT_BEST, kBestRJ, true>), g, dim3(kScanThreads), 0, s, a);
         else
             hipLaunchKernelGGL((k_step<WT, INT, TSP_2OPT_BEST, kBestRJ, false>), g, dim3(kScanThreads), 0, s, a);
-    } else if (!t->first_v1) {
+    } else {
         a.states = t->d_state_base; a.slot = t->slot;
         a.first_max_rows = t->first_max_rows2;
-        const int tj = kScanThreads * t->first_rj;
+        constexpr int tj = kScanThreads * kFirstCols;
         const dim3 g((t->n + tj - 1) / tj, t->first_grid_rows, t->B);
-        if (t->first_rj == 2) hipLaunchKernelGGL((k_first<WT, INT, 2>), g, dim3(kScanThreads), 0, s, a);
-        else hipLaunchKernelGGL((k_first<WT, INT, 1>), g, dim3(kScanThreads), 0, s, a);
+        hipLaunchKernelGGL((k_first<WT, INT, kFirstCols>), g, dim3(kScanThreads), 0, s, a);
         t->slot ^= 1;                                  // the launch's last block has written the other slot
         t->d_state = t->d_state_base + (size_t)t->slot * t->B;
-    } else {
-        const dim3 g = scan_grid<TSP_2OPT_FIRST>(t);
-        a.first_max_rows = (int)g.y * t->first_rows_per_block;
-        hipLaunchKernelGGL((k_step<WT, INT, TSP_2OPT_FIRST, kFirstRJ, false>), g, dim3(kScanThreads), 0, s, a);
     }
     return TSP_OK;
 }
@@ -416,20 +399,12 @@ int launch_step_rt(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int
 void launch_arm(tsp_dev_tours *t, int mode) {
     hipStream_t s = t->inst->ctx->stream;
     if (mode == TSP_2OPT_BEST) {
-        const dim3 g = scan_grid<TSP_2OPT_BEST>(t);
-        hipLaunchKernelGGL((k_arm<TSP_2OPT_BEST>), dim3(t->B), dim3(kScanThreads), 0, s, t->d_state, t->d_ticket,
-                           t->d_row_ticket, t->max_tile_rows, t->n,
-                           t->best_rows_per_block, (int)g.x, (int)g.y, kScanThreads * kBestRJ);
-    } else if (!t->first_v1) {
+        hipLaunchKernelGGL((k_arm<TSP_2OPT_BEST>), dim3(t->B), dim3(kScanThreads), 0, s, t->d_ticket, t->d_row_ticket, t->max_tile_rows);
+    } else {
         (void)hipMemsetAsync(t->d_ticket, 0, sizeof(int) * (size_t)t->B, s);   // k_first counts up from zero
         // both control-block slots start equal (a run on tours that are already done must find `done` in both)
         (void)hipMemcpyAsync(t->d_state_base + (size_t)(1 - t->slot) * t->B, t->d_state, sizeof(TourState) * (size_t)t->B,
                              hipMemcpyDeviceToDevice, s);
-    } else {
-        const dim3 g = scan_grid<TSP_2OPT_FIRST>(t);
-        hipLaunchKernelGGL((k_arm<TSP_2OPT_FIRST>), dim3(t->B), dim3(kScanThreads), 0, s, t->d_state, t->d_ticket,
-                           t->d_row_ticket, t->max_tile_rows, t->n,
-                           t->first_rows_per_block, (int)g.x, (int)g.y, kScanThreads * kFirstRJ);
     }
 }
 
@@ -482,30 +457,10 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
         burst = std::min(batch, burst * 2);
         if (max_steps >= 0) todo = std::min<int64_t>(todo, max_steps - queued);
         if (todo <= 0) break;
-        // A full batch of identical launches is replayed from a captured hipGraph (the kernel arguments
-        // never change: the descent is driven by the device-resident control block); partial batches and
-        // tabu runs (iter/tenure change per call) are launched directly.
-        bool replayed = false;
-        if (todo == batch && !tabu && t->use_graph && (mode == TSP_2OPT_BEST || t->first_v1)) {   // k_first alternates its slot argument
-            hipGraphExec_t &exec = t->graph_exec[mode];
-            if (!exec) {
-                hipGraph_t g = nullptr;
-                if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    for (int64_t k = 0; k < batch; ++k) launch_step_rt(t, mode, nullptr, 0, 0);
-                    if (hipStreamEndCapture(s, &g) == hipSuccess && g) {
-                        if (hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
-                        (void)hipGraphDestroy(g);
-                    }
-                }
-                if (!exec) { (void)hipGetLastError(); t->use_graph = 0; }
-            }
-            if (exec) { TSP_HIP_TRY(hipGraphLaunch(exec, s)); replayed = true; }
+        for (int64_t k = 0; k < todo; ++k) {
+            int rc = launch_step_rt(t, mode, tabu, iter, tenure);
+            if (rc) return rc;
         }
-        if (!replayed)
-            for (int64_t k = 0; k < todo; ++k) {
-                int rc = launch_step_rt(t, mode, tabu, iter, tenure);
-                if (rc) return rc;
-            }
         queued += todo;
         TSP_HIP_TRY(hipGetLastError());
         if (!sync) continue;
@@ -518,7 +473,7 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
     }
     if (tabu && t->tabu_list_run)   // the sweeps counted every non-adjacent pair; the skipped ones come off
         hipLaunchKernelGGL(k_tabu_fix_evals, dim3(1), dim3(64), 0, s, t->d_state, tabu->d_tabu_pairs);
-    if (sorted_run(t, mode, tabu) || exh_run(t, mode, tabu) || (mode == TSP_2OPT_FIRST && !t->first_v1)) {
+    if (sorted_run(t, mode, tabu) || exh_run(t, mode, tabu) || mode == TSP_2OPT_FIRST) {
         launch_flush(t);
         TSP_HIP_TRY(hipGetLastError());
         if (sync == 1) TSP_HIP_TRY(hipStreamSynchronize(s));   // sync == 2: the caller queues more work and waits once
@@ -1007,33 +962,18 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
     int auto_min = (int)std::min<long long>(32, std::max<long long>(4, pairs_budget / ((long long)B * inst->n)));
     auto_min = auto_min >= 32 ? 32 : (auto_min >= 16 ? 16 : (auto_min >= 8 ? 8 : 4));
     t->first_min_rows = std::max(1, TSP_SW(inst, FIRST_MIN_ROWS, auto_min));
-    t->first_rows_per_block =
-        std::min(kMaxRowsPerBlock, std::max(1, TSP_SW(inst, FIRST_ROWS_PER_BLOCK, std::min(8, t->first_min_rows))));
-    t->first_max_rows = std::max(t->first_min_rows, TSP_SW(inst, FIRST_MAX_ROWS, 2048));
-    {   // Every launch dispatches the grid of the LARGEST chunk (blocks beyond a tour's current chunk
-        // return at once, but dispatching them is not free): with many tours keep that grid near
-        // 16k blocks so that a step stays latency-sized.
-        const long long gx = (inst->n + kScanThreads * kFirstRJ - 1) / (kScanThreads * kFirstRJ);
-        const long long budget = std::max<long long>(1, 16384 / (gx * B));
-        const int cap = (int)std::max<long long>(t->first_min_rows, budget * t->first_rows_per_block);
-        t->first_max_rows = std::min(t->first_max_rows, cap);
-    }
     {   // k_first: a fixed grid of gy tile rows (<= 64: a block numbers the working blocks with one wave); a block
         // takes ceil(chunk / gy) <= kMaxRowsPerBlock rows.  Many tours: keep the launch near 16k blocks.
-        t->first_rj = TSP_SW(inst, FIRST_RJ, 2) == 2 ? 2 : 1;
-        const long long gx = (inst->n + kScanThreads * t->first_rj - 1) / (kScanThreads * t->first_rj);
+        const long long gx = (inst->n + kScanThreads * kFirstCols - 1) / (kScanThreads * kFirstCols);
         // every working block takes a ticket on one word (~12 ns each): few, fat blocks
         const int gy = (int)std::max<long long>(1, std::min<long long>(TSP_SW(inst, FIRST_GRID_ROWS, 8), 16384 / (gx * B)));
         t->first_grid_rows = std::min(64, gy);
         t->first_max_rows2 = std::max(t->first_min_rows, std::min(TSP_SW(inst, FIRST_MAX_ROWS, 2048), t->first_grid_rows * kMaxRowsPerBlock));
-        t->first_v1 = TSP_SW(inst, FIRST_V1, 0);
     }
     t->best_rows_per_block = std::min(kMaxRowsPerBlock, std::max(1, TSP_SW(inst, BEST_ROWS_PER_BLOCK, 32)));
-    t->count_evals = TSP_SW(inst, COUNT_EVALS, 1);
-    t->use_graph = TSP_SW(inst, USE_GRAPH, 0);
     const size_t bn = (size_t)B * inst->n;
-    const dim3 gb = scan_grid<TSP_2OPT_BEST>(t), gf = scan_grid<TSP_2OPT_FIRST>(t);
-    t->partial_per_tour = std::max((size_t)gb.x * gb.y, (size_t)gf.x * gf.y);
+    const dim3 gb = best_grid(t);
+    t->partial_per_tour = (size_t)gb.x * gb.y;
     t->partial_per_tour = std::max(t->partial_per_tour, (size_t)((inst->n + kScanThreads - 1) / kScanThreads) * t->first_grid_rows);
     t->sorted_min_n = TSP_SW(inst, SORTED_MIN_N, 1000);
     t->cl_sorted_min_n = TSP_SW(inst, SORTED_MIN_N, 8);
@@ -1073,39 +1013,33 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
     }
     if (inst->filter_margin > 1e299 && TSP_SW(inst, EXH_POS, 1) && inst->n >= 5 &&
         (inst->wtype == WT_EUC_2D_ICOORD || inst->wtype == WT_CEIL_2D_ICOORD || inst->wtype == WT_ATT_ICOORD)) {
-        // the exhaustive sweep in position order (two_opt_exh.hpp): EXH_WAVES waves per SIMD of one tour's grid, all resident
-        const int waves = std::max(1, std::min(8, TSP_SW(inst, EXH_WAVES, 4)));
+        // the exhaustive sweep in position order (two_opt_exh.hpp): four waves per SIMD of one tour's grid, all resident
+        constexpr int waves = 4;
         t->exh_blocks = std::max(1, std::min(2048, inst->ctx->num_cus * waves / std::max(1, B > 4 ? 4 : B)));
         // One tour: the grid is `waves` workgroups of four waves per CU, and every CU must get exactly that many -- the kernel is
-        // VALU-bound and the waves' shares are equal, so a CU that the dispatcher handed six workgroups finishes 1.5 x later than
-        // the mean (measured: waves leaving their rows between 13 and 40 us, mean 24.6).  Each workgroup therefore asks for
-        // 1 / waves of the CU's LDS (it uses none of it): one more does not fit.
-        if (B == 1 && inst->ctx->lds_bytes >= 65536 && TSP_SW(inst, EXH_EVEN, 1))
-            t->exh_lds = (waves == 1 ? (inst->ctx->lds_bytes * 3) / 5 : std::min(65536, inst->ctx->lds_bytes / waves)) - 1024;   // one per CU: more than half of it
-        const int rj = TSP_SW(inst, EXH_RJ, 4);
-        t->exh_prio = TSP_SW(inst, EXH_PRIO, 0);
-        t->exh_rj = (rj == 16 || rj == 8 || rj == 2 || rj == 1) ? rj : 4;
+        // VALU-bound, so a CU that the dispatcher handed six workgroups finishes 1.5 x later than the mean (measured with equal
+        // shares: waves leaving their rows between 13 and 40 us, mean 24.6).  Each workgroup therefore asks for 1 / waves of the
+        // CU's LDS (it uses none of it): one more does not fit.  (Below 64 KiB: no opt-in attribute needed.)
+        if (B == 1 && inst->ctx->lds_bytes >= 65536)
+            t->exh_lds = std::min(65536, inst->ctx->lds_bytes / waves) - 1024;
         t->partial_per_tour = std::max(t->partial_per_tour, (size_t)t->exh_blocks);
         const size_t pn = (size_t)B * (inst->n + kExhPad);
         TSP_HIP_TRY(hipMalloc(&t->d_pxy, pn * sizeof(double2)));
         TSP_HIP_TRY(hipMalloc(&t->d_pe, pn * sizeof(int)));
         TSP_HIP_TRY(hipMalloc(&t->d_pid, pn * sizeof(int)));
         {   // rows per wave for each of the `waves` equal parts of the grid (k_exh: the older a workgroup, the larger its share);
-            // TSP_EXH_SHARES = per-cent figures (or "0": equal shares), defaults measured on MI355X for 2 / 3 / 4 workgroups per CU
+            // TSP_EXH_SHARES = per-cent figures (or "0": equal shares), the default measured on MI355X
             t->exh_share[0] = t->exh_share[1] = t->exh_share[2] = t->exh_share[3] = 0;
             t->exh_gens = 0;
-            int pc[4] = {0, 0, 0, 0};
-            bool on = B == 1 && waves >= 2 && waves <= 4;
-            if (waves == 4) { pc[0] = 52; pc[1] = 28; pc[2] = 13; pc[3] = 7; }   // (tools/exh_shares.sh: 44.7 us per sweep against 45.7 with 53 / 26 / 13 / 8)
-            if (waves == 3) { pc[0] = 56; pc[1] = 29; pc[2] = 15; }
-            if (waves == 2) { pc[0] = 62; pc[1] = 38; }
+            int pc[4] = {52, 28, 13, 7};   // (tools/exh_shares.sh: 44.7 us per sweep against 45.7 with 53 / 26 / 13 / 8)
+            bool on = B == 1;
             const char *e = getenv("TSP_EXH_SHARES");
             if (e && *e) {
                 pc[0] = pc[1] = pc[2] = pc[3] = 0;
                 const int got = sscanf(e, "%d,%d,%d,%d", &pc[0], &pc[1], &pc[2], &pc[3]);
                 on = on && got == waves && pc[0] > 0;
             }
-            const int W = 64 * t->exh_rj, WEFF = W - 1, strips = (inst->n + WEFF - 1) / WEFF;
+            const int W = 64 * kExhRJ, WEFF = W - 1, strips = (inst->n + WEFF - 1) / WEFF;
             long long total = 0;
             for (int sidx = 0; sidx < strips; ++sidx) total += std::min(inst->n - 1, sidx * WEFF + WEFF - 1);
             const long long wtot = (long long)t->exh_blocks * (kScanThreads / 64);
@@ -1131,7 +1065,7 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
     TSP_HIP_TRY(hipMalloc(&t->d_ticket, (size_t)B * sizeof(int)));
     t->use_recs = TSP_SW(inst, BEST_RECS, 1);
     TSP_HIP_TRY(hipMalloc(&t->d_rec, (size_t)B * rec_per_tour * sizeof(NodeRec)));
-    t->max_tile_rows = std::max((int)gb.y, (int)gf.y);
+    t->max_tile_rows = (int)gb.y;
     TSP_HIP_TRY(hipMalloc(&t->d_row_ticket, (size_t)B * t->max_tile_rows * sizeof(int)));
     TSP_HIP_TRY(hipMalloc(&t->d_row_evals, (size_t)B * t->max_tile_rows * sizeof(int)));
     TSP_HIP_TRY(hipMalloc(&t->d_row_slot, (size_t)B * t->max_tile_rows * sizeof(Partial)));
@@ -1153,7 +1087,6 @@ void tsp_dev_tours_destroy(tsp_dev_tours *t) {
     (void)hipFree(t->d_cl_slots); (void)hipFree(t->d_cl_pairtab); (void)hipFree(t->d_cl_stats);
     (void)hipFree(t->d_chain); (void)hipHostFree(t->h_chain); (void)hipFree(t->d_order_snap); (void)hipFree(t->d_kick_result); (void)hipHostFree(t->h_kick_result); (void)hipHostFree(t->h_cl_err);
     (void)hipHostFree(t->h_state);
-    for (int m = 0; m < 2; ++m) if (t->graph_exec[m]) (void)hipGraphExecDestroy(t->graph_exec[m]);
     delete t;
 }
 
@@ -1290,14 +1223,14 @@ int tsp_dev_tours_device_ms(tsp_dev_tours *t, double *ms) {
 int tsp_dev_tours_describe(tsp_dev_tours *t, int mode, char *buf, int cap) {
     if (!t || !buf || cap < 1 || (mode != TSP_2OPT_FIRST && mode != TSP_2OPT_BEST)) return TSP_DEV_E_ARG;
     if (exh_run(t, mode, nullptr))
-        snprintf(buf, (size_t)cap, "k_move_pos + k_exh<RJ=%d> x %d workgroups (every delta expression, tour-position order)", t->exh_rj, t->exh_blocks);
+        snprintf(buf, (size_t)cap, "k_move_pos + k_exh<RJ=%d> x %d workgroups (every delta expression, tour-position order)", kExhRJ, t->exh_blocks);
     else if (sorted_run(t, mode, nullptr))
         snprintf(buf, (size_t)cap, "k_move_recs + k_sweep x %d workgroups (sorted sweep, box bound)", t->sweep_blocks);
     else if (mode == TSP_2OPT_BEST)
         snprintf(buf, (size_t)cap, "%sk_step<BEST> (tiled sweep%s)", t->use_recs && t->n >= 4096 ? "k_recs + " : "",
                  t->inst->filter_margin > 1e299 ? ", every delta expression" : ", bound tiers");
     else
-        snprintf(buf, (size_t)cap, "%s", t->first_v1 ? "k_step<FIRST>" : "k_first");
+        snprintf(buf, (size_t)cap, "%s", "k_first");
     return TSP_OK;
 }
 

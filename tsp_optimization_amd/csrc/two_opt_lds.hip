@@ -61,8 +61,8 @@ template <int WT, bool INT, int MODE, bool CACHE, bool F32>
 __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__restrict__ coord_g,
                                                              int *__restrict__ orders_g,
                                                              TourState *__restrict__ states, int n, int rmin,
-                                                             int rmax, int count_evals, int max_iters, double margin, double prune,
-                                                             int probe, int probe2, double org_x, double org_y) {
+                                                             int rmax, int max_iters, double margin, double prune,
+                                                             int probe, double org_x, double org_y) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     NodeRec *s_rows = reinterpret_cast<NodeRec *>(smem);
     double2 *coord = reinterpret_cast<double2 *>(smem + sizeof(NodeRec) * kLdsRows);
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__re
     long long sweeps = st->sweeps, evals = st->evals, moves = st->moves, reversed = st->reversed,
               scanned = st->pairs_scanned, steps = st->steps;
     bool probe_on = true;                       // FIRST: the last hit lay within `probe` pairs of the cursor
-    bool after_hit = true;                      // FIRST: the step before found a move (TSP_LDS_PROBE2=1: the second round only then)
+    bool after_hit = true;                      // FIRST: the step before found a move (the second probe round runs only then)
     // Evaluation count: pairs between the old and the new cursor minus the adjacent ones among them (heuristics.c:471).  The
     // adjacent pairs telescope over the steps of a sweep (two_opt_cluster.hip has the derivation): with A(K) = tour edges whose
     // pair key is <= K, a sweep's total is A_now(cursor) - A(cursor at the start) - sum over its moves of
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__re
     if (tid < 2) s_vote[tid] = 0;
     __syncthreads();
     if constexpr (MODE == TSP_2OPT_FIRST) {
-        if (count_evals && (ci != 0 || cj != 0)) { adjA0 = edges_upto(make_key(ci, cj)); sweep_open = true; }
+        if (ci != 0 || cj != 0) { adjA0 = edges_upto(make_key(ci, cj)); sweep_open = true; }
     }
     if constexpr (CACHE) {
         for (int p = tid; p < n; p += kLdsThreads) {
@@ -240,7 +240,8 @@ __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__re
                 // has reported one (s_flag, an LDS minimum); the adjacent pairs up to the winner are counted per thread into
                 // adj_acc (summed once per launch).  Rows of >= 591 columns only: the 4 608 pairs then span at most nine rows
                 // and never reach the end of the sweep.
-                if (!probe_hit && probe2 && (probe2 > 1 || after_hit) && ci <= n - 600) {   // (4 and 8 rounds measure alike, 12 and more lose: configs[4] 227 / 227 / 229 / 233 / 242 ms at 4 / 8 / 12 / 16 / 24)
+                // Only in the step right after a move: after every first-round miss it measured 2.4 % slower.
+                if (!probe_hit && after_hit && ci <= n - 600) {   // (4 and 8 rounds measure alike, 12 and more lose: configs[4] 227 / 227 / 229 / 233 / 242 ms at 4 / 8 / 12 / 16 / 24)
                     constexpr int NWV = kLdsThreads / 64, R2 = 8;
                     long long *s_t2 = s_ll + 8;                                  // per wave: smallest pair number with a hit
                     double *s_d2 = s_d + 8;
@@ -497,13 +498,11 @@ __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__re
             // a probe hit carries the positions and successors along: nobody reads the tour between its vote and the swaps,
             // so the barrier that otherwise separates those reads from the swaps is not needed
             const int pa = probe_hit ? win.x : (int)pos[wi], pb = probe_hit ? win.y : (int)pos[wj];
-            if constexpr (MODE == TSP_2OPT_FIRST) {
-                if (count_evals) {   // d of this move, on the tour as it is before the move
-                    const int a1 = probe_hit ? win.z : (int)order[pa + 1 == n ? 0 : pa + 1], b1 = probe_hit ? win.w : (int)order[pb + 1 == n ? 0 : pb + 1];
-                    const u64 hi = make_key(wi, wj);
-                    auto le = [&](int u, int v) { return make_key(min(u, v), max(u, v)) <= hi ? 1 : 0; };
-                    adjD += 1 + le(a1, b1) - le(wi, a1) - le(wj, b1);
-                }
+            if constexpr (MODE == TSP_2OPT_FIRST) {   // d of this move, on the tour as it is before the move
+                const int a1 = probe_hit ? win.z : (int)order[pa + 1 == n ? 0 : pa + 1], b1 = probe_hit ? win.w : (int)order[pb + 1 == n ? 0 : pb + 1];
+                const u64 hi = make_key(wi, wj);
+                auto le = [&](int u, int v) { return make_key(min(u, v), max(u, v)) <= hi ? 1 : 0; };
+                adjD += 1 + le(a1, b1) - le(wi, a1) - le(wj, b1);
             }
             float new_edge = 0.f;
             if constexpr (CACHE) {
@@ -617,10 +616,8 @@ __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__re
     // ---- write back ---------------------------------------------------------------------------------------
     __syncthreads();
     if constexpr (MODE == TSP_2OPT_FIRST) {
-        if (count_evals) {
-            if (sweep_open) adj_seen += edges_upto(make_key(ci, cj)) - adjA0 - adjD;   // the sweep goes on in the next launch
-            evals -= adj_seen;
-        }
+        if (sweep_open) adj_seen += edges_upto(make_key(ci, cj)) - adjA0 - adjD;   // the sweep goes on in the next launch
+        evals -= adj_seen;
     }
     for (int v = tid; v < n; v += kLdsThreads) order_g[v] = (int)order[v];
     if (tid == 0) {
@@ -654,7 +651,7 @@ hipError_t launch_lds_k(tsp_dev_tours *t, int rmin, int rmax, int max_iters) {
         granted = bytes;
     }
     hipLaunchKernelGGL(k, dim3(t->B), dim3(kLdsThreads), bytes, s, t->inst->d_coord, t->d_order, t->d_state, t->n,
-                       rmin, rmax, t->count_evals, max_iters, t->inst->filter_margin, t->inst->prune_margin, TSP_SW(t->inst, LDS_PROBE, 65536), TSP_SW(t->inst, LDS_PROBE2, 1),
+                       rmin, rmax, max_iters, t->inst->filter_margin, t->inst->prune_margin, TSP_SW(t->inst, LDS_PROBE, 65536),
                        t->inst->org_x, t->inst->org_y);
     return hipGetLastError();
 }

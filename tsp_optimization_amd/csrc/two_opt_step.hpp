@@ -59,23 +59,6 @@ __device__ __forceinline__ void read_partial(const Partial *slot, double &delta,
 // once and take no ticket).  Block (bx, by) is skipped iff bx < (r0(by) + 1) / TJ.
 __device__ __forceinline__ int skipped_in_tile_row(int r0, int gx, int TJ) { return min(gx, (r0 + 1) / TJ); }
 
-__device__ __forceinline__ int count_active_blocks(int row_lo, int row_hi, int rpb, int gx, int gy, int TJ,
-                                                   int *scratch) {
-    const int tile_rows = min((row_hi - row_lo + rpb - 1) / rpb, gy);
-    int c = 0;
-    for (int by = threadIdx.x; by < tile_rows; by += (int)blockDim.x)
-        c += gx - skipped_in_tile_row(row_lo + by * rpb, gx, TJ);
-    return block_sum<int>(c, scratch);
-}
-
-template <int MODE>
-__device__ __forceinline__ void active_rows(const TourState *st, int n, int &row_lo, int &row_hi) {
-    row_lo = 0; row_hi = n - 1;
-    if constexpr (MODE == TSP_2OPT_FIRST) {
-        row_lo = st->ci;
-        row_hi = min(st->ci + st->chunk_rows, n - 1);
-    }
-}
 
 // ---- tour cost ----------------------------------------------------------------------------
 // Sum over nodes of d(v, succ v) in node order (tabusearch.c:168-172), by one whole block.
@@ -167,7 +150,7 @@ struct StepArgs {
     int *tabu;
     const NodeRec *recs;   // BEST: materialised by k_recs before the step; nullptr = derive per tile
     size_t partial_per_tour;
-    int n, rows_per_block, first_min_rows, first_max_rows, count_evals, iter, tenure;
+    int n, rows_per_block, first_min_rows, first_max_rows, iter, tenure;
     int slot;          // k_first: which of the tour's two control blocks this launch reads (the other is written)
     double margin;     // root filter (tsp_dist.hpp); 1e300 = every pair is evaluated exactly
     double prune;      // new-edge bound margin (tsp_dist.hpp); 1e300 = never prune
@@ -193,9 +176,8 @@ __device__ __forceinline__ void apply_step(const StepArgs &a, int tour, int row_
 #endif
                                            , double *chunk_buf = nullptr   // FLAT: 4096 doubles of LDS the caller no longer needs
 ) {
-    constexpr int TJ = kScanThreads * RJ;
     const int n = a.n, rpb = a.rows_per_block;
-    const int gx = gridDim.x, gy = gridDim.y;
+    const int gy = gridDim.y;
     TourState *st = a.states + tour;
     const int tid = threadIdx.x;
     int *order = a.orders + (size_t)tour * n;
@@ -211,13 +193,12 @@ __device__ __forceinline__ void apply_step(const StepArgs &a, int tour, int row_
     __shared__ double s_d[kScanThreads / 64];
     __shared__ u64 s_k[kScanThreads / 64];
     __shared__ long long s_ll[kScanThreads / 64];
-    __shared__ int s_i32[kScanThreads / 64];
 
     // BEST: one pre-reduced candidate per tile row; FLAT (sorted sweep): one candidate per block, all live
-    constexpr bool HIER = MODE == TSP_2OPT_BEST && !FLAT;
-    const int ci = MODE == TSP_2OPT_FIRST ? st->ci : 0, cj = MODE == TSP_2OPT_FIRST ? st->cj : 0;
+    static_assert(MODE == TSP_2OPT_BEST, "first improvement runs through k_first");
+    constexpr bool HIER = !FLAT;
     const int tile_rows = min((row_hi - row_lo + rpb - 1) / rpb, gy);
-    const int nslots = FLAT ? a.flat_slots : (HIER ? tile_rows : tile_rows * gx);
+    const int nslots = FLAT ? a.flat_slots : tile_rows;
     if constexpr (HIER) part = a.row_slots + (size_t)tour * a.max_tile_rows;
 
     // 1. winner over the blocks that published a candidate (loads batched: they are sc1 loads
@@ -231,15 +212,14 @@ __device__ __forceinline__ void apply_step(const StepArgs &a, int tour, int row_
 #pragma unroll
         for (int k = 0; k < PU; ++k) {
             const int s = s0 + k * kScanThreads;
-            const int by = s / gx, bx = s - by * gx;
-            live[k] = s < nslots && (HIER || FLAT || bx >= skipped_in_tile_row(row_lo + by * rpb, gx, TJ));
+            live[k] = s < nslots;
             pd[k] = 0.0; pi[k] = -1; pj[k] = -1;
             if (live[k]) read_partial(part + s, pd[k], pi[k], pj[k]);
         }
 #pragma unroll
         for (int k = 0; k < PU; ++k) {
             const u64 kk = make_key(pi[k], pj[k]);
-            const bool take = live[k] && ((MODE == TSP_2OPT_BEST) ? better(pd[k], kk, bd, key) : (kk < key));
+            const bool take = live[k] && better(pd[k], kk, bd, key);
             if (take) { bd = pd[k]; key = kk; }
             if constexpr (TABU) {
                 if (live[k])
@@ -249,38 +229,18 @@ __device__ __forceinline__ void apply_step(const StepArgs &a, int tour, int row_
             }
         }
     }
-    block_argmin<MODE == TSP_2OPT_BEST>(bd, key, s_d, s_k);
+    block_argmin<true>(bd, key, s_d, s_k);
     TSP_STAMP(6);
     if constexpr (TABU) tabu_evals = block_sum<long long>(tabu_evals, s_ll);
-    const bool found = key != kNoKey && (MODE == TSP_2OPT_FIRST || bd < 0);
+    const bool found = key != kNoKey && bd < 0;
     const int wi = found ? key_i(key) : -1, wj = found ? key_j(key) : -1;
     int pa = 0, pb = 0;
     if (found) { pa = pos[wi]; pb = pos[wj]; }
 
-    // 2. FIRST: how many pairs between the old and the new cursor the reference would have skipped
-    //    as adjacent (heuristics.c:471), on the tour the scan saw.  Row r's adjacent columns are
-    //    succ(r) and pred(r), when they are > r.
-    long long adj = 0;
-    int ni = wi, nj = wj;  // new cursor
-    if constexpr (MODE == TSP_2OPT_FIRST) {
-        if (!found) { ni = row_hi - 1; nj = n - 1; }
-        if (a.count_evals) {
-            const u64 lo = make_key(ci, cj), hi = make_key(ni, nj);
-            long long c = 0;
-            for (int r = ci + tid; r <= ni; r += kScanThreads) {
-                const int p = pos[r];
-                const int s = order[p + 1 == n ? 0 : p + 1], q = order[p == 0 ? n - 1 : p - 1];
-                const u64 ks = make_key(r, s), kq = make_key(r, q);
-                c += (s > r && ks > lo && ks <= hi) ? 1 : 0;
-                c += (q > r && kq > lo && kq <= hi) ? 1 : 0;
-            }
-            adj = block_sum<long long>(c, s_ll);
-        }
-    }
     __syncthreads();  // every read of the old order/pos is done
     TSP_STAMP(7);
 
-    // 3. the move: reverse positions pa+1 .. pb (cyclic)
+    // 2. the move: reverse positions pa+1 .. pb (cyclic)
     int L = 0;
     if (found) { L = pb - pa; if (L < 0) L += n; }
     if (found && !FLAT) {   // FLAT: the move is left to the next launch of k_move_recs (all blocks, not one)
@@ -307,67 +267,33 @@ __device__ __forceinline__ void apply_step(const StepArgs &a, int tour, int row_
     }
 
     TSP_STAMP(8);
-    // 4. BEST at the local optimum: recomputed cost
+    // 3. at the local optimum: recomputed cost
     double final_cost = 0.0;
-    if constexpr (MODE == TSP_2OPT_BEST) {
-        if (!found) {
-            // the sequential cost of non-integer lengths is staged through 32 KB of LDS: the sweep lends its staging
-            // area (its own 32 KB would cost the float-cost variants two thirds of their resident blocks)
-            __shared__ double s_chunk[(INT || WT == WT_CEIL_2D || FLAT) ? 1 : 4096];
-            final_cost = tour_cost_block<WT, INT>(a.coord, order, pos, n, s_d, FLAT ? chunk_buf : s_chunk);
-        }
+    if (!found) {
+        // the sequential cost of non-integer lengths is staged through 32 KB of LDS: the sweep lends its staging
+        // area (its own 32 KB would cost the float-cost variants two thirds of their resident blocks)
+        __shared__ double s_chunk[(INT || WT == WT_CEIL_2D || FLAT) ? 1 : 4096];
+        final_cost = tour_cost_block<WT, INT>(a.coord, order, pos, n, s_d, FLAT ? chunk_buf : s_chunk);
     }
 
-    // 5. next cursor / chunk, and the ticket for the next launch
-    int done = 0, n_ci = 0, n_cj = 0, n_chunk = st->chunk_rows, sweep_end = 0;
-    double obj = st->obj, seen = st->seen_cost;
-    if constexpr (MODE == TSP_2OPT_BEST) {
-        if (found) { obj = st->obj; } else { done = 1; obj = final_cost; }
-    } else {
-        if (found) {
-            obj += bd;                               // heuristics.c:486
-            n_ci = wi; n_cj = wj; n_chunk = a.first_min_rows;
-        } else {
-            n_chunk = min(st->chunk_rows * 2, a.first_max_rows);
-            if (row_hi >= n - 1) {                   // sweep complete
-                sweep_end = 1;
-                if (obj >= seen) done = 1;           // heuristics.c:492
-                else { seen = obj; n_ci = 0; n_cj = 0; }
-            } else { n_ci = row_hi - 1; n_cj = n - 1; }
-        }
-    }
-    int next_lo = 0, next_hi = n - 1;
-    if constexpr (MODE == TSP_2OPT_FIRST) { next_lo = n_ci; next_hi = min(n_ci + n_chunk, n - 1); }
-    int next_active = 0;
+    // 4. the tickets for the next launch
+    const int done = found ? 0 : 1;
+    const double obj = found ? st->obj : final_cost;
     if constexpr (HIER) {   // count-up tickets back to zero for the next launch
         for (int k = tid; k < tile_rows; k += kScanThreads)
             __hip_atomic_store((gi32 *)(a.row_tickets + (size_t)tour * a.max_tile_rows + k), 0, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-    } else if constexpr (!FLAT) {
-        next_active = count_active_blocks(next_lo, next_hi, rpb, gx, gy, TJ, s_i32);
     }
 
     if (tid == 0) {
         st->steps += 1;
-        if constexpr (MODE == TSP_2OPT_BEST) {
-            st->sweeps += 1;
-            st->evals += TABU ? tabu_evals : (long long)n * (n - 1) / 2 - n;  // non-adjacent pairs (n >= 4)
-            st->pairs_scanned += (long long)n * (n - 1) / 2;
-            if (found) { st->moves += 1; st->reversed += L - 1; }
-        } else {
-            const long long r_old = pair_rank(ci, cj, n);
-            st->pairs_scanned += pair_rank(row_hi - 1, n - 1, n) - r_old;
-            st->evals += pair_rank(ni, nj, n) - r_old - adj;
-            if (found) { st->moves += 1; st->reversed += L - 1; }   // successors rewritten by utility.c:710-717
-            st->sweeps += sweep_end;
-            st->ci = n_ci; st->cj = n_cj; st->chunk_rows = n_chunk; st->seen_cost = seen;
-        }
+        st->sweeps += 1;
+        st->evals += TABU ? tabu_evals : (long long)n * (n - 1) / 2 - n;  // non-adjacent pairs (n >= 4)
+        st->pairs_scanned += (long long)n * (n - 1) / 2;
+        if (found) { st->moves += 1; st->reversed += L - 1; }
         st->obj = obj;
         st->done = done;
         if constexpr (FLAT) { st->parity = cur_parity; st->pending = found ? 1 : 0; st->mv_pa = pa; st->mv_pb = pb; }
-        if constexpr (!HIER && !FLAT)
-            __hip_atomic_store((gi32 *)(a.tickets + tour), done ? 0 : next_active, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
 #ifdef TSP_STAMPS
         stamps[9] = wall_clock64();
         for (int k = 1; k < 10; ++k) atomicAdd(&g_stamp_sum[k], stamps[k] - stamps[k - 1]);
