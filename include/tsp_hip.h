@@ -307,6 +307,40 @@ int tsp_dev_multistart_allreduce_f64_group(tsp_dev_comm *const *comms, int ndev,
 int tsp_dev_multistart_bcast_tour_group(tsp_dev_comm *const *comms, int ndev, int root, const int *succ_root, int succ_stride,
                                         int n, int read_back_rank, int *succ_out);
 
+/* ---- Or-opt (extension; the reference declares HEU_3opt, include/heuristics.h:51-56, and never defines it) ------------------
+ * A move takes a segment f -> .. -> l of L = 1..3 nodes (p = pred f, s = succ l) out of the tour and puts it between a and
+ * b = succ a, a not in {p, f .. l}, forward (a f .. l b) or reversed (a l .. f b; L > 1):
+ *     delta = ((d(a,f) + d(l,b)) - d(a,b)) - ((d(p,f) + d(l,s)) - d(p,s))      [reversed: (d(a,l) + d(f,b)) in the first bracket]
+ * Each decision takes the improving move (delta < 0) of smallest delta, ties -> smallest key ((f*3 + L-1)*n + a)*2 + o
+ * (o = 1 reversed; node ids).  n(5n - 16) moves per decision; n < 5 returns TSP_OK with the tours unchanged. */
+typedef struct {
+    int64_t sweeps;          /* decisions taken: moves + the last one, which found no improving move                    */
+    int64_t evals;           /* sum of n(5n - 16) over the decisions (the logical count, as tsp_two_opt_stats.evals)     */
+    int64_t moves;           /* applied Or-opt moves                                                                     */
+    int64_t moves_by_len[3]; /* ... of segments of 1, 2, 3 nodes                                                         */
+    int64_t moves_reversed;  /* ... that inserted the segment reversed                                                   */
+    int64_t deltas_executed; /* delta expressions the device actually ran (a full scan per decision, or the incremental
+                                path: the rows a move touched rescanned, every other row checked on the new edges); a
+                                full scan's count includes the lanes that own no row: about 1.04 x n(5n - 16)           */
+    int64_t rounds;          /* tsp_dev_two_opt_or_opt: 2-opt + Or-opt rounds; 0 from tsp_dev_or_opt                     */
+    double seconds;          /* wall time of the call, host clock                                                        */
+    double device_ms;        /* device time of the call, HIP events on the engine's stream                               */
+} tsp_or_opt_stats;
+
+/* Or-opt descent (best improvement, as above) of B tours until no move improves or max_moves moves (max_moves < 0:
+ * unlimited).  obj[B] out: the recomputed cost of the final tour (as tsp_dev_two_opt's BEST mode leaves it), not a sum of
+ * deltas.  time_limit_s <= 0 = unlimited; on expiry TSP_TIME_LIMIT_EXCEEDED with the tours as they stand (valid) and their
+ * costs.  stats may be NULL, else B entries. */
+int tsp_dev_or_opt(tsp_dev_inst *inst, int B, int *succ, int succ_stride, int64_t tour_stride,
+                   double *obj, int64_t max_moves, double time_limit_s, tsp_or_opt_stats *stats);
+/* 2-opt + Or-opt: per tour, tsp_dev_two_opt(two_opt_mode, TSP_ENGINE_AUTO) then an Or-opt descent, repeated until an Or-opt
+ * descent makes no move; the result is a local optimum of both neighbourhoods.  obj[B] in/out (in: as tsp_dev_two_opt
+ * takes it; out: the recomputed cost).  One time budget over all phases.  The stats (NULL, or B entries each) sum the
+ * phases of each tour; or_opt_stats[b].rounds = rounds. */
+int tsp_dev_two_opt_or_opt(tsp_dev_inst *inst, int two_opt_mode, int B, int *succ, int succ_stride,
+                           int64_t tour_stride, double *obj, double time_limit_s,
+                           tsp_two_opt_stats *two_opt_stats, tsp_or_opt_stats *or_opt_stats);
+
 #ifdef __cplusplus
 }
 #endif

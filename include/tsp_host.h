@@ -49,7 +49,10 @@ typedef enum {                                                                  
     SOLVE_2OPT_GRASP, SOLVE_2OPT_GRASP_ITER, SOLVE_2OPT_GREEDY, SOLVE_2OPT_GREEDY_ITER, SOLVE_2OPT_EXTR_MIL,
     SOLVE_VNS, SOLVE_TABU_STEP, SOLVE_TABU_LIN, SOLVE_TABU_RAND, SOLVE_GENETIC,
     SOLVE_2OPT_GRASP_MULTI,  /* extension of this build (after the reference's last value): BASELINE configs[3] */
-    SOLVE_2OPT_POP_MULTI     /* extension: BASELINE configs[4], random individuals + alg_2opt each, sharded over the GPUs */
+    SOLVE_2OPT_POP_MULTI,    /* extension: BASELINE configs[4], random individuals + alg_2opt each, sharded over the GPUs */
+    SOLVE_2OPT_OR_GREEDY,    /* extension: greedy, then 2-opt + Or-opt to a joint local optimum (alg_2opt_oropt) */
+    SOLVE_2OPT_OR_GRASP,     /* extension: grasp, then alg_2opt_oropt */
+    SOLVE_2OPT_OR_EXTR_MIL   /* extension: extra mileage, then alg_2opt_oropt */
 } solver_type;
 
 typedef enum { UDIR_EDGE, DIR_EDGE } edge_type;                                          /* :99-102 */
@@ -116,6 +119,16 @@ int HEU_2opt_grasp_iter(instance *inst);                                        
 int HEU_2opt_greedy(instance *inst);                                                     /* :572 */
 int HEU_2opt_greedy_iter(instance *inst);                                                /* :584 */
 int HEU_2opt_extramileage(instance *inst);                                               /* :596 */
+
+/* ---- Or-opt (extension: the reference declares HEU_3opt, include/heuristics.h:51-56, and never defines it; Or-opt is
+ * not 3-opt and does not take that name).  Both leave the RECOMPUTED cost of the final tour in inst->solution.obj_best --
+ * unlike alg_2opt after HEU_Grasp, which carries GRASP's double-counted closing edge (heuristics.c:135,:152) along. */
+int alg_oropt(instance *inst);        /* Or-opt descent (tsp_dev_or_opt) of inst->solution                          */
+int alg_2opt_oropt(instance *inst);   /* alg_2opt's rule (first improvement) and Or-opt in turn until Or-opt makes no
+                                         move (tsp_dev_two_opt_or_opt): a local optimum of both neighbourhoods           */
+int HEU_2opt_oropt_greedy(instance *inst);        /* HEU_greedy + alg_2opt_oropt       */
+int HEU_2opt_oropt_grasp(instance *inst);         /* HEU_Grasp + alg_2opt_oropt        */
+int HEU_2opt_oropt_extramileage(instance *inst);  /* HEU_extramileage + alg_2opt_oropt */
 
 /* ---- src/tabusearch.c (externally linked there, not in its header) --------------------------- */
 int alg_2opt_tabu(instance *inst, int *skip_edge, int *stored_prev, const int iter, const int tenure); /* :107 */
@@ -217,6 +230,9 @@ int tsp_host_random_lookahead(void);
 double tsp_host_last_driver_loop_seconds(void);
 /* Counters of the last alg_2opt / alg_2opt_tabu call of this thread. */
 void tsp_host_last_stats(long long *sweeps, long long *evals, long long *moves, double *device_ms);
+/* Counters of the Or-opt phases of the last alg_oropt / alg_2opt_oropt call of this thread (rounds = 0 after alg_oropt);
+ * the 2-opt phases of alg_2opt_oropt go to tsp_host_last_stats. */
+void tsp_host_last_or_stats(tsp_or_opt_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */
 void tsp_host_shutdown(void);
 

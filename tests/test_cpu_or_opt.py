@@ -1,0 +1,184 @@
+"""Or-opt (extension): the tests' CPU reference (tests/or_opt_ref.py) against a plain enumeration of the definition in
+include/tsp_hip.h, and the new entry points of the C ABI.  No GPU needed."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import or_opt_ref as R
+from helpers import random_tour
+from oracle import oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def enumerate_moves(D, succ):
+    """Every (f, L, a, o) of the definition, node by node -> list of (delta, key, f, L, a, o)."""
+    n = len(succ)
+    pred = np.empty(n, dtype=np.int64)
+    pred[succ] = np.arange(n)
+    out = []
+    for f in range(n):
+        for L in (1, 2, 3):
+            x = [f]
+            for _ in range(L - 1):
+                x.append(int(succ[x[-1]]))
+            l, p = x[-1], int(pred[f])
+            s = int(succ[l])
+            rem = (D[p, f] + D[l, s]) - D[p, s]
+            for a in range(n):
+                if a == p or a in x:
+                    continue
+                b = int(succ[a])
+                for o in ((0,) if L == 1 else (0, 1)):
+                    ins = (D[a, f] + D[l, b]) - D[a, b] if o == 0 else (D[a, l] + D[f, b]) - D[a, b]
+                    out.append((ins - rem, R.key(f, L, a, o, n), f, L, a, o))
+    return out
+
+
+def brute_best(moves):
+    imp = [m for m in moves if m[0] < 0.0]
+    return min(imp, key=lambda m: (m[0], m[1])) if imp else None
+
+
+def check_one(xy, wt, succ, integer_cost=1):
+    D = O.dist_matrix(xy, wt, integer_cost)
+    n = len(succ)
+    moves = enumerate_moves(D, succ)
+    assert len(moves) == R.n_moves(n) == n * (5 * n - 16)
+    assert len({m[1] for m in moves}) == len(moves)          # keys are unique
+    bb = brute_best(moves)
+    got = R.decide(D, succ)
+    if bb is None:
+        assert got is None
+        return None
+    assert got == (bb[0], bb[1])
+    f, L, a, o = R.decode(bb[1], n)
+    assert (f, L, a, o) == bb[2:]
+    new = R.apply_move(succ, f, L, a, o)
+    assert O.is_tour(new)
+    # the applied move changes the cost by exactly delta (integer costs)
+    if integer_cost:
+        assert O.succ_cost(xy, wt, new, 1) == O.succ_cost(xy, wt, succ, 1) + bb[0]
+    s1, c = R.or_opt_descent(xy, wt, succ, integer_cost, max_moves=1, D=D)
+    assert (s1 == new).all() and c["moves"] == 1 and c["sweeps"] == 1 and c["evals"] == R.n_moves(n)
+    return bb
+
+
+@pytest.mark.parametrize("n", list(range(5, 13)))
+def test_reference_matches_enumeration_random(n):
+    rng = np.random.default_rng(100 + n)
+    for rep in range(6):
+        xy = rng.integers(0, 100, size=(n, 2)).astype(np.float64)
+        succ = random_tour(n, rng)
+        check_one(xy, O.EUC_2D, succ, 1)
+        check_one(xy, O.EUC_2D, succ, 0)   # --fcost: the fp64 evaluation order of the definition
+
+
+def test_reference_matches_enumeration_lattice_ties():
+    """6 x 6 integer grid: many moves share the best delta, the key decides."""
+    g = np.array([(x, y) for x in range(6) for y in range(6)], dtype=np.float64) * 10
+    rng = np.random.default_rng(7)
+    ties = 0
+    for rep in range(8):
+        succ = random_tour(len(g), rng)
+        D = O.dist_matrix(g, O.EUC_2D, 1)
+        moves = enumerate_moves(D, succ)
+        bb = brute_best(moves)
+        ties += sum(1 for m in moves if m[0] == bb[0]) > 1
+        check_one(g, O.EUC_2D, succ, 1)
+    assert ties > 0
+
+
+def test_reference_descent_ends_at_local_optimum():
+    rng = np.random.default_rng(3)
+    xy = rng.integers(0, 1000, size=(40, 2)).astype(np.float64)
+    succ = random_tour(40, rng)
+    out, c = R.or_opt_descent(xy, O.EUC_2D, succ, 1)
+    assert O.is_tour(out) and c["moves"] > 0 and c["sweeps"] == c["moves"] + 1
+    assert sum(c["moves_by_len"]) == c["moves"]
+    D = O.dist_matrix(xy, O.EUC_2D, 1)
+    assert brute_best(enumerate_moves(D, out)) is None
+    assert R.is_or_opt_optimal(xy, O.EUC_2D, out, 1)
+    assert R.min_delta(xy, O.EUC_2D, succ, 1, chunk=7) == min(m[0] for m in enumerate_moves(D, succ))
+
+
+def test_reference_small_n_is_a_no_op():
+    xy = np.array([[0, 0], [5, 1], [2, 7], [9, 9]], dtype=np.float64)
+    succ = np.array([1, 2, 3, 0], dtype=np.int32)
+    out, c = R.or_opt_descent(xy, O.EUC_2D, succ, 1)
+    assert (out == succ).all() and c["sweeps"] == c["moves"] == c["evals"] == 0
+
+
+def test_or_opt_entry_points_declared_and_exported():
+    from tsp_optimization_amd import engine as E
+    with open(os.path.join(ROOT, "include", "tsp_hip.h")) as f:
+        hdr = f.read()
+    for name in ("tsp_dev_or_opt", "tsp_dev_two_opt_or_opt"):
+        assert re.search(r"\bint %s\s*\(" % name, hdr)
+        assert name in E.EXPORTED
+        assert hasattr(E.lib(), name)
+    assert "tsp_or_opt_stats" in hdr
+    # the ctypes structure has the header's layout: 7 int64 counters (one of them an array of 3) and 2 doubles
+    assert C.sizeof(E.OrOptStats) == 9 * 8 + 2 * 8
+
+
+OLD_METHODS = ["GREEDY", "GREEDY_ITER", "EXTR_MIL", "GRASP", "GRASP_ITER", "2OPT_GRASP", "2OPT_GRASP_ITER", "2OPT_GRASP_MULTI",
+               "2OPT_POP_MULTI", "2OPT_GREEDY", "2OPT_GREEDY_ITER", "2OPT_EXTR_MIL", "VNS", "TABU_STEP", "TABU_LIN", "TABU_RAND",
+               "GENETIC"]
+NEW_METHODS = ["2OPT_OR_GREEDY", "2OPT_OR_GRASP", "2OPT_OR_EXTR_MIL"]
+
+
+@pytest.fixture(scope="module")
+def built():
+    import __graft_entry__ as g
+    g.build()
+    return True
+
+
+def test_host_or_opt_entry_points_exported(built):
+    from tsp_optimization_amd.build import lib_path
+    L = C.CDLL(lib_path("libtsp_host.so"))
+    for name in ("alg_oropt", "alg_2opt_oropt", "HEU_2opt_oropt_greedy", "HEU_2opt_oropt_grasp", "HEU_2opt_oropt_extramileage",
+                 "tsp_host_last_or_stats"):
+        assert hasattr(L, name), name
+    assert not hasattr(L, "HEU_3opt")
+    with open(os.path.join(ROOT, "include", "tsp_host.h")) as f:
+        hdr = f.read()
+    assert re.search(r"SOLVE_2OPT_POP_MULTI,[^}]*SOLVE_2OPT_OR_GREEDY,[^}]*SOLVE_2OPT_OR_GRASP,[^}]*SOLVE_2OPT_OR_EXTR_MIL\s*/\*[^}]*\}\s*solver_type",
+                     hdr)
+
+
+def test_methods_list_new_rows_after_the_old_ones(built):
+    from tsp_optimization_amd.build import lib_path
+    r = subprocess.run([lib_path("tsp"), "--methods"], capture_output=True, text=True)
+    assert r.returncode == 0
+    rows = [ln.split()[0] for ln in r.stdout.splitlines() if ln.strip()]
+    assert rows == OLD_METHODS + NEW_METHODS
+    for ln in r.stdout.splitlines():
+        if ln.split() and ln.split()[0] in NEW_METHODS:
+            assert ln.rstrip().endswith("(extension)")
+
+
+def test_every_method_string_resolves_to_its_own_row():
+    """The CLI matches -method with the reference's cascade of strncmp prefixes, later rows overriding earlier ones
+    (src/utility.c:100-277): emulated over the table of host/tsp_host.c, every old string keeps its row and no new prefix
+    captures an old string."""
+    with open(os.path.join(ROOT, "tsp_optimization_amd", "host", "tsp_host.c")) as f:
+        src = f.read()
+    table = re.findall(r'\{"(\w+)", (\d+), (SOLVE_\w+), "', src)
+    assert [t[0] for t in table] == OLD_METHODS + NEW_METHODS
+
+    def resolve(m):
+        got = None
+        for prefix, ln, sid in table:
+            if m[:int(ln)] == prefix[:int(ln)] and len(m) >= int(ln):
+                got = sid
+        return got
+
+    for prefix, _, sid in table:
+        assert resolve(prefix) == sid, prefix
+    assert len({sid for _, _, sid in table}) == len(table)

@@ -23,6 +23,8 @@ int tsp_cluster_size(const tsp_dev_tours *t, int mode);
 int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double time_limit_s, int *all_done, int *fell_through,
                     tsp_dev_tabu *tabu = nullptr, int iter = 0, int tenure = 0);
 
+void tsp_or_scratch_free(void *p);   // or_opt.hip
+
 void *tsp_io_pool(tsp_dev_inst *inst, size_t bytes) {
     bytes = (bytes + 255) & ~(size_t)255;
     if (bytes > inst->io_pool_bytes) {
@@ -364,6 +366,7 @@ void tsp_dev_inst_destroy(tsp_dev_inst *inst) {
     if (inst->scratch1) tsp_dev_tours_destroy(inst->scratch1);
     if (inst->scratch_b) tsp_dev_tours_destroy(inst->scratch_b);
     if (inst->ev0) { (void)hipEventDestroy(inst->ev0); (void)hipEventDestroy(inst->ev1); }
+    tsp_or_scratch_free(inst->or_scratch);
     (void)hipFree(inst->d_coord); (void)hipFree(inst->d_sperm); (void)hipFree(inst->d_gbox); (void)hipFree(inst->d_sxy); (void)hipFree(inst->cons_pool);
     (void)hipFree(inst->d_rcoord); (void)hipFree(inst->d_sinv); (void)hipFree(inst->io_pool);
     delete inst;

@@ -56,7 +56,7 @@ constexpr int kApplyThreads = 1024;
     X(CLUSTER_SPIN_MS) X(CLUSTER_COPIES) X(CLUSTER_TILE_ROWS) X(CLUSTER_XCD_LOCAL) X(CLUSTER_ALLOW_OVERSUB) X(CLUSTER_DEBUG) X(CLUSTER_PROBE) X(CLUSTER_FIRST_SORTED) X(TABU_DENSE)     \
     X(LDS_PROBE) X(LDS_MIN_ROWS) X(LDS_EDGE_CACHE) X(NO_ICOORD) X(NO_FILTER) X(NO_PRUNE) X(SORTED_MIN_N)      \
     X(SWEEP_BLOCKS) X(SWEEP_TABLE) X(BEST_ROWS_PER_BLOCK) X(BEST_RECS) X(FIRST_GRID_ROWS) X(FIRST_MIN_ROWS)                \
-    X(FIRST_MAX_ROWS) X(CONSTRUCT_GLOBAL) X(CONSTRUCT_NN) X(CLUSTER_FS_ROWS) X(LDS_F32_MIN_N) X(EXH_POS) X(TABU_INKERNEL)
+    X(FIRST_MAX_ROWS) X(CONSTRUCT_GLOBAL) X(CONSTRUCT_NN) X(CLUSTER_FS_ROWS) X(LDS_F32_MIN_N) X(EXH_POS) X(TABU_INKERNEL) X(OROPT_FULL)
 namespace tsp {
 enum SwitchId {
 #define TSP_SW_ENUM(name) SW_##name,
@@ -122,6 +122,7 @@ struct tsp_dev_inst {
     int *d_sinv = nullptr;             // CLUSTER engine, sorted scan: node -> rank slot
     std::vector<double> h_xy;   // host copy of the raw coordinates (2n)
     tsp::Switches sw;           // the TSP_* switches as they stood when this handle was created
+    void *or_scratch = nullptr; // Or-opt buffers of the last batch size (or_opt.hip)
 };
 
 struct tsp_dev_tabu {

@@ -427,6 +427,13 @@ double wall_s() {
 }  // namespace
 
 // Shared with the other translation units of the library.
+// d_out[b] = recomputed cost of tour b, as a finished best-improvement run leaves it (or_opt.hip)
+int tsp_grid_tour_cost(tsp_dev_tours *t, double *d_out) {
+    launch_tour_cost(t, d_out, sizeof(double));
+    TSP_HIP_TRY(hipGetLastError());
+    return TSP_OK;
+}
+
 int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int tenure, int64_t max_steps,
                  double time_limit_s, int sync, int *all_done) {
     if (!t || (mode != TSP_2OPT_FIRST && mode != TSP_2OPT_BEST)) return TSP_DEV_E_ARG;

@@ -29,6 +29,17 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class OrOptStats(C.Structure):
+    _fields_ = [("sweeps", C.c_int64), ("evals", C.c_int64), ("moves", C.c_int64), ("moves_by_len", C.c_int64 * 3),
+                ("moves_reversed", C.c_int64), ("deltas_executed", C.c_int64), ("rounds", C.c_int64),
+                ("seconds", C.c_double), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["moves_by_len"] = list(self.moves_by_len)
+        return d
+
+
 _lib = None
 
 
@@ -106,6 +117,9 @@ def lib():
         L.tsp_dev_multistart_bcast_tour.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int]
         L.tsp_dev_multistart_allreduce_group.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.tsp_dev_multistart_bcast_tour_group.argtypes = [C.POINTER(vp), C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip]
+        orp = C.POINTER(OrOptStats)
+        L.tsp_dev_or_opt.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double, orp]
+        L.tsp_dev_two_opt_or_opt.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_double, sp, orp]
         _lib = L
     return _lib
 
@@ -124,6 +138,7 @@ EXPORTED = [
     "tsp_dev_comm_info", "tsp_dev_multistart_pack", "tsp_dev_multistart_allreduce", "tsp_dev_multistart_bcast_tour",
     "tsp_dev_multistart_allreduce_group", "tsp_dev_multistart_bcast_tour_group",
     "tsp_dev_multistart_allreduce_f64", "tsp_dev_multistart_allreduce_f64_group",
+    "tsp_dev_or_opt", "tsp_dev_two_opt_or_opt",
 ]
 
 COMM_ID_BYTES = 128
@@ -263,6 +278,43 @@ class Instance:
         if single:
             return rc, succ2[0], float(o[0]), stats[0]
         return rc, succ2, o, stats
+
+    # -- Or-opt (extension) ---------------------------------------------------------------
+    def _tours(self, succ):
+        succ = np.array(succ, dtype=np.int32, copy=True, order="C")
+        single = succ.ndim == 1
+        succ2 = succ.reshape(1, -1) if single else succ
+        assert succ2.shape[1] == self.n
+        return single, succ2
+
+    def or_opt(self, succ, obj=None, max_moves=-1, time_limit=-1.0):
+        """Or-opt descent (tsp_dev_or_opt).  succ [n] or [B,n].  -> (status, succ', obj' (recomputed cost), stats dict(s))"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
+        st = (OrOptStats * B)()
+        rc = lib().tsp_dev_or_opt(self._h, B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
+        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
+        stats = [s.as_dict() for s in st]
+        if single:
+            return rc, succ2[0], float(o[0]), stats[0]
+        return rc, succ2, o, stats
+
+    def two_opt_or_opt(self, succ, obj, mode=FIRST, time_limit=-1.0):
+        """2-opt + Or-opt rounds to a joint local optimum (tsp_dev_two_opt_or_opt).
+        -> (status, succ', obj' (recomputed cost), 2-opt stats dict(s), Or-opt stats dict(s))"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)), copy=True)
+        st2 = (Stats * B)()
+        sto = (OrOptStats * B)()
+        rc = lib().tsp_dev_two_opt_or_opt(self._h, mode, B, _i(succ2), 1, n, _d(o), time_limit, st2, sto)
+        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
+        s2 = [s.as_dict() for s in st2]
+        so = [s.as_dict() for s in sto]
+        if single:
+            return rc, succ2[0], float(o[0]), s2[0], so[0]
+        return rc, succ2, o, s2, so
 
     def perm_cost(self, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

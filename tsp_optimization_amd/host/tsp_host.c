@@ -136,6 +136,7 @@ static unsigned long g_clock = 0;
 static __thread long long t_sweeps, t_evals, t_moves, t_grasp_iter_starts;
 static __thread double t_driver_loop_s;   /* seconds the last tsp_host_tabu / tsp_host_vns spent in its iteration loop (not the initial solution) */
 static __thread double t_device_ms;
+static __thread tsp_or_opt_stats t_or_stats;   /* the Or-opt phases of the last alg_oropt / alg_2opt_oropt */
 
 static void dev_fail(const char *what, int rc) {
     LOG_E("%s failed with %d %s (this build has no CPU path: an MI355X and libtsp_hip.so are required)", what, rc,
@@ -220,6 +221,10 @@ void tsp_host_last_stats(long long *sweeps, long long *evals, long long *moves, 
     if (evals) *evals = t_evals;
     if (moves) *moves = t_moves;
     if (device_ms) *device_ms = t_device_ms;
+}
+
+void tsp_host_last_or_stats(tsp_or_opt_stats *out) {
+    if (out) *out = t_or_stats;
 }
 
 static void keep_stats(const tsp_two_opt_stats *st) {
@@ -472,6 +477,46 @@ int HEU_2opt_grasp_iter(instance *inst) { (void)HEU_Grasp_iter(inst, inst->param
 int HEU_2opt_greedy(instance *inst) { (void)HEU_greedy(inst); return alg_2opt(inst); }
 int HEU_2opt_greedy_iter(instance *inst) { (void)HEU_Greedy_iter(inst); return alg_2opt(inst); }
 int HEU_2opt_extramileage(instance *inst) { (void)HEU_extramileage(inst); return alg_2opt(inst); }
+
+/* ---- Or-opt (extension) ---------------------------------------------------------------------------------- */
+
+int alg_oropt(instance *inst) {
+    tsp_or_opt_stats st;
+    memset(&st, 0, sizeof st);
+    double obj = inst->solution.obj_best;
+    pthread_mutex_lock(&g_lock);
+    int rc = tsp_dev_or_opt(dev_inst_locked(inst), 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)inst->num_nodes, &obj, -1,
+                            limit_of(inst), &st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_or_opt", rc);
+    inst->solution.obj_best = obj;
+    t_or_stats = st;
+    if (rc == TIME_LIMIT_EXCEEDED) LOG_I("Or-opt heuristics time exceeded");
+    return rc;
+}
+
+int alg_2opt_oropt(instance *inst) {
+    tsp_two_opt_stats st2;
+    tsp_or_opt_stats sto;
+    memset(&st2, 0, sizeof st2);
+    memset(&sto, 0, sizeof sto);
+    double obj = inst->solution.obj_best;
+    pthread_mutex_lock(&g_lock);
+    int rc = tsp_dev_two_opt_or_opt(dev_inst_locked(inst), TSP_2OPT_FIRST, 1, &inst->solution.edges[0].j, 2,
+                                    2 * (int64_t)inst->num_nodes, &obj, limit_of(inst), &st2, &sto);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_two_opt_or_opt", rc);
+    inst->solution.obj_best = obj;
+    keep_stats(&st2);
+    t_or_stats = sto;
+    if (rc == TIME_LIMIT_EXCEEDED) LOG_I("2-opt + Or-opt heuristics time exceeded");
+    return rc;
+}
+
+/* construction + alg_2opt_oropt, like HEU_2opt_greedy and friends: the constructive status is overwritten */
+int HEU_2opt_oropt_greedy(instance *inst) { (void)HEU_greedy(inst); return alg_2opt_oropt(inst); }
+int HEU_2opt_oropt_grasp(instance *inst) { (void)HEU_Grasp(inst); return alg_2opt_oropt(inst); }
+int HEU_2opt_oropt_extramileage(instance *inst) { (void)HEU_extramileage(inst); return alg_2opt_oropt(inst); }
 
 /* ---- VNS (src/vns.c) ------------------------------------------------------------------------------------- */
 
@@ -1493,6 +1538,9 @@ int TSP_heuc(instance *inst) {
     case SOLVE_2OPT_GREEDY_ITER: HEU_2opt_greedy_iter(inst); break;
     case SOLVE_EXTR_MIL: HEU_extramileage(inst); break;
     case SOLVE_2OPT_EXTR_MIL: HEU_2opt_extramileage(inst); break;
+    case SOLVE_2OPT_OR_GREEDY: HEU_2opt_oropt_greedy(inst); break;
+    case SOLVE_2OPT_OR_GRASP: HEU_2opt_oropt_grasp(inst); break;
+    case SOLVE_2OPT_OR_EXTR_MIL: HEU_2opt_oropt_extramileage(inst); break;
     case SOLVE_VNS: HEU_VNS(inst); break;
     case SOLVE_GENETIC: HEU_Genetic(inst); break;
     case SOLVE_2OPT_GRASP_MULTI: {
@@ -1521,7 +1569,8 @@ int TSP_heuc(instance *inst) {
         break;
     default:
         LOG_E("method %s is outside this build's scope (2-opt hot path: GREEDY, GREEDY_ITER, EXTR_MILE, GRASP, GRASP_ITER, 2OPT_EXTR_MIL, "
-              "2OPT_GRASP, 2OPT_GRASP_ITER, 2OPT_GRASP_MULTI, 2OPT_POP_MULTI, 2OPT_GREEDY, 2OPT_GREEDY_ITER, VNS, TABU_STEP, TABU_LIN, TABU_RAND, GENETIC)",
+              "2OPT_GRASP, 2OPT_GRASP_ITER, 2OPT_GRASP_MULTI, 2OPT_POP_MULTI, 2OPT_GREEDY, 2OPT_GREEDY_ITER, VNS, TABU_STEP, TABU_LIN, TABU_RAND, GENETIC, "
+              "2OPT_OR_GREEDY, 2OPT_OR_GRASP, 2OPT_OR_EXTR_MIL)",
               inst->params.method.name ? inst->params.method.name : "?");
     }
     gettimeofday(&t1, 0);
@@ -1556,6 +1605,10 @@ static const struct { const char *prefix; int len; solver_type id; const char *n
     {"TABU_LIN", 8, SOLVE_TABU_LIN, "TABU SEARCH META-HEURISTIC WITH LINEAR POLICY"},
     {"TABU_RAND", 9, SOLVE_TABU_RAND, "TABU SEARCH META-HEURISTIC WITH RANDOM POLICY"},
     {"GENETIC", 7, SOLVE_GENETIC, "GENETIC ALGORITHM META-HEURISTIC"},
+    /* extensions: full-length prefixes that no earlier row's string starts with, so every old string keeps its id */
+    {"2OPT_OR_GREEDY", 14, SOLVE_2OPT_OR_GREEDY, "2-OPT + OR-OPT HEURISTIC WITH GREEDY INITIALIZATION (extension)"},
+    {"2OPT_OR_GRASP", 13, SOLVE_2OPT_OR_GRASP, "2-OPT + OR-OPT HEURISTIC WITH GRASP INITIALIZATION (extension)"},
+    {"2OPT_OR_EXTR_MIL", 16, SOLVE_2OPT_OR_EXTR_MIL, "2-OPT + OR-OPT HEURISTIC WITH EXTRA MILEAGE INITIALIZATION (extension)"},
 };
 
 static char *dup_string(const char *s) {
