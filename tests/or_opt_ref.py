@@ -143,9 +143,9 @@ def _euc_rows(xy, rows, cols, integer_cost):
     return np.floor(d + 0.5) if integer_cost else d
 
 
-def min_delta(xy, wt, succ, integer_cost=1, chunk=256, D=None):
-    """Smallest delta over every Or-opt move of the tour (rows in chunks: usable up to n of about 20 000 for EUC_2D, whose
-    distances are computed here block by block; other metrics take the oracle's full matrix)."""
+def _blocked_rows(xy, wt, succ, integer_cost, chunk, D):
+    """Yields (row positions i, L, o, delta block over (i, every column position)) with +inf where not a move, rows in
+    chunks: the same IEEE operations in the same order as _decision_mats."""
     n = len(succ)
     order = tour_order(succ)
     xy = np.asarray(xy, dtype=np.float64)
@@ -164,7 +164,6 @@ def min_delta(xy, wt, succ, integer_cost=1, chunk=256, D=None):
         dx, dy = xy[a, 0] - xy[b, 0], xy[a, 1] - xy[b, 1]
         d = np.sqrt(dx * dx + dy * dy)
         E = np.floor(d + 0.5) if integer_cost else d
-    best = np.inf
     Ecol = E[None, :]
     for r0 in range(0, n, chunk):
         i = np.arange(r0, min(n, r0 + chunk))
@@ -183,10 +182,66 @@ def min_delta(xy, wt, succ, integer_cost=1, chunk=256, D=None):
             outs = [((row(i) + row1(ll)) - Ecol) - rem[:, None]]
             if L > 1:
                 outs.append(((row(ll) + row1(i)) - Ecol) - rem[:, None])
-            for dm in outs:
+            for o, dm in enumerate(outs):
                 dm[invalid] = np.inf
-                best = min(best, float(dm.min()))
+                yield order, i, L, o, dm
+
+
+def min_delta(xy, wt, succ, integer_cost=1, chunk=256, D=None):
+    """Smallest delta over every Or-opt move of the tour (rows in chunks: usable up to n of about 20 000 for EUC_2D, whose
+    distances are computed here block by block; other metrics take the oracle's full matrix)."""
+    best = np.inf
+    for _, _, _, _, dm in _blocked_rows(xy, wt, succ, integer_cost, chunk, D):
+        best = min(best, float(dm.min()))
     return best
+
+
+def decide_blocked(xy, wt, succ, integer_cost=1, chunk=256, D=None):
+    """decide() with the rows in chunks, as min_delta walks them (no n x n matrix for EUC_2D): -> (delta, key) or None."""
+    n = len(succ)
+    if n < 5:
+        return None
+    best = None
+    for order, i, L, o, dm in _blocked_rows(xy, wt, succ, integer_cost, chunk, D):
+        m = dm.min()
+        if not m < 0.0:
+            continue
+        ii, jj = np.nonzero(dm == m)
+        k = int((((order[i[ii]] * 3 + (L - 1)) * n + order[jj]) * 2 + o).min())
+        if best is None or m < best[0] or (m == best[0] and k < best[1]):
+            best = (float(m), k)
+    return best
+
+
+def or_opt_prefix_blocked(xy, wt, succ, moves, integer_cost=1, D=None):
+    """The first `moves` decisions of the descent through decide_blocked -> (succ', counters as or_opt_descent's,
+    [(m1, m2)] of every applied move as shift_lengths gives them)."""
+    succ = np.array(succ, dtype=np.int32, copy=True)
+    n = len(succ)
+    c = {"sweeps": 0, "evals": 0, "moves": 0, "moves_by_len": [0, 0, 0], "moves_reversed": 0}
+    shifts = []
+    while n >= 5 and c["moves"] < moves:
+        c["sweeps"] += 1
+        c["evals"] += n_moves(n)
+        d = decide_blocked(xy, wt, succ, integer_cost, D=D)
+        if d is None:
+            break
+        f, L, a, o = decode(d[1], n)
+        shifts.append(shift_lengths(succ, f, L, a))
+        succ = apply_move(succ, f, L, a, o)
+        c["moves"] += 1
+        c["moves_by_len"][L - 1] += 1
+        c["moves_reversed"] += o
+    return succ, c, shifts
+
+
+def shift_lengths(succ, f, L, a):
+    """(m1, m2) of the move as k_or_pick_apply splits the tour: m1 nodes s .. a, m2 nodes b .. p."""
+    n = len(succ)
+    pos = np.empty(n, dtype=np.int64)
+    pos[tour_order(succ)] = np.arange(n)
+    m1 = (int(pos[a]) - (int(pos[f]) + L)) % n + 1
+    return m1, n - L - m1
 
 
 def is_or_opt_optimal(xy, wt, succ, integer_cost=1, rel_tol=0.0, cost=None):

@@ -106,6 +106,79 @@ def test_reference_descent_ends_at_local_optimum():
     assert R.min_delta(xy, O.EUC_2D, succ, 1, chunk=7) == min(m[0] for m in enumerate_moves(D, succ))
 
 
+def brute_best_pair(xy, wt, succ, ic):
+    bb = brute_best(enumerate_moves(O.dist_matrix(xy, wt, ic), succ))
+    return None if bb is None else (bb[0], bb[1])
+
+
+@pytest.mark.parametrize("n", list(range(5, 13)))
+def test_decide_blocked_matches_decide_random(n):
+    """Small n: the row blocks wrap and hold fewer rows than a chunk; chunk = 3 splits the rows, chunk = 256 does not."""
+    rng = np.random.default_rng(200 + n)
+    for rep in range(6):
+        xy = rng.integers(0, 100, size=(n, 2)).astype(np.float64)
+        succ = random_tour(n, rng)
+        for ic in (1, 0):
+            ref = R.decide(O.dist_matrix(xy, O.EUC_2D, ic), succ)
+            assert ref == brute_best_pair(xy, O.EUC_2D, succ, ic)
+            for chunk in (3, 256):
+                assert R.decide_blocked(xy, O.EUC_2D, succ, ic, chunk=chunk) == ref
+
+
+def test_decide_blocked_matches_decide_lattice_ties():
+    g = np.array([(x, y) for x in range(6) for y in range(6)], dtype=np.float64) * 10
+    rng = np.random.default_rng(11)
+    D = O.dist_matrix(g, O.EUC_2D, 1)
+    for rep in range(8):
+        succ = random_tour(len(g), rng)
+        ref = R.decide(D, succ)
+        assert ref is not None and ref == brute_best_pair(g, O.EUC_2D, succ, 1)
+        assert R.decide_blocked(g, O.EUC_2D, succ, 1, chunk=5) == ref
+        assert R.decide_blocked(g, O.EUC_2D, succ, 1, chunk=5, D=D) == ref
+
+
+@pytest.mark.parametrize("ic", [1, 0])
+def test_decide_blocked_matches_decide_n300(ic):
+    """n = 300 in blocks of 64 (the last one partial) along a short descent, EUC_2D distances computed block by block."""
+    rng = np.random.default_rng(300 + ic)
+    xy = rng.uniform(0, 10_000, size=(300, 2))
+    D = O.dist_matrix(xy, O.EUC_2D, ic)
+    succ = random_tour(300, rng)
+    for step in range(4):
+        ref = R.decide(D, succ)
+        assert ref is not None and R.decide_blocked(xy, O.EUC_2D, succ, ic, chunk=64) == ref
+        f, L, a, o = R.decode(ref[1], 300)
+        succ = R.apply_move(succ, f, L, a, o)
+    s1, c1 = R.or_opt_descent(xy, O.EUC_2D, succ, ic, max_moves=3, D=D)
+    s2, c2, sh = R.or_opt_prefix_blocked(xy, O.EUC_2D, succ, 3, ic)
+    assert (s1 == s2).all() and c1 == c2 and len(sh) == 3 and all(m1 >= 1 and m2 >= 1 and m1 + m2 <= 299 for m1, m2 in sh)
+
+
+@pytest.mark.parametrize("wt", [O.MAN_2D, O.MAX_2D])
+def test_decide_blocked_matches_decide_man_max_ties(wt):
+    """MAN_2D / MAX_2D take dy = |y2 - y2|: every node with the same x coincides, so the node-id key decides most ties."""
+    rng = np.random.default_rng(40 + wt)
+    xy = np.stack([rng.integers(0, 40, 300), rng.integers(0, 1000, 300)], axis=1).astype(np.float64)
+    D = O.dist_matrix(xy, wt, 1)
+    succ = random_tour(300, rng)
+    for step in range(3):
+        ref = R.decide(D, succ)
+        assert ref is not None and R.decide_blocked(xy, wt, succ, 1, chunk=100) == ref
+        f, L, a, o = R.decode(ref[1], 300)
+        succ = R.apply_move(succ, f, L, a, o)
+    if wt == O.MAN_2D:     # the small-n definition check on the same tie-heavy metric
+        small = xy[:12]
+        s12 = random_tour(12, rng)
+        assert R.decide_blocked(small, wt, s12, 1, chunk=5) == brute_best_pair(small, wt, s12, 1)
+
+
+def test_shift_lengths():
+    succ = O.perm_to_succ(np.arange(10, dtype=np.int32))     # 0 -> 1 -> .. -> 9 -> 0: position = node
+    assert R.shift_lengths(succ, 2, 2, 6) == (3, 5)          # s .. a = 4 5 6, b .. p = 7 8 9 0 1
+    assert R.shift_lengths(succ, 8, 3, 1) == (1, 6)          # segment 8 9 0 wraps, a = s = 1, b .. p = 2 .. 7
+    assert R.shift_lengths(succ, 5, 1, 3) == (8, 1)          # s .. a = 6 .. 9 0 .. 3, b .. p = 4
+
+
 def test_reference_small_n_is_a_no_op():
     xy = np.array([[0, 0], [5, 1], [2, 7], [9, 9]], dtype=np.float64)
     succ = np.array([1, 2, 3, 0], dtype=np.int32)
