@@ -341,6 +341,48 @@ int tsp_dev_two_opt_or_opt(tsp_dev_inst *inst, int two_opt_mode, int B, int *suc
                            int64_t tour_stride, double *obj, double time_limit_s,
                            tsp_two_opt_stats *two_opt_stats, tsp_or_opt_stats *or_opt_stats);
 
+/* ---- candidate neighbour lists (extension): a 2-opt + Or-opt descent over the moves that use an edge of the lists --------------
+ * (A decision scans O(n K) moves and applies one in O(n) on one compute unit; DESIGN.md 4.11 has the measured times beside
+ * tsp_dev_two_opt_or_opt's.)
+ * Lists.  For 1 <= K <= min(TSP_NL_MAX_K, n - 1), nbr[v][0 .. K-1] are the K nodes u != v smallest by (calc_dist(v, u), u), in
+ * that order: the instance's own distance (the value tsp_dev_dist_pairs returns), ties -> lower node id, coincident nodes are
+ * neighbours at distance 0.  N(v) is the set; u ~ v when u in N(v) or v in N(u).  A caller's own lists may be any n x K array
+ * with entries in [0, n) other than v itself; duplicates are allowed, only the set matters.
+ * Moves.  kind 0, 2-opt: node pairs i < j with i1 = succ i, j1 = succ j, skipped when j = i1 or j1 = i;
+ *     delta = ((d(i,j) + d(i1,j1)) - d(i,i1)) - d(j,j1)   (alg_2opt_tabu's), key = i * n + j;
+ * in the list neighbourhood iff i ~ j or i1 ~ j1; applied as alg_2opt_tabu applies it (succ i = j, succ i1 = j1, the forward path
+ * i1 .. j reversed).  kind 1, Or-opt: the moves (f, L, a, o) of tsp_dev_or_opt with their delta and key; in the list
+ * neighbourhood iff, for o = 0, a ~ f or l ~ b, and for o = 1, a ~ l or f ~ b; applied as tsp_dev_or_opt applies them.
+ * Decision.  Among the enabled kinds the move of smallest delta < 0, ties -> lower kind, then lower key; one move per decision.
+ * The descent ends at the first decision without an improving move, after max_moves moves or at the time limit.  A kind that has
+ * no move at the instance's size (2-opt: n < 4, Or-opt: n < 5) is left out; with none left the tours come back unchanged.
+ * With K = n - 1 kind 0 alone follows alg_2opt_tabu(NULL) and kind 1 alone follows tsp_dev_or_opt. */
+enum { TSP_NL_2OPT = 1, TSP_NL_OROPT = 2 }; /* kinds mask */
+#define TSP_NL_MAX_K 16
+#define TSP_NL_DEFAULT_K 10
+/* The lists live in the instance handle.  Bad K or bad entries: TSP_DEV_E_ARG, and the lists the handle had stay in place. */
+int tsp_dev_inst_knn_build(tsp_dev_inst *inst, int K, float *kernel_ms); /* exact, on the device; kernel_ms may be NULL */
+int tsp_dev_inst_knn_set(tsp_dev_inst *inst, int K, const int *nbr);     /* the caller's n x K lists, validated        */
+int tsp_dev_inst_knn_get(tsp_dev_inst *inst, int *K, int *nbr);          /* nbr may be NULL: K only (0 = no lists)     */
+typedef struct {
+    int64_t decisions;       /* decisions taken: moves + the last one, if it found no improving move                     */
+    int64_t moves;           /* applied moves                                                                            */
+    int64_t moves_2opt;      /* ... of kind 0                                                                            */
+    int64_t moves_oropt;     /* ... of kind 1                                                                            */
+    int64_t moves_by_len[3]; /* Or-opt moves of segments of 1, 2, 3 nodes                                                */
+    int64_t moves_reversed;  /* Or-opt moves that inserted the segment reversed                                          */
+    int64_t reversed;        /* successors rewritten by the 2-opt moves' reversals of the forward path i1 .. j (the
+                                reference's count, tsp_two_opt_stats.reversed)                                           */
+    int64_t deltas_executed; /* delta expressions the device ran (a move is reached through several list entries)        */
+    double seconds;          /* wall time of the call, host clock                                                        */
+    double device_ms;        /* device time of the call, HIP events on the engine's stream                               */
+} tsp_nl_opt_stats;
+/* Descent over the list neighbourhood of B tours (kinds: TSP_NL_2OPT | TSP_NL_OROPT, at least one).  Without lists in the
+ * handle it builds them with K = min(TSP_NL_DEFAULT_K, n - 1).  obj[B] out: the recomputed cost of the final tour.  max_moves,
+ * time_limit_s, the status and stats as tsp_dev_or_opt. */
+int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride,
+                   double *obj, int64_t max_moves, double time_limit_s, tsp_nl_opt_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,15 @@ int HEU_2opt_oropt_greedy(instance *inst);        /* HEU_greedy + alg_2opt_oropt
 int HEU_2opt_oropt_grasp(instance *inst);         /* HEU_Grasp + alg_2opt_oropt        */
 int HEU_2opt_oropt_extramileage(instance *inst);  /* HEU_extramileage + alg_2opt_oropt */
 
+/* ---- neighbour lists (extension; include/tsp_hip.h, tsp_dev_nl_opt).  Library entry points only: the solver_type enum and
+ * the -method table have no rows for them. */
+int tsp_host_set_knn(int K);          /* list length of alg_nl_opt, 1 .. TSP_NL_MAX_K (default TSP_NL_DEFAULT_K); else TSP_DEV_E_ARG */
+int alg_nl_opt(instance *inst);       /* 2-opt + Or-opt over the lists of the min(K, n - 1) nearest nodes of inst->solution;
+                                         inst->solution.obj_best receives the recomputed cost                                */
+int HEU_nl_greedy(instance *inst);        /* HEU_greedy + alg_nl_opt       */
+int HEU_nl_grasp(instance *inst);         /* HEU_Grasp + alg_nl_opt        */
+int HEU_nl_extramileage(instance *inst);  /* HEU_extramileage + alg_nl_opt */
+
 /* ---- src/tabusearch.c (externally linked there, not in its header) --------------------------- */
 int alg_2opt_tabu(instance *inst, int *skip_edge, int *stored_prev, const int iter, const int tenure); /* :107 */
 
@@ -233,6 +242,8 @@ void tsp_host_last_stats(long long *sweeps, long long *evals, long long *moves, 
 /* Counters of the Or-opt phases of the last alg_oropt / alg_2opt_oropt call of this thread (rounds = 0 after alg_oropt);
  * the 2-opt phases of alg_2opt_oropt go to tsp_host_last_stats. */
 void tsp_host_last_or_stats(tsp_or_opt_stats *out);
+/* Counters of the last alg_nl_opt call of this thread. */
+void tsp_host_last_nl_stats(tsp_nl_opt_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */
 void tsp_host_shutdown(void);
 

@@ -24,6 +24,7 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
                     tsp_dev_tabu *tabu = nullptr, int iter = 0, int tenure = 0);
 
 void tsp_or_scratch_free(void *p);   // or_opt.hip
+void tsp_nl_data_free(void *p);      // nl_opt.hip
 
 void *tsp_io_pool(tsp_dev_inst *inst, size_t bytes) {
     bytes = (bytes + 255) & ~(size_t)255;
@@ -367,6 +368,7 @@ void tsp_dev_inst_destroy(tsp_dev_inst *inst) {
     if (inst->scratch_b) tsp_dev_tours_destroy(inst->scratch_b);
     if (inst->ev0) { (void)hipEventDestroy(inst->ev0); (void)hipEventDestroy(inst->ev1); }
     tsp_or_scratch_free(inst->or_scratch);
+    tsp_nl_data_free(inst->nl_data);
     (void)hipFree(inst->d_coord); (void)hipFree(inst->d_sperm); (void)hipFree(inst->d_gbox); (void)hipFree(inst->d_sxy); (void)hipFree(inst->cons_pool);
     (void)hipFree(inst->d_rcoord); (void)hipFree(inst->d_sinv); (void)hipFree(inst->io_pool);
     delete inst;

@@ -1,0 +1,517 @@
+// nl_opt.hip -- candidate neighbour lists: the exact KNN build (tsp_dev_inst_knn_*) and the 2-opt + Or-opt descent over the
+// list neighbourhood (tsp_dev_nl_opt).  The definitions are in include/tsp_hip.h.
+//
+// KNN      k_knn_scan (one lane = one row node, its 16 best (distance, id) sorted in registers, columns in <= 16 chunks)
+//          -> k_knn_merge (one lane = one row: the chunks' lists merged, the first K ids stored).
+// Decision k_nl_prep (per node: length of its tour edge, rem of the three segments that start at it) -> k_nl_scan (one
+//          lane = one list entry (v, u): the 2 + 20 moves whose new / attaching edge is {v, u}; one (delta, kind, key) per
+//          workgroup) -> k_nl_pick_apply (the workgroups' candidates, then the move on order/pos; one workgroup per tour).
+// Every distance goes through dsym(): the lower node id first, so that a move reached through several (v, u, role)
+// combinations has the same delta bits each time.  A 2-opt move always reverses the forward path i1 .. j in place, so that
+// order/pos keep the orientation of succ and the Or-opt shift works unchanged.
+#include "or_opt_shift.hpp"
+
+#include <time.h>
+#include <algorithm>
+
+#pragma clang fp contract(off)
+
+using namespace tsp;
+
+namespace {
+
+constexpr int kK = TSP_NL_MAX_K;     // k_knn_scan keeps this many per row whatever K is asked for: the K best are a prefix
+constexpr int kKnnChunks = 16;       // k_knn_scan: most column chunks per row
+constexpr int kKnnWaves = 4096;      // ... chosen so that about this many waves exist
+constexpr int kPickThreads = 1024;
+constexpr u64 kKindBit = 1ull << 62; // decision key: kind in bit 62, the kind's own key below (6 n^2 < 2^62)
+
+struct alignas(16) NlBest {
+    double d;
+    u64 k;
+};
+
+struct alignas(16) NlState {
+    long long max_moves;   // < 0: unlimited
+    long long decisions, moves, moves_2opt, moves_oropt, moves_len[3], moves_rev, reversed, deltas;
+    int done, pad;
+};
+
+__device__ __forceinline__ void offer(double delta, u64 key, double &bd, u64 &bk) {
+    if (delta < 0.0 && better(delta, key, bd, bk)) { bd = delta; bk = key; }
+}
+
+// calc_dist of two nodes, the lower id first
+template <int WT, bool INT>
+__device__ __forceinline__ double dsym(const double2 *coord, int u, int v) {
+    const double2 a = coord[min(u, v)], b = coord[max(u, v)];
+    return dist_xy<WT, INT>(a.x, a.y, b.x, b.y);
+}
+
+// (d, id) into the sorted list; d == a held distance goes behind it (the callers offer equal distances in id order)
+__device__ __forceinline__ void knn_insert(double (&kd)[kK], int (&ki)[kK], double d, int id) {
+#pragma unroll
+    for (int s = kK - 1; s >= 1; --s) {
+        const bool shift = d < kd[s - 1], here = !shift && d < kd[s];
+        kd[s] = shift ? kd[s - 1] : (here ? d : kd[s]);
+        ki[s] = shift ? ki[s - 1] : (here ? id : ki[s]);
+    }
+    const bool first = d < kd[0];
+    kd[0] = first ? d : kd[0];
+    ki[0] = first ? id : ki[0];
+}
+
+// Row node v = one lane, columns [chunk * CH, chunk * CH + CH): pd / pi [(chunk * 16 + s) * n + v] = s-th best of the chunk
+// (+inf, -1 where the chunk has fewer).  The column is wave-uniform: its coordinates come from scalar loads.
+template <int WT, bool INT>
+__global__ __launch_bounds__(256) void k_knn_scan(const double2 *__restrict__ coord, int n, int CH, double *__restrict__ pd,
+                                                  int *__restrict__ pi) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    const int chunk = blockIdx.y;
+    const int c0 = chunk * CH, c1 = min(n, c0 + CH);
+    const double2 cv = coord[min(v, n - 1)];
+    double kd[kK];
+    int ki[kK];
+#pragma unroll
+    for (int s = 0; s < kK; ++s) { kd[s] = INFINITY; ki[s] = -1; }
+    for (int c = c0; c < c1; ++c) {
+        const double2 cc = coord[c];
+        const double d = dist_xy<WT, INT>(cv.x, cv.y, cc.x, cc.y);
+        if (d < kd[kK - 1] && c != v) knn_insert(kd, ki, d, c);
+    }
+    if (v >= n) return;
+#pragma unroll
+    for (int s = 0; s < kK; ++s) {
+        const size_t at = ((size_t)chunk * kK + s) * n + v;
+        pd[at] = kd[s]; pi[at] = ki[s];
+    }
+}
+
+// nbr[v * K + s] = s-th best of row v over the chunks (taken in column order, so that equal distances stay in id order)
+__global__ __launch_bounds__(256) void k_knn_merge(int n, int Cc, int K, const double *__restrict__ pd, const int *__restrict__ pi,
+                                                   int *__restrict__ nbr) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    double kd[kK];
+    int ki[kK];
+#pragma unroll
+    for (int s = 0; s < kK; ++s) { kd[s] = INFINITY; ki[s] = -1; }
+    for (int c = 0; c < Cc; ++c)
+        for (int s = 0; s < kK; ++s) {
+            const size_t at = ((size_t)c * kK + s) * n + v;
+            const int id = pi[at];
+            if (id < 0) break;
+            const double d = pd[at];
+            if (d < kd[kK - 1]) knn_insert(kd, ki, d, id);
+        }
+#pragma unroll
+    for (int s = 0; s < kK; ++s)
+        if (s < K) nbr[(size_t)v * K + s] = ki[s];
+}
+
+// Per node v at position i: E[v] = d(v, succ v), rem[(L-1) * n + v] of the segment of L nodes that starts at v.
+template <int WT, bool INT>
+__global__ void k_nl_prep(const double2 *__restrict__ coord, const int *__restrict__ orders, const NlState *__restrict__ st,
+                          int n, double *__restrict__ Es, double *__restrict__ rems) {
+    const int b = blockIdx.y;
+    if (st[b].done) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int *order = orders + (size_t)b * n;
+    const int v = order[i];
+    const int pm = order[or_wrap(i - 1, n)], v1 = order[or_wrap(i + 1, n)];
+    const double dpf = dsym<WT, INT>(coord, pm, v);
+    const double e0 = dsym<WT, INT>(coord, v, v1);
+    Es[(size_t)b * n + v] = e0;
+    if (n < 5) return;   // no Or-opt move
+    double *rem = rems + (size_t)b * 3 * n;
+    rem[v] = (dpf + e0) - dsym<WT, INT>(coord, pm, v1);
+    const int v2 = order[or_wrap(i + 2, n)], v3 = order[or_wrap(i + 3, n)];
+    rem[n + v] = (dpf + dsym<WT, INT>(coord, v1, v2)) - dsym<WT, INT>(coord, pm, v2);
+    rem[2 * n + v] = (dpf + dsym<WT, INT>(coord, v2, v3)) - dsym<WT, INT>(coord, pm, v3);
+}
+
+// What a lane of k_nl_scan reads the tour through.
+template <int WT, bool INT>
+struct NlView {
+    const double2 *coord;
+    const int *order, *pos;
+    const double *E, *rem;
+    int n;
+    double bd;
+    u64 bk;
+    unsigned cnt;
+
+    __device__ __forceinline__ int at(int p) const { return order[or_wrap(p, n)]; }
+    __device__ __forceinline__ double d(int u, int v) const { return dsym<WT, INT>(coord, u, v); }
+
+    // 2-opt move of the pair {x, y}; `known` says which new edge has the length dk: 0 = d(i,j), 1 = d(i1,j1)
+    __device__ __forceinline__ void two(int x, int px, int y, int py, int known, double dk) {
+        if (x > y) { int t = x; x = y; y = t; t = px; px = py; py = t; }
+        const int i1 = at(px + 1), j1 = at(py + 1);
+        if (y == i1 || j1 == x) return;
+        const double dij = known == 0 ? dk : d(x, y), d11 = known == 1 ? dk : d(i1, j1);
+        const double delta = ((dij + d11) - E[x]) - E[y];
+        cnt += 1;
+        offer(delta, (u64)x * (u64)n + (u64)y, bd, bk);
+    }
+
+    // Or-opt move (f, L, a, o); `known` says which attaching edge has the length dk: 0 = the one at a, 1 = the one at b
+    __device__ __forceinline__ void oro(int f, int pf, int L, int a, int pa, int o, int known, double dk) {
+        int dj = pa - (pf - 1);   // in [-(n - 2), n]
+        if (dj < 0) dj += n;
+        else if (dj >= n) dj -= n;
+        if (dj <= L) return;      // a in {p, f .. l}
+        const int l = at(pf + L - 1), bb = at(pa + 1);
+        const double d1 = known == 0 ? dk : (o ? d(a, l) : d(a, f));
+        const double d2 = known == 1 ? dk : (o ? d(f, bb) : d(l, bb));
+        const double delta = ((d1 + d2) - E[a]) - rem[(size_t)(L - 1) * n + f];
+        cnt += 1;
+        offer(delta, kKindBit | (u64)((((long long)f * 3 + (L - 1)) * n + a) * 2 + o), bd, bk);
+    }
+
+    // the ten Or-opt moves that attach the segment with the edge x -> y (x ahead of y in the new tour)
+    __device__ __forceinline__ void roles(int x, int px, int y, int py, double dk) {
+        const int pa = or_wrap(py - 1, n), a = order[pa];
+#pragma unroll
+        for (int L = 1; L <= 3; ++L) {
+            oro(y, py, L, x, px, 0, 0, dk);                              // (a, f) = (x, y)
+            const int pf = or_wrap(px - (L - 1), n);
+            oro(order[pf], pf, L, a, pa, 0, 1, dk);                      // (l, b) = (x, y)
+            if (L > 1) {
+                const int pg = or_wrap(py - (L - 1), n);
+                oro(order[pg], pg, L, x, px, 1, 0, dk);                  // (a, l) = (x, y)
+                oro(x, px, L, a, pa, 1, 1, dk);                          // (f, b) = (x, y)
+            }
+        }
+    }
+};
+
+// One lane per list entry (v, k), u = nbr[v][k]: the moves whose new (2-opt) or attaching (Or-opt) edge is {v, u}.
+template <int WT, bool INT>
+__global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coord, const int *__restrict__ orders,
+                                                 const int *__restrict__ poss, NlState *__restrict__ st, int n, int K, int kinds,
+                                                 const int *__restrict__ nbr, const double *__restrict__ Es,
+                                                 const double *__restrict__ rems, NlBest *__restrict__ parts) {
+    const int b = blockIdx.y;
+    if (st[b].done) return;
+    __shared__ double sd[4];
+    __shared__ u64 sk[4];
+    NlView<WT, INT> w;
+    w.coord = coord; w.order = orders + (size_t)b * n; w.pos = poss + (size_t)b * n;
+    w.E = Es + (size_t)b * n; w.rem = rems + (size_t)b * 3 * n; w.n = n;
+    w.bd = INFINITY; w.bk = kNoKey; w.cnt = 0;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < (long long)n * K) {
+        const int v = (int)(t / K);
+        const int u = nbr[t];
+        if (u != v) {
+            const int pv = w.pos[v], pu = w.pos[u];
+            const double dk = w.d(v, u);
+            if (kinds & TSP_NL_2OPT) {
+                w.two(v, pv, u, pu, 0, dk);                                      // {i, j} = {v, u}
+                const int qv = or_wrap(pv - 1, n), qu = or_wrap(pu - 1, n);
+                w.two(w.order[qv], qv, w.order[qu], qu, 1, dk);                  // {i1, j1} = {v, u}
+            }
+            if (kinds & TSP_NL_OROPT) {
+                w.roles(v, pv, u, pu, dk);
+                w.roles(u, pu, v, pv, dk);
+            }
+        }
+    }
+    double bd = w.bd;
+    u64 bk = w.bk;
+    block_argmin<true>(bd, bk, sd, sk);
+    if (threadIdx.x == 0) parts[(size_t)b * gridDim.x + blockIdx.x] = NlBest{bd, bk};
+    unsigned long long cnt = w.cnt;
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd((unsigned long long *)&st[b].deltas, cnt);
+}
+
+// Decision over the workgroups' candidates, then the move.  One workgroup per tour.
+__global__ __launch_bounds__(kPickThreads) void k_nl_pick_apply(int *__restrict__ orders, int *__restrict__ poss,
+                                                                NlState *__restrict__ st, int n, int nparts,
+                                                                const NlBest *__restrict__ parts) {
+    const int b = blockIdx.x;
+    NlState &S = st[b];
+    if (S.done) return;
+    __shared__ double sd[kPickThreads / 64];
+    __shared__ u64 sk[kPickThreads / 64];
+    const int tid = threadIdx.x;
+    if (S.max_moves >= 0 && S.moves >= S.max_moves) {
+        if (tid == 0) S.done = 1;
+        return;
+    }
+    const NlBest *part = parts + (size_t)b * nparts;
+    double bd = INFINITY; u64 bk = kNoKey;
+    for (int r = tid; r < nparts; r += kPickThreads) {
+        const NlBest q = part[r];
+        if (q.k != kNoKey && better(q.d, q.k, bd, bk)) { bd = q.d; bk = q.k; }
+    }
+    block_argmin<true>(bd, bk, sd, sk);
+    __syncthreads();
+    if (tid == 0) { S.decisions += 1; if (bk == kNoKey) S.done = 1; }
+    if (bk == kNoKey) return;
+    int *order = orders + (size_t)b * n, *pos = poss + (size_t)b * n;
+    if (!(bk & kKindBit)) {
+        // 2-opt: the forward path i1 .. j (positions pi + 1 .. pi + len) is reversed in place
+        const int i = (int)(bk / (u64)n), j = (int)(bk % (u64)n);
+        const int pi = pos[i];
+        int len = pos[j] - pi;
+        if (len < 0) len += n;
+        __syncthreads();
+        if (tid == 0) {
+            S.moves += 1; S.moves_2opt += 1; S.reversed += len - 1;   // the successors rewritten: all of the path but i1's
+            if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
+        }
+        for (int q = tid; q < len / 2; q += kPickThreads) {
+            const int pa = or_wrap(pi + 1 + q, n), pb = or_wrap(pi + len - q, n);
+            const int va = order[pa], vb = order[pb];
+            order[pa] = vb; pos[vb] = pa;
+            order[pb] = va; pos[va] = pb;
+        }
+        return;
+    }
+    const u64 key = bk & (kKindBit - 1);
+    const int o = (int)(key & 1);
+    const u64 t = key >> 1;
+    const int a = (int)(t % (u64)n);
+    const int fl = (int)(t / (u64)n);
+    const int L = fl % 3 + 1, f = fl / 3;
+    const int i = pos[f], ja = pos[a];
+    int x[3] = {0, 0, 0};
+    for (int q = 0; q < L; ++q) x[q] = order[or_wrap(i + q, n)];
+    __syncthreads();   // every thread has read the tour before anything moves
+    if (tid == 0) {
+        S.moves += 1; S.moves_oropt += 1; S.moves_len[L - 1] += 1; S.moves_rev += o;
+        if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
+    }
+    or_shift_apply<kPickThreads>(order, pos, n, i, ja, L, o, x);
+}
+
+double wall_s() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+// Lists and scratch of one instance.
+struct NlData {
+    int K = 0;                 // 0: no lists
+    int *d_nbr = nullptr;      // n x K
+    int B = 0, nparts = 0, parts_K = 0;
+    NlState *d_st = nullptr;
+    NlState *h_st = nullptr;   // pinned
+    double *d_E = nullptr, *d_rem = nullptr, *d_cost = nullptr;
+    NlBest *d_part = nullptr;
+    void free_scratch() {
+        (void)hipFree(d_st); (void)hipHostFree(h_st); (void)hipFree(d_E); (void)hipFree(d_rem); (void)hipFree(d_cost);
+        (void)hipFree(d_part);
+        d_st = nullptr; h_st = nullptr; d_E = d_rem = d_cost = nullptr; d_part = nullptr; B = 0;
+    }
+    ~NlData() { free_scratch(); (void)hipFree(d_nbr); }
+};
+
+NlData *nl_data(tsp_dev_inst *inst) {
+    if (!inst->nl_data) inst->nl_data = new NlData();
+    return static_cast<NlData *>(inst->nl_data);
+}
+
+int scratch_alloc(NlData *x, int B, int n, int K) {
+    x->free_scratch();
+    x->nparts = (int)(((long long)n * K + 255) / 256);
+    x->parts_K = K;
+    const size_t Bn = (size_t)B * n;
+    TSP_HIP_TRY(hipMalloc(&x->d_st, sizeof(NlState) * B));
+    TSP_HIP_TRY(hipHostMalloc(&x->h_st, sizeof(NlState) * B, hipHostMallocDefault));
+    TSP_HIP_TRY(hipMalloc(&x->d_E, sizeof(double) * Bn));
+    TSP_HIP_TRY(hipMalloc(&x->d_rem, sizeof(double) * 3 * Bn));
+    TSP_HIP_TRY(hipMalloc(&x->d_cost, sizeof(double) * B));
+    TSP_HIP_TRY(hipMalloc(&x->d_part, sizeof(NlBest) * (size_t)B * x->nparts));
+    x->B = B;
+    return TSP_OK;
+}
+
+void launch_decision(tsp_dev_tours *t, NlData *x, int kinds) {
+    tsp_dev_inst *inst = t->inst;
+    hipStream_t s = inst->ctx->stream;
+    const int n = t->n, B = t->B;
+    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
+        hipLaunchKernelGGL((k_nl_prep<WTC, INTC>), dim3((n + 255) / 256, B), dim3(256), 0, s, inst->d_coord, t->d_order, x->d_st, n,
+                           x->d_E, x->d_rem);
+        hipLaunchKernelGGL((k_nl_scan<WTC, INTC>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
+                           x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part);
+    });
+    hipLaunchKernelGGL(k_nl_pick_apply, dim3(B), dim3(kPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts, x->d_part);
+}
+
+bool bad_k(const tsp_dev_inst *inst, int K) { return K < 1 || K > TSP_NL_MAX_K || K > inst->n - 1; }
+
+}  // namespace
+
+tsp_dev_tours *tsp_scratch_tours(tsp_dev_inst *inst, int B, bool *owned, int *rc);   // api.hip
+int tsp_grid_tour_cost(tsp_dev_tours *t, double *d_out);                          // two_opt_grid.hip
+
+void tsp_nl_data_free(void *p) { delete static_cast<NlData *>(p); }
+
+extern "C" {
+
+int tsp_dev_inst_knn_build(tsp_dev_inst *inst, int K, float *kernel_ms) {
+    if (!inst || bad_k(inst, K)) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
+    hipStream_t s = inst->ctx->stream;
+    const int waves = (n + 63) / 64;
+    const int Cc0 = std::max(1, std::min(kKnnChunks, (kKnnWaves + waves - 1) / waves));
+    const int CH = (n + Cc0 - 1) / Cc0, Cc = (n + CH - 1) / CH;
+    DevBuf<double> pd;
+    DevBuf<int> pi, nbr;
+    TSP_HIP_TRY(pd.alloc((size_t)Cc * kK * n));
+    TSP_HIP_TRY(pi.alloc((size_t)Cc * kK * n));
+    TSP_HIP_TRY(nbr.alloc((size_t)n * K));
+    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
+    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
+        hipLaunchKernelGGL((k_knn_scan<WTC, INTC>), dim3((n + 255) / 256, Cc), dim3(256), 0, s, inst->d_coord, n, CH, pd.p, pi.p);
+    });
+    hipLaunchKernelGGL(k_knn_merge, dim3((n + 255) / 256), dim3(256), 0, s, n, Cc, K, pd.p, pi.p, nbr.p);
+    TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
+    TSP_HIP_TRY(hipEventSynchronize(inst->ev1));
+    TSP_HIP_TRY(hipGetLastError());
+    float ms = 0.f;
+    TSP_HIP_TRY(hipEventElapsedTime(&ms, inst->ev0, inst->ev1));
+    if (kernel_ms) *kernel_ms = ms;
+    NlData *x = nl_data(inst);
+    (void)hipFree(x->d_nbr);
+    x->d_nbr = nbr.p; nbr.p = nullptr;
+    x->K = K;
+    return TSP_OK;
+}
+
+int tsp_dev_inst_knn_set(tsp_dev_inst *inst, int K, const int *nbr) {
+    if (!inst || !nbr || bad_k(inst, K)) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    for (int v = 0; v < n; ++v)
+        for (int k = 0; k < K; ++k) {
+            const int u = nbr[(size_t)v * K + k];
+            if (u < 0 || u >= n || u == v) return TSP_DEV_E_ARG;
+        }
+    TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
+    DevBuf<int> d;
+    TSP_HIP_TRY(d.alloc((size_t)n * K));
+    TSP_HIP_TRY(hipMemcpy(d.p, nbr, sizeof(int) * (size_t)n * K, hipMemcpyHostToDevice));
+    TSP_HIP_TRY(hipStreamSynchronize(inst->ctx->stream));   // nothing queued may still read the old lists
+    NlData *x = nl_data(inst);
+    (void)hipFree(x->d_nbr);
+    x->d_nbr = d.p; d.p = nullptr;
+    x->K = K;
+    return TSP_OK;
+}
+
+int tsp_dev_inst_knn_get(tsp_dev_inst *inst, int *K, int *nbr) {
+    if (!inst || !K) return TSP_DEV_E_ARG;
+    const NlData *x = static_cast<const NlData *>(inst->nl_data);
+    *K = x ? x->K : 0;
+    if (!nbr || *K == 0) return TSP_OK;
+    TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
+    TSP_HIP_TRY(hipStreamSynchronize(inst->ctx->stream));
+    TSP_HIP_TRY(hipMemcpy(nbr, x->d_nbr, sizeof(int) * (size_t)inst->n * x->K, hipMemcpyDeviceToHost));
+    return TSP_OK;
+}
+
+int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                   int64_t max_moves, double time_limit_s, tsp_nl_opt_stats *stats) {
+    if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
+    if (kinds < 1 || kinds > (TSP_NL_2OPT | TSP_NL_OROPT)) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
+    const double t0 = wall_s();
+    TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
+    hipStream_t s = inst->ctx->stream;
+    bool owned = false;
+    int rc = TSP_OK;
+    tsp_dev_tours *t = tsp_scratch_tours(inst, B, &owned, &rc);
+    if (rc) return rc;
+    struct Own { tsp_dev_tours *t; bool o; ~Own() { if (o) tsp_dev_tours_destroy(t); } } own{t, owned};
+    rc = tsp_dev_tours_upload(t, succ, succ_stride, tour_stride, obj);   // checks every successor list
+    if (rc) return rc;
+    NlData *x = nl_data(inst);
+    if (x->K == 0) {
+        rc = tsp_dev_inst_knn_build(inst, std::min(TSP_NL_DEFAULT_K, n - 1), nullptr);
+        if (rc) return rc;
+    }
+    if (x->B != B || x->parts_K != x->K) {
+        rc = scratch_alloc(x, B, n, x->K);
+        if (rc) { x->free_scratch(); return rc; }
+    }
+    // a kind without any move at this size is left out: 2-opt needs four nodes, Or-opt five
+    if (n < 4) kinds &= ~TSP_NL_2OPT;
+    if (n < 5) kinds &= ~TSP_NL_OROPT;
+    const bool trivial = kinds == 0 || max_moves == 0;
+    for (int b = 0; b < B; ++b) {
+        NlState z;
+        memset(&z, 0, sizeof z);
+        z.max_moves = max_moves < 0 ? -1 : max_moves;
+        z.done = trivial ? 1 : 0;
+        x->h_st[b] = z;
+    }
+    TSP_HIP_TRY(hipMemcpyAsync(x->d_st, x->h_st, sizeof(NlState) * B, hipMemcpyHostToDevice, s));
+    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
+    int status = TSP_OK;
+    if (!trivial) {
+        double tq = wall_s();
+        launch_decision(t, x, kinds);
+        int batch = 4, queued = 1;
+        for (;;) {
+            TSP_HIP_TRY(hipMemcpyAsync(x->h_st, x->d_st, sizeof(NlState) * B, hipMemcpyDeviceToHost, s));
+            TSP_HIP_TRY(hipStreamSynchronize(s));
+            TSP_HIP_TRY(hipGetLastError());
+            bool all = true;
+            for (int b = 0; b < B; ++b) all = all && x->h_st[b].done;
+            if (all) break;
+            const double now = wall_s();
+            if (time_limit_s > 0 && now - t0 > time_limit_s) { status = TSP_TIME_LIMIT_EXCEEDED; break; }
+            int next = batch;
+            if (time_limit_s > 0) {
+                // no more decisions than the budget left holds at the last batch's rate
+                const double per = (now - tq) / queued, left = time_limit_s - (now - t0);
+                if (per > 0.0) next = (int)std::max(1.0, std::min((double)batch, left / per));
+            }
+            // decisions queued back to back; those behind a tour's last one return at once (done)
+            tq = now;
+            for (int k = 0; k < next; ++k) launch_decision(t, x, kinds);
+            queued = next;
+            batch = std::min(batch * 2, 256);
+        }
+    }
+    {
+        int r2 = tsp_grid_tour_cost(t, x->d_cost);
+        if (r2) return r2;
+    }
+    TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
+    TSP_HIP_TRY(hipEventSynchronize(inst->ev1));
+    TSP_HIP_TRY(hipGetLastError());
+    float ms = 0.f;
+    TSP_HIP_TRY(hipEventElapsedTime(&ms, inst->ev0, inst->ev1));
+    std::vector<double> cost((size_t)B);
+    TSP_HIP_TRY(hipMemcpyAsync(cost.data(), x->d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+    TSP_HIP_TRY(hipMemcpyAsync(x->h_st, x->d_st, sizeof(NlState) * B, hipMemcpyDeviceToHost, s));
+    rc = tsp_dev_tours_download(t, succ, succ_stride, tour_stride, nullptr, nullptr);   // (synchronises the stream)
+    if (rc) return rc;
+    for (int b = 0; b < B; ++b) {
+        obj[b] = cost[b];
+        if (stats) {
+            const NlState &z = x->h_st[b];
+            tsp_nl_opt_stats &o = stats[b];
+            memset(&o, 0, sizeof o);
+            o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
+            for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
+            o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
+            o.seconds = wall_s() - t0; o.device_ms = ms;
+        }
+    }
+    return status;
+}
+
+}  // extern "C"

@@ -15,7 +15,7 @@
 // Per row (f, L) the cache holds the lexicographically smallest (delta, key) among its improving candidates, or none.
 // A row whose segment, p and s kept their succ / pred and whose cached insertion edge still exists keeps every old
 // candidate's delta, so its new best is min(cached, candidates on the new edges): both paths take the same decisions.
-#include "two_opt_common.hpp"
+#include "or_opt_shift.hpp"
 
 #include <time.h>
 #include <algorithm>
@@ -348,35 +348,7 @@ __global__ __launch_bounds__(kPickThreads) void k_or_pick_apply(int *__restrict_
         S.moves += 1; S.moves_len[L - 1] += 1; S.moves_rev += o;
         if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
     }
-    int m1 = ja - (i + L);
-    if (m1 < 0) m1 += n;
-    m1 += 1;                      // nodes s .. a
-    const int m2 = n - L - m1;    // nodes b .. p
-    int seg0;
-    if (m1 <= m2) {   // s .. a move back by L (ascending chunks: a chunk's writes lie below every later chunk's reads)
-        for (int t0 = 0; t0 < m1; t0 += kPickThreads) {
-            const int q = t0 + tid;
-            const int v = q < m1 ? order[wrap(i + L + q, n)] : -1;
-            __syncthreads();
-            if (v >= 0) { const int np = wrap(i + q, n); order[np] = v; pos[v] = np; }
-            __syncthreads();
-        }
-        seg0 = i + m1;
-    } else {          // b .. p move on by L (descending chunks)
-        for (int t0 = ((m2 - 1) / kPickThreads) * kPickThreads; t0 >= 0; t0 -= kPickThreads) {
-            const int q = t0 + tid;
-            const int v = q < m2 ? order[wrap(ja + 1 + q, n)] : -1;
-            __syncthreads();
-            if (v >= 0) { const int np = wrap(ja + 1 + L + q, n); order[np] = v; pos[v] = np; }
-            __syncthreads();
-        }
-        seg0 = ja + 1;
-    }
-    if (tid < L) {
-        const int v = o ? x[L - 1 - tid] : x[tid];
-        const int np = wrap(seg0 + tid, n);
-        order[np] = v; pos[v] = np;
-    }
+    or_shift_apply<kPickThreads>(order, pos, n, i, ja, L, o, x);
 }
 
 double wall_s() {

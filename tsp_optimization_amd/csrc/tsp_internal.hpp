@@ -123,6 +123,7 @@ struct tsp_dev_inst {
     std::vector<double> h_xy;   // host copy of the raw coordinates (2n)
     tsp::Switches sw;           // the TSP_* switches as they stood when this handle was created
     void *or_scratch = nullptr; // Or-opt buffers of the last batch size (or_opt.hip)
+    void *nl_data = nullptr;    // neighbour lists and the buffers of their descent (nl_opt.hip)
 };
 
 struct tsp_dev_tabu {

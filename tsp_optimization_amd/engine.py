@@ -12,6 +12,9 @@ FIRST, BEST = 0, 1
 GREEDY, GRASP = 0, 1
 ENGINE_AUTO, ENGINE_GRID, ENGINE_LDS, ENGINE_CLUSTER = 0, 1, 2, 3
 OK, WRONG_STARTING_NODE, TIME_LIMIT_EXCEEDED = 0, 1, 2
+E_ARG = -3
+NL_2OPT, NL_OROPT = 1, 2
+NL_MAX_K, NL_DEFAULT_K = 16, 10
 
 
 class TspDeviceError(RuntimeError):
@@ -33,6 +36,17 @@ class OrOptStats(C.Structure):
     _fields_ = [("sweeps", C.c_int64), ("evals", C.c_int64), ("moves", C.c_int64), ("moves_by_len", C.c_int64 * 3),
                 ("moves_reversed", C.c_int64), ("deltas_executed", C.c_int64), ("rounds", C.c_int64),
                 ("seconds", C.c_double), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["moves_by_len"] = list(self.moves_by_len)
+        return d
+
+
+class NlOptStats(C.Structure):
+    _fields_ = [("decisions", C.c_int64), ("moves", C.c_int64), ("moves_2opt", C.c_int64), ("moves_oropt", C.c_int64),
+                ("moves_by_len", C.c_int64 * 3), ("moves_reversed", C.c_int64), ("reversed", C.c_int64),
+                ("deltas_executed", C.c_int64), ("seconds", C.c_double), ("device_ms", C.c_double)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -120,6 +134,10 @@ def lib():
         orp = C.POINTER(OrOptStats)
         L.tsp_dev_or_opt.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double, orp]
         L.tsp_dev_two_opt_or_opt.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_double, sp, orp]
+        L.tsp_dev_inst_knn_build.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+        L.tsp_dev_inst_knn_set.argtypes = [vp, C.c_int, ip]
+        L.tsp_dev_inst_knn_get.argtypes = [vp, ip, ip]
+        L.tsp_dev_nl_opt.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double, C.POINTER(NlOptStats)]
         _lib = L
     return _lib
 
@@ -139,6 +157,7 @@ EXPORTED = [
     "tsp_dev_multistart_allreduce_group", "tsp_dev_multistart_bcast_tour_group",
     "tsp_dev_multistart_allreduce_f64", "tsp_dev_multistart_allreduce_f64_group",
     "tsp_dev_or_opt", "tsp_dev_two_opt_or_opt",
+    "tsp_dev_inst_knn_build", "tsp_dev_inst_knn_set", "tsp_dev_inst_knn_get", "tsp_dev_nl_opt",
 ]
 
 COMM_ID_BYTES = 128
@@ -315,6 +334,44 @@ class Instance:
         if single:
             return rc, succ2[0], float(o[0]), s2[0], so[0]
         return rc, succ2, o, s2, so
+
+    # -- candidate neighbour lists (extension) ----------------------------------------------
+    def knn_build(self, K=NL_DEFAULT_K):
+        """Exact K-nearest lists built on the device and kept in the handle (tsp_dev_inst_knn_build) -> kernel ms"""
+        ms = C.c_float(0)
+        _check(lib().tsp_dev_inst_knn_build(self._h, int(K), C.byref(ms)))
+        return ms.value
+
+    def knn_set(self, nbr):
+        """The caller's own (n, K) candidate lists (tsp_dev_inst_knn_set)."""
+        nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+        if nbr.ndim != 2 or nbr.shape[0] != self.n:
+            raise TspDeviceError("tsp_dev call failed with %d (lists must be (n, K))" % E_ARG)
+        _check(lib().tsp_dev_inst_knn_set(self._h, nbr.shape[1], _i(nbr)))
+
+    def knn(self):
+        """-> the handle's lists as an (n, K) int32 array, or None when it has none"""
+        K = C.c_int(0)
+        _check(lib().tsp_dev_inst_knn_get(self._h, C.byref(K), None))
+        if K.value == 0:
+            return None
+        out = np.empty((self.n, K.value), dtype=np.int32)
+        _check(lib().tsp_dev_inst_knn_get(self._h, C.byref(K), _i(out)))
+        return out
+
+    def nl_opt(self, succ, obj=None, kinds=NL_2OPT | NL_OROPT, max_moves=-1, time_limit=-1.0):
+        """2-opt + Or-opt descent over the neighbour-list neighbourhood (tsp_dev_nl_opt).  succ [n] or [B,n].
+        -> (status, succ', obj' (recomputed cost), stats dict(s))"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
+        st = (NlOptStats * B)()
+        rc = lib().tsp_dev_nl_opt(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
+        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
+        stats = [s.as_dict() for s in st]
+        if single:
+            return rc, succ2[0], float(o[0]), stats[0]
+        return rc, succ2, o, stats
 
     def perm_cost(self, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

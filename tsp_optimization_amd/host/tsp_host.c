@@ -137,6 +137,8 @@ static __thread long long t_sweeps, t_evals, t_moves, t_grasp_iter_starts;
 static __thread double t_driver_loop_s;   /* seconds the last tsp_host_tabu / tsp_host_vns spent in its iteration loop (not the initial solution) */
 static __thread double t_device_ms;
 static __thread tsp_or_opt_stats t_or_stats;   /* the Or-opt phases of the last alg_oropt / alg_2opt_oropt */
+static __thread tsp_nl_opt_stats t_nl_stats;   /* the last alg_nl_opt */
+static int g_knn_k = TSP_NL_DEFAULT_K;         /* list length of alg_nl_opt (tsp_host_set_knn) */
 
 static void dev_fail(const char *what, int rc) {
     LOG_E("%s failed with %d %s (this build has no CPU path: an MI355X and libtsp_hip.so are required)", what, rc,
@@ -517,6 +519,47 @@ int alg_2opt_oropt(instance *inst) {
 int HEU_2opt_oropt_greedy(instance *inst) { (void)HEU_greedy(inst); return alg_2opt_oropt(inst); }
 int HEU_2opt_oropt_grasp(instance *inst) { (void)HEU_Grasp(inst); return alg_2opt_oropt(inst); }
 int HEU_2opt_oropt_extramileage(instance *inst) { (void)HEU_extramileage(inst); return alg_2opt_oropt(inst); }
+
+/* ---- neighbour lists (extension) ------------------------------------------------------------------------- */
+
+int tsp_host_set_knn(int K) {
+    if (K < 1 || K > TSP_NL_MAX_K) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_knn_k = K;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+void tsp_host_last_nl_stats(tsp_nl_opt_stats *out) {
+    if (out) *out = t_nl_stats;
+}
+
+/* 2-opt + Or-opt over the lists of the min(K, n - 1) nearest nodes (built when the cached instance has none of that length) */
+int alg_nl_opt(instance *inst) {
+    tsp_nl_opt_stats st;
+    memset(&st, 0, sizeof st);
+    double obj = inst->solution.obj_best;
+    pthread_mutex_lock(&g_lock);
+    tsp_dev_inst *dev = dev_inst_locked(inst);
+    const int want = g_knn_k < inst->num_nodes - 1 ? g_knn_k : inst->num_nodes - 1;
+    int have = 0;
+    int rc = tsp_dev_inst_knn_get(dev, &have, NULL);
+    if (rc == 0 && have != want) rc = tsp_dev_inst_knn_build(dev, want, NULL);
+    if (rc == 0)
+        rc = tsp_dev_nl_opt(dev, TSP_NL_2OPT | TSP_NL_OROPT, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)inst->num_nodes, &obj,
+                            -1, limit_of(inst), &st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_nl_opt", rc);
+    inst->solution.obj_best = obj;
+    t_nl_stats = st;
+    if (rc == TIME_LIMIT_EXCEEDED) LOG_I("neighbour-list heuristics time exceeded");
+    return rc;
+}
+
+/* construction + alg_nl_opt: the constructive status is overwritten */
+int HEU_nl_greedy(instance *inst) { (void)HEU_greedy(inst); return alg_nl_opt(inst); }
+int HEU_nl_grasp(instance *inst) { (void)HEU_Grasp(inst); return alg_nl_opt(inst); }
+int HEU_nl_extramileage(instance *inst) { (void)HEU_extramileage(inst); return alg_nl_opt(inst); }
 
 /* ---- VNS (src/vns.c) ------------------------------------------------------------------------------------- */
 
