@@ -1,0 +1,93 @@
+// exh_arith.hpp -- the arithmetic of the exhaustive sweep's distances (two_opt_exh.hpp), free of HIP: k_move_pos and k_exh
+// compile exactly this text for the device, tests/test_cpu_exh_arith.py compiles it with the host compiler and checks it against
+// integer arithmetic.  Every function is an exact integer identity on its stated domain; none of them rounds.  The layout of the
+// strips (exh_strip, at the end) lives here for the same reason.
+//
+// Squared distance from norms.  Positions are stored relative to one node of the instance, so every coordinate is an integer
+// of magnitude < 2^21 (the *_ICOORD metrics bound the instance's diagonal; the pads lie at -6e6).  With the record
+// (-2x, -2y, x^2 + y^2) of the row's position,
+//     s = cx * (-2 rx) + (cy * (-2 ry) + (cn + rn))  =  (cx - rx)^2 + (cy - ry)^2:
+// every operand and every partial result is an integer below 2^53 (norms < 2^43 for instance positions, 1.4e14 with a pad), so
+// the add and the two fmas are exact and s is the same number as dx * dx + dy * dy -- in three instructions instead of four.
+//
+// Integer root.  g is the hardware's approximate root of s (of s / 10 for ATT), |g - r| < 0.25 for the true root r < 2^21
+// (tsp_dist.hpp).  Rounding g itself -- no constant added first -- leaves the wanted integer at k or k + 1:
+//   EUC_2D   k = floor(g):  r in (k - 0.25, k + 1.25), so nint(r) is k or k + 1, and it is k + 1 iff s > k^2 + k;
+//   CEIL_2D  k = rint(g):   r in (k - 0.75, k + 0.75), so ceil(r) is k or k + 1, and it is k + 1 iff s > k^2;
+//   ATT      the same with r = sqrt(s / 10) and s > 10 k^2.
+// The residual e = s - k^2 (s - 10 k^2) is exact in fp64, one fma.  The margin on g is 0.5 on either side.
+#pragma once
+
+#if defined(__HIPCC__)
+#define TSP_EXH_HD __host__ __device__ __forceinline__
+#else
+#define TSP_EXH_HD inline
+#endif
+
+namespace tsp {
+
+enum : int { EXH_NINT = 0, EXH_CEIL = 1, EXH_ATT = 2 };
+
+// what one position contributes as a ROW of the sweep: 32 bytes, so that a batch of rows is one aligned scalar load
+struct alignas(32) ExhRec {
+    double m2x, m2y;   // -2 x, -2 y (relative coordinates)
+    double nrm;        // x^2 + y^2
+    int eprev;         // length of the tour edge that ENDS at this position: d(u_{p-1}, u_p); 0 at position 0 and on the pads
+    int pad_;
+};
+
+TSP_EXH_HD void exh_rec_xy(double x, double y, ExhRec &r) {
+    r.m2x = -2.0 * x;
+    r.m2y = -2.0 * y;
+    r.nrm = __builtin_fma(x, x, y * y);   // exact: integers, the sum < 2^53
+}
+
+// the column's own coordinate back from its record (exact: a power of two)
+TSP_EXH_HD double exh_col(double m2) { return -0.5 * m2; }
+
+TSP_EXH_HD double exh_s(double cx, double cy, double cn, double rm2x, double rm2y, double rn) {
+    return __builtin_fma(cx, rm2x, __builtin_fma(cy, rm2y, cn + rn));
+}
+
+// the argument of the hardware root
+template <int MODE>
+TSP_EXH_HD double exh_root_arg(double s) { return MODE == EXH_ATT ? s * 0.1 : s; }
+
+// the four stages after the root; k_exh issues each of them for all columns of a lane before the next
+template <int MODE>
+TSP_EXH_HD double exh_k(double g) { return MODE == EXH_NINT ? __builtin_floor(g) : __builtin_rint(g); }
+
+template <int MODE>
+TSP_EXH_HD double exh_e(double s, double k) { return __builtin_fma(MODE == EXH_ATT ? -10.0 * k : -k, k, s); }
+
+template <int MODE>
+TSP_EXH_HD bool exh_up(double k, double e) { return MODE == EXH_NINT ? e > k : e > 0.0; }
+
+TSP_EXH_HD int exh_ki(double k) { return (int)k; }
+
+TSP_EXH_HD int exh_d(int ki, bool up) { return ki + (up ? 1 : 0); }
+
+// the integer-valued distance of tsp_dist.hpp's int_root from s and the approximate root g of exh_root_arg(s)
+template <int MODE>
+TSP_EXH_HD int exh_round(double s, double g) {
+    const double k = exh_k<MODE>(g);
+    return exh_d(exh_ki(k), exh_up<MODE>(k, exh_e<MODE>(s, k)));
+}
+
+// The strips of pair-columns, right-aligned: strip s holds the D-columns q0 .. q0 + weff of its wave and the pair-rows
+// p' < rows.  The slack strips * weff - n sits in strip 0 (rows from the unclamped q0; q0 itself clamped to 0, so strip 0
+// overlaps strip 1: a pair evaluated twice cannot change an arg-min whose tie-break is strict).  Kernel and host
+// (tsp_dev_tours_create's shares) both count the row units with these.
+struct ExhStrip { int q0, rows; };
+TSP_EXH_HD int exh_strips(int n, int weff) { return (n + weff - 1) / weff; }
+TSP_EXH_HD ExhStrip exh_strip(int n, int weff, int s) {
+    const int q0 = s * weff - (exh_strips(n, weff) * weff - n);
+    return {q0 < 0 ? 0 : q0, q0 + weff - 1 < n - 1 ? q0 + weff - 1 : n - 1};
+}
+TSP_EXH_HD long long exh_total_rows(int n, int weff) {
+    long long total = 0;
+    for (int s = 0, ns = exh_strips(n, weff); s < ns; ++s) total += exh_strip(n, weff, s).rows;
+    return total;
+}
+
+}  // namespace tsp

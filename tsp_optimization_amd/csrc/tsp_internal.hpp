@@ -11,6 +11,7 @@
 
 #include "../../include/tsp_hip.h"
 #include "tsp_dist.hpp"
+#include "exh_arith.hpp"
 
 namespace tsp {
 
@@ -161,9 +162,9 @@ struct tsp_dev_tours {
     int cl_sorted_min_n = 8;         // ... the sorted scan (CLUSTER engine: ahead of its tiles scan from n = 52 up, tools/small_best.py)
     int sweep_blocks = 512;          // k_sweep blocks per tour
     int *d_cl_ticket = nullptr;      // k_sweep: arrival counters per tour x cluster
-    // exhaustive sweep in position order (two_opt_exh.hpp): the tour's coordinates, edge lengths and ids by position (padded)
-    double2 *d_pxy = nullptr;
-    int *d_pe = nullptr, *d_pid = nullptr;
+    // exhaustive sweep in position order (two_opt_exh.hpp): the tour's row records and ids by position (padded)
+    tsp::ExhRec *d_prec = nullptr;
+    int *d_pid = nullptr;
     int exh_share[4] = {0, 0, 0, 0};   // k_exh: rows per wave of each part of the grid (0: equal shares)
     int exh_gens = 0;                  // ... parts (= workgroups per CU)
     int exh_lds = 0;                 // k_exh: dynamic LDS a workgroup asks for (unused; it pins the number of workgroups per CU)

@@ -19,13 +19,16 @@
 // Every delta is still computed exactly (integer-valued distances from the exact roots of tsp_dist.hpp's int_root).
 //
 // Layout.  k_move_pos (one thread per position) carries the previous sweep's move out of place (as k_move_recs does)
-// and writes, in position order and padded: pxy[p] = coordinates of u_p (position n repeats position 0; further pads lie
-// far outside the instance), pe[p] = e[p] as int32, pid[p] = u_p.
-// k_exh: the pair-columns are cut into strips of W - 1 (W = 64 RJ columns of D per wave, RJ adjacent columns per lane);
-// a strip's rows are its units of work, and the units of all strips, laid end to end, are dealt to the waves in equal
-// contiguous ranges (every wave does the same number of row steps; at most two strips per wave).  Per row step a lane
+// and writes, in position order and padded: rec[p] = the record of u_p (exh_arith.hpp: -2x, -2y and the norm of its
+// coordinates relative to node 0, and e[p - 1]; position n repeats position 0; further pads lie far outside the instance),
+// pid[p] = u_p.
+// k_exh: the pair-columns are cut into strips of W - 1 (W = 64 RJ columns of D per wave, RJ adjacent columns per lane),
+// laid out from the RIGHT end (exh_strip: the partial strip is the leftmost one, which has the fewest rows);
+// a strip's rows are its units of work, and the units of all strips, laid end to end, are dealt to the waves in
+// contiguous ranges (at most two strips per wave).  Per row step a lane
 // computes D(p, q) for its RJ columns (row operands are wave-uniform: scalar loads, no LDS), forms
-//     sum = [D(p - 1, q - 1) - e[q - 1]] + D(p, q)           (the bracket: own register, or v_add_u32_dpp wave_shr:1)
+//     sum = D(p - 1, q - 1) + D(p, q) - e[q - 1]             (one three-operand add; D(p - 1, q - 1): own register, or
+//                                                             v_mov_b32_dpp wave_shr:1 for the lane's first column)
 // and compares it with wbd + e[p - 1], wbd = the best delta any lane of the WAVE has seen so far: a wave-uniform bound, so the
 // common path is one integer minimum per pair and one compare against a scalar per row step, and a rarely taken branch
 // does the exact bookkeeping (delta, tie-break on node ids) for the few pairs that reach that bound -- about ln(pairs of the
@@ -34,12 +37,9 @@
 // (atomicMin on improvement, re-read every 16 rows: 4 096 waves on one L2 line cost more than the pruning saves, 69.6 us).
 #pragma once
 #include "two_opt_step.hpp"
+#include "exh_arith.hpp"
 
 #pragma clang fp contract(off)
-
-#ifndef TSP_EXH_EXP
-#define TSP_EXH_EXP 0
-#endif
 
 namespace tsp {
 
@@ -53,62 +53,62 @@ __device__ unsigned long long g_exh_t[8];
 
 constexpr int kExhPad = 1152;          // positions past n that k_move_pos fills (>= the widest strip + 2)
 constexpr int kExhCluster = 32;        // blocks per first-level arrival counter
-constexpr int kRowBatch = 4;           // rows whose operands one scalar load instruction fetches
+constexpr int kRowBatch = 4;           // rows whose records one batch of scalar loads fetches
 constexpr int kExhRJ = 4;              // k_exh: columns per lane (8 and 16, and 1 and 2, measured slower)
 
 template <int WT>
 constexpr bool exh_metric() { return WT == WT_EUC_2D_ICOORD || WT == WT_CEIL_2D_ICOORD || WT == WT_ATT_ICOORD; }
 
-// the exact integer-valued distance of tsp_dist.hpp's int_root as an int32
 template <int WT>
-__device__ __forceinline__ int exh_dist(double cx, double cy, double rx, double ry) {
-    const double dx = cx - rx, dy = cy - ry;                  // exact: integer operands
-    const double s = __builtin_fma(dx, dx, dy * dy);          // exact: < 2^53, so fused or not is the same number
-    if constexpr (WT == WT_EUC_2D_ICOORD) {
-        const double k = floor(__builtin_amdgcn_sqrt(s) + 0.25);
-        const double e = __builtin_fma(-k, k, s);
-        return __double2int_rz(k) + (e > k ? 1 : 0);          // s > k^2 + k: the root rounds to k + 1
-    } else if constexpr (WT == WT_CEIL_2D_ICOORD) {
-        const double k = floor(__builtin_amdgcn_sqrt(s) + 0.75);
-        const double e = __builtin_fma(-k, k, s);
-        return __double2int_rz(k) + (e > 0.0 ? 1 : 0);
-    } else {
-        const double k = floor(__builtin_amdgcn_sqrt(s * 0.1) + 0.75);
-        const double e = __builtin_fma(-10.0 * k, k, s);
-        return __double2int_rz(k) + (e > 0.0 ? 1 : 0);
-    }
+constexpr int exh_mode() { return WT == WT_EUC_2D_ICOORD ? EXH_NINT : (WT == WT_CEIL_2D_ICOORD ? EXH_CEIL : EXH_ATT); }
+
+// the exact integer-valued distance of tsp_dist.hpp's int_root as an int32 (exh_arith.hpp)
+template <int WT>
+__device__ __forceinline__ int exh_dist(double cx, double cy, double cn, const ExhRec &r) {
+    const double s = exh_s(cx, cy, cn, r.m2x, r.m2y, r.nrm);
+    return exh_round<exh_mode<WT>()>(s, __builtin_amdgcn_sqrt(exh_root_arg<exh_mode<WT>()>(s)));
 }
 
 // The same for the RJ columns of a lane against one row, STAGE BY STAGE across the columns: the wave issues in order, so the RJ
-// dependent chains (sub -> mul -> fma -> sqrt -> add -> floor -> fma -> compare -> convert -> add-with-carry) only overlap if
+// dependent chains (add -> fma -> fma -> sqrt -> round -> fma -> compare -> convert -> add-with-carry) only overlap if
 // their instructions are interleaved in the stream.  Left to itself the scheduler keeps most of a chain together (fewer live
 // registers) and a lone wave then runs the chains one after the other (RJ = 16, one wave per SIMD: 2 960 cycles per row step
 // against 1 056 of issue).  The scheduling barriers pin the stage order.
 template <int WT, int RJ>
-__device__ __forceinline__ void exh_dist_row(const double (&cx)[RJ], const double (&cy)[RJ], double rx, double ry, int (&D)[RJ]) {
+__device__ __forceinline__ void exh_dist_row(const double (&cx)[RJ], const double (&cy)[RJ], const double (&cn)[RJ], const ExhRec &r,
+                                             int (&D)[RJ]) {
+    constexpr int M = exh_mode<WT>();
     double s[RJ], k[RJ], e[RJ];
+    int ki[RJ];
+    bool up[RJ];
 #pragma unroll
-    for (int q = 0; q < RJ; ++q) { const double dx = cx[q] - rx, dy = cy[q] - ry; s[q] = __builtin_fma(dx, dx, dy * dy); }
+    for (int q = 0; q < RJ; ++q) s[q] = exh_s(cx[q], cy[q], cn[q], r.m2x, r.m2y, r.nrm);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int q = 0; q < RJ; ++q) k[q] = __builtin_amdgcn_sqrt(WT == WT_ATT_ICOORD ? s[q] * 0.1 : s[q]);
+    for (int q = 0; q < RJ; ++q) k[q] = __builtin_amdgcn_sqrt(exh_root_arg<M>(s[q]));
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int q = 0; q < RJ; ++q) k[q] = floor(k[q] + (WT == WT_EUC_2D_ICOORD ? 0.25 : 0.75));
+    for (int q = 0; q < RJ; ++q) k[q] = exh_k<M>(k[q]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int q = 0; q < RJ; ++q) e[q] = __builtin_fma(WT == WT_ATT_ICOORD ? -10.0 * k[q] : -k[q], k[q], s[q]);
+    for (int q = 0; q < RJ; ++q) e[q] = exh_e<M>(s[q], k[q]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int q = 0; q < RJ; ++q) D[q] = __double2int_rz(k[q]) + ((WT == WT_EUC_2D_ICOORD ? e[q] > k[q] : e[q] > 0.0) ? 1 : 0);
+    for (int q = 0; q < RJ; ++q) { ki[q] = exh_ki(k[q]); up[q] = exh_up<M>(k[q], e[q]); }   // every compare before the first
+    __builtin_amdgcn_sched_barrier(0);   // add-with-carry, each with a carry register of its own (back to back they wait on VCC)
+#pragma unroll
+    for (int q = 0; q < RJ; ++q) {
+        D[q] = exh_d(ki[q], up[q]);
+        asm("" : "+v"(D[q]));   // D itself in a register (the next row needs it): the caller's sums are then one v_add3_u32 each
+    }
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// (1) the pending move, out of place; (2) the tour AFTER that move in position order: coordinates, edge lengths, ids.
+// (1) the pending move, out of place; (2) the tour AFTER that move in position order: records and ids.
 template <int WT, bool INT>
 __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__restrict__ coord, int *orders, int *poss, int *orders2,
-                                                           int *poss2, const TourState *__restrict__ states, double2 *__restrict__ pxy,
-                                                           int *__restrict__ pe, int *__restrict__ pid, int n) {
+                                                           int *poss2, const TourState *__restrict__ states, ExhRec *__restrict__ rec,
+                                                           int *__restrict__ pid, int n) {
     const int tour = blockIdx.y;
     const TourState *st = states + tour;
     if (st->done) return;
@@ -118,25 +118,28 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__rest
     if (k >= n + kExhPad) return;
     // every load of the current copy (which this kernel never writes) comes before the first store
     const int u = k < n ? mv.node_at(k) : (k == n ? mv.node_at(0) : -1);
-    const int v = k < n ? mv.node_at(k + 1 == n ? 0 : k + 1) : -1;
+    const int v = k >= 1 && k <= n ? mv.node_at(k - 1) : -1;   // the position before
     const double2 c0 = coord[0];
     double2 cu = make_double2(c0.x - 6.0e6, c0.y - 6.0e6);   // pads: farther from every node than any tour edge is long
     int len = 0;
     if (u >= 0) cu = coord[u];
-    if (v >= 0) { const double2 cv = coord[v]; len = (int)dist_xy<WT, INT>(cu.x, cu.y, cv.x, cv.y); }
+    if (v >= 0) { const double2 cv = coord[v]; len = (int)dist_xy<WT, INT>(cv.x, cv.y, cu.x, cu.y); }
     if (mv.L > 0 && k < n) {
         int *o_new = (st->parity ? orders : orders2) + base, *p_new = (st->parity ? poss : poss2) + base;
         o_new[k] = u;
         p_new[u] = k;
     }
-    pxy[pbase + k] = cu;
-    pe[pbase + k] = len;
+    ExhRec r;
+    exh_rec_xy(cu.x - c0.x, cu.y - c0.y, r);   // exact: integers whose difference is below 2^21 (the pads: 6e6)
+    r.eprev = len;
+    r.pad_ = 0;
+    rec[pbase + k] = r;
     pid[pbase + k] = u;
 }
 
 // RJ = kExhRJ columns per lane, four workgroups of four waves per CU (the host pins that with its LDS request)
 template <int WT, bool INT, int RJ>
-__global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const double2 *__restrict__ pxy_all, const int *__restrict__ pe_all,
+__global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const ExhRec *__restrict__ rec_all,
                                                       const int *__restrict__ pid_all, int waves_total, int4 share, int gens) {
     // the position arrays are kernel arguments of their own, restrict-qualified: the row operands are wave-uniform loads, and
     // the compiler only issues them as scalar loads (s_load: no vector-memory slot, no VGPRs) when it can prove that the
@@ -148,8 +151,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
     if (st->done) return;
     const int n = a.n, tid = threadIdx.x, lane = tid & 63;
     const size_t pbase = (size_t)tour * (n + kExhPad);
-    const double2 *__restrict__ pxy = pxy_all + pbase;
-    const int *__restrict__ pe = pe_all + pbase;
+    const ExhRec *__restrict__ rec = rec_all + pbase;
     const int *__restrict__ pid = pid_all + pbase;
 
 #ifdef TSP_STAMPS
@@ -158,9 +160,8 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
 #endif
     // ---- this wave's share: units [u_lo, u_hi) of the strips' rows laid end to end --------------------------------
     const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kScanThreads / 64) + (tid >> 6));
-    const int strips = (n + WEFF - 1) / WEFF;                       // pair-columns 0 .. n-1
-    long long total = 0;
-    for (int s = 0; s < strips; ++s) total += min(n - 1, s * WEFF + WEFF - 1);   // pair-rows p' < q' <= Q0 + WEFF - 1, p' <= n - 2
+    const int strips = exh_strips(n, WEFF);                         // pair-columns 0 .. n-1
+    const long long total = exh_total_rows(n, WEFF);                // pair-rows p' < q' <= q0 + WEFF - 1, p' <= n - 2
     // A SIMD serves its oldest wave first, and the workgroups of a CU are as old as their place in the grid: the first quarter of
     // the grid leaves its rows at 13.7 us, the others at 20.6 / 28.2 / 35.4 (equal shares; tools/diag_exh.py) -- while four waves
     // are active the SIMD's issue slots go 53 / 26 / 13 / 8 %.  share = the rows per wave of each part of the grid (quarters at four workgroups per CU) in those
@@ -197,52 +198,48 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
 
     long long cum = 0;
     for (int s = 0; s < strips && u_lo < u_hi; ++s) {
-        const int rows_s = min(n - 1, s * WEFF + WEFF - 1);
+        const ExhStrip strip = exh_strip(n, WEFF, s);
+        const int rows_s = strip.rows;
         if (u_lo >= cum + rows_s) { cum += rows_s; continue; }
         // segment of strip s: pair-rows [pa, pb)
         const int pa = (int)(u_lo - cum), pb = (int)min<long long>(rows_s, u_hi - cum);
         u_lo = cum + pb;
         cum += rows_s;
-        const int Q0 = s * WEFF;
-        double cx[RJ], cy[RJ];
-        int ce[RJ], S[RJ], qk[RJ];
+        const int Q0 = strip.q0;
+        double cx[RJ], cy[RJ], cn[RJ];
+        int nce[RJ], Dp[RJ], qk[RJ];   // nce[k] = -e[q_k - 1]: what the pair of column k removes on the column side
 #pragma unroll
         for (int k = 0; k < RJ; ++k) {
             qk[k] = Q0 + RJ * lane + k;
-            const double2 c = pxy[qk[k]];
-            cx[k] = c.x; cy[k] = c.y; ce[k] = pe[qk[k]];
+            const ExhRec c = rec[qk[k]];
+            cx[k] = exh_col(c.m2x); cy[k] = exh_col(c.m2y); cn[k] = c.nrm; nce[k] = -c.eprev;
         }
-        {   // row pa: distances only
-            const double2 r = pxy[pa];
+        // lane 0's first column has no left neighbour in this wave (the DPP hands it 0, and position 0 has no edge before it):
+        // its pair belongs to the strip on the left; should D alone ever pass the test below, the bookkeeping drops it
+        if (lane == 0) nce[0] = 0;
 #pragma unroll
-            for (int k = 0; k < RJ; ++k) S[k] = exh_dist<WT>(cx[k], cy[k], r.x, r.y) - ce[k];
+        for (int k = 0; k < RJ; ++k) asm("" : "+v"(nce[k]));   // kept negated: an addend of v_add3_u32, not a subtraction of its own
+        {   // row pa: distances only
+            const ExhRec r = rec[pa];
+#pragma unroll
+            for (int k = 0; k < RJ; ++k) Dp[k] = exh_dist<WT>(cx[k], cy[k], cn[k], r);
         }
         // rows p = pa + 1 .. pb: D(p, .), then the pairs (p - 1, q - 1).  Up to p = Q0 every column of the strip lies above
         // the row (q_k > p for every evaluated pair); beyond it the pairs on and below the diagonal are masked.
-        auto step = [&](int p, const double2 r_in, const int erow, auto pred_c) {
+        auto step = [&](int p, const ExhRec r, auto pred_c) {
             constexpr bool PRED = decltype(pred_c)::value;
             int D[RJ], sum[RJ];
-#if TSP_EXH_EXP == 1
-            double2 r;   // experiment: row operands in VGPRs
-            asm volatile("v_mov_b32 %0, %1" : "=v"(((int *)&r)[0]) : "s"(((const int *)&r_in)[0]));
-            asm volatile("v_mov_b32 %0, %1" : "=v"(((int *)&r)[1]) : "s"(((const int *)&r_in)[1]));
-            asm volatile("v_mov_b32 %0, %1" : "=v"(((int *)&r)[2]) : "s"(((const int *)&r_in)[2]));
-            asm volatile("v_mov_b32 %0, %1" : "=v"(((int *)&r)[3]) : "s"(((const int *)&r_in)[3]));
-#else
-            const double2 r = r_in;
-#endif
-            exh_dist_row<WT, RJ>(cx, cy, r.x, r.y, D);
-            // lane 0's first column has no left neighbour in this wave (the DPP hands it 0): its pair belongs to the strip on
-            // the left; should D alone ever pass the test below, the bookkeeping drops it (valid == false)
-            sum[0] = __builtin_amdgcn_update_dpp(0, S[RJ - 1], 0x138 /* wave_shr:1 */, 0xf, 0xf, true) + D[0];
+            const int erow = r.eprev;   // e[p - 1]
+            exh_dist_row<WT, RJ>(cx, cy, cn, r, D);
+            sum[0] = __builtin_amdgcn_update_dpp(0, Dp[RJ - 1], 0x138 /* wave_shr:1 */, 0xf, 0xf, true) + D[0] + nce[0];
 #pragma unroll
-            for (int k = 1; k < RJ; ++k) sum[k] = S[k - 1] + D[k];
+            for (int k = 1; k < RJ; ++k) sum[k] = Dp[k - 1] + D[k] + nce[k];
             const int thr = wbd + erow;   // scalar
             bool hit = false;
 #pragma unroll
             for (int k = 0; k < RJ; ++k) hit = hit || (sum[k] <= thr && (!PRED || qk[k] > p));
 #pragma unroll
-            for (int k = 0; k < RJ; ++k) S[k] = D[k] - ce[k];
+            for (int k = 0; k < RJ; ++k) Dp[k] = D[k];
             if (__builtin_expect(__any(hit), 0)) {
 #ifdef TSP_STAMPS
                 const unsigned long long sc0 = clock64();
@@ -256,28 +253,24 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
 #endif
             }
         };
-        // The row operands are wave-uniform: scalar loads, kRowBatch rows per load instruction, and the NEXT batch is on its way
+        // The row records are wave-uniform: scalar loads, kRowBatch rows per batch, and the NEXT batch is on its way
         // while this one is worked (a scalar load that misses the CU's constant cache takes longer than one row step: with a
         // prefetch distance of one row the waves spent a quarter of their cycles in s_waitcnt, SQ_WAIT_ANY).  Positions up to
-        // n + kRowBatch exist: k_move_pos pads.
-        struct RowsXY { double2 r[kRowBatch]; };
-        struct RowsE { int e[kRowBatch]; };
+        // n + 2 kRowBatch exist: k_move_pos pads.
+        struct Rows { ExhRec r[kRowBatch]; };
         const int p_plain = min(pb, Q0);
         int p = pa + 1;
-        RowsXY nx = *reinterpret_cast<const RowsXY *>(pxy + p);
-        RowsE ne = *reinterpret_cast<const RowsE *>(pe + p - 1);
+        Rows nx = *reinterpret_cast<const Rows *>(rec + p);
         for (; p <= pb; p += kRowBatch) {
-            const RowsXY cx4 = nx;
-            const RowsE ce4 = ne;
-            nx = *reinterpret_cast<const RowsXY *>(pxy + p + kRowBatch);
-            ne = *reinterpret_cast<const RowsE *>(pe + p + kRowBatch - 1);
+            const Rows cur = nx;
+            nx = *reinterpret_cast<const Rows *>(rec + p + kRowBatch);
             if (p + kRowBatch - 1 <= p_plain) {
 #pragma unroll
-                for (int u = 0; u < kRowBatch; ++u) step(p + u, cx4.r[u], ce4.e[u], std::false_type{});
+                for (int u = 0; u < kRowBatch; ++u) step(p + u, cur.r[u], std::false_type{});
             } else {
 #pragma unroll
                 for (int u = 0; u < kRowBatch; ++u)
-                    if (p + u <= pb) step(p + u, cx4.r[u], ce4.e[u], std::true_type{});   // the predicate is harmless above the diagonal
+                    if (p + u <= pb) step(p + u, cur.r[u], std::true_type{});   // the predicate is harmless above the diagonal
             }
         }
     }

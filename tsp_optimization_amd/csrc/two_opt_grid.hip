@@ -254,7 +254,7 @@ bool sorted_run(const tsp_dev_tours *t, int mode, const tsp_dev_tabu *tabu) {
 
 // BEST sweeps of this handle execute every delta expression through k_move_pos + k_exh (bounds off, integer-coordinate metric)
 bool exh_run(const tsp_dev_tours *t, int mode, const tsp_dev_tabu *tabu) {
-    return mode == TSP_2OPT_BEST && !tabu && t->exh_blocks > 0 && t->d_pxy && t->inst->filter_margin > 1e299 &&
+    return mode == TSP_2OPT_BEST && !tabu && t->exh_blocks > 0 && t->d_prec && t->inst->filter_margin > 1e299 &&
            (t->inst->wtype == WT_EUC_2D_ICOORD || t->inst->wtype == WT_CEIL_2D_ICOORD || t->inst->wtype == WT_ATT_ICOORD);
 }
 
@@ -340,11 +340,11 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
     if constexpr (exh_metric<WT>()) {
         if (exh_run(t, mode, tabu)) {
             hipLaunchKernelGGL((k_move_pos<WT, INT>), dim3((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B), dim3(kScanThreads), 0, s,
-                               t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2, t->d_state, t->d_pxy, t->d_pe, t->d_pid, t->n);
+                               t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2, t->d_state, t->d_prec, t->d_pid, t->n);
             a.flat_slots = t->exh_blocks;
             const int wt_ = t->exh_blocks * (kScanThreads / 64);
             const dim3 g(t->exh_blocks, 1, t->B);
-            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_pxy, t->d_pe, t->d_pid, wt_,
+            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_prec, t->d_pid, wt_,
                                make_int4(t->exh_share[0], t->exh_share[1], t->exh_share[2], t->exh_share[3]), t->exh_gens);
             return TSP_OK;
         }
@@ -1031,14 +1031,13 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
             t->exh_lds = std::min(65536, inst->ctx->lds_bytes / waves) - 1024;
         t->partial_per_tour = std::max(t->partial_per_tour, (size_t)t->exh_blocks);
         const size_t pn = (size_t)B * (inst->n + kExhPad);
-        TSP_HIP_TRY(hipMalloc(&t->d_pxy, pn * sizeof(double2)));
-        TSP_HIP_TRY(hipMalloc(&t->d_pe, pn * sizeof(int)));
+        TSP_HIP_TRY(hipMalloc(&t->d_prec, pn * sizeof(ExhRec)));
         TSP_HIP_TRY(hipMalloc(&t->d_pid, pn * sizeof(int)));
         {   // rows per wave for each of the `waves` equal parts of the grid (k_exh: the older a workgroup, the larger its share);
             // TSP_EXH_SHARES = per-cent figures (or "0": equal shares), the default measured on MI355X
             t->exh_share[0] = t->exh_share[1] = t->exh_share[2] = t->exh_share[3] = 0;
             t->exh_gens = 0;
-            int pc[4] = {52, 28, 13, 7};   // (tools/exh_shares.sh: 44.7 us per sweep against 45.7 with 53 / 26 / 13 / 8)
+            int pc[4] = {48, 29, 15, 8};   // (tools/exh_shares.sh: 42.2 us per sweep against 43.7 with 52 / 28 / 13 / 7)
             bool on = B == 1;
             const char *e = getenv("TSP_EXH_SHARES");
             if (e && *e) {
@@ -1046,9 +1045,7 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
                 const int got = sscanf(e, "%d,%d,%d,%d", &pc[0], &pc[1], &pc[2], &pc[3]);
                 on = on && got == waves && pc[0] > 0;
             }
-            const int W = 64 * kExhRJ, WEFF = W - 1, strips = (inst->n + WEFF - 1) / WEFF;
-            long long total = 0;
-            for (int sidx = 0; sidx < strips; ++sidx) total += std::min(inst->n - 1, sidx * WEFF + WEFF - 1);
+            const long long total = exh_total_rows(inst->n, 64 * kExhRJ - 1);   // the kernel's own count of its row units
             const long long wtot = (long long)t->exh_blocks * (kScanThreads / 64);
             const int sum = pc[0] + pc[1] + pc[2] + pc[3];
             if (on && sum > 0 && wtot % waves == 0) {
@@ -1090,7 +1087,7 @@ void tsp_dev_tours_destroy(tsp_dev_tours *t) {
     (void)hipFree(t->d_state_base); (void)hipFree(t->d_partial); (void)hipFree(t->d_slot_evals); (void)hipFree(t->d_ticket); (void)hipFree(t->d_rec);
     (void)hipFree(t->d_gmax); (void)hipFree(t->d_order2); (void)hipFree(t->d_pos2); (void)hipFree(t->d_pairtab); (void)hipFree(t->d_cl_ticket);
     (void)hipFree(t->d_row_ticket); (void)hipFree(t->d_row_evals); (void)hipFree(t->d_row_slot);
-    (void)hipFree(t->d_pxy); (void)hipFree(t->d_pe); (void)hipFree(t->d_pid);
+    (void)hipFree(t->d_prec); (void)hipFree(t->d_pid);
     (void)hipFree(t->d_cl_slots); (void)hipFree(t->d_cl_pairtab); (void)hipFree(t->d_cl_stats);
     (void)hipFree(t->d_chain); (void)hipHostFree(t->h_chain); (void)hipFree(t->d_order_snap); (void)hipFree(t->d_kick_result); (void)hipHostFree(t->h_kick_result); (void)hipHostFree(t->h_cl_err);
     (void)hipHostFree(t->h_state);
