@@ -383,6 +383,43 @@ typedef struct {
 int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride,
                    double *obj, int64_t max_moves, double time_limit_s, tsp_nl_opt_stats *stats);
 
+/* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
+ * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
+ * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.
+ * Weight of edge {i,j}, lo = min, hi = max:  w = (d(lo,hi) + pi[lo]) + pi[hi], evaluated in exactly this order.
+ * Edge order: lexicographic on (w, lo, hi) -- a strict total order, so the minimum spanning tree is unique.
+ * 1-tree (n >= 3, special node 0): the minimum spanning tree of nodes 1 .. n-1 under that order plus the two smallest edges at
+ * node 0 under the same order.  deg[v] = degree of v in it (the degrees sum to 2n).
+ * Value: W(pi) = sum of w(e) over the 1-tree - 2 * sum of pi[v].  Every tour costs at least W(pi), for every pi.  The sums are
+ * taken in a fixed order without floating-point atomics: two runs return the same bits.
+ * Ascent (host-visible scalars fp64): pi as given (NULL = zeros), lambda = lambda0, best = -inf, stall = 0; per iteration
+ *   1. the 1-tree, W and g = deg - 2;
+ *   2. W > best: best = W, pi_best = pi, stall = 0; else stall += 1 and, when it reaches patience, lambda /= 2, stall = 0;
+ *   3. |g|^2 == 0: the 1-tree is a tour: stop with tour_found = 1;
+ *   4. t = lambda (ub - W) / |g|^2,  pi += t (0.7 g + 0.3 g_prev)   (first iteration: g_prev = g);
+ *   5. stop after max_iters iterations or at the time limit;
+ * and best, pi_best are returned.  At the time limit: TSP_TIME_LIMIT_EXCEEDED with the best so far, which is a valid bound. */
+#define TSP_HK_DEFAULT_ITERS 300
+#define TSP_HK_DEFAULT_LAMBDA 2.0
+typedef struct {
+    int64_t iterations;     /* ascent iterations carried out (0 from tsp_dev_one_tree)                                      */
+    int64_t trees;          /* 1-trees built                                                                                */
+    int64_t rounds;         /* Boruvka rounds over all trees                                                                */
+    int64_t dists_executed; /* edge weights the scans evaluated (rows of the launched grid x (n - 1) columns per round)     */
+    int tour_found;         /* a 1-tree was a tour: the bound is the optimum                                                */
+    double lambda_final;
+    double seconds;         /* wall time of the call, host clock                                                            */
+    double device_ms;       /* device time of the call, HIP events on the engine's stream                                   */
+} tsp_lb_stats;
+/* One 1-tree for pi (NULL = zeros).  edges: n pairs (lo, hi), sorted; deg[n]; *value = W(pi).  Each output may be NULL.
+ * Penalties that are not finite: TSP_DEV_E_ARG. */
+int tsp_dev_one_tree(tsp_dev_inst *inst, const double *pi, int *edges, int *deg, double *value, tsp_lb_stats *stats);
+/* The ascent.  ub: the cost of any tour, finite and > 0; max_iters >= 1; lambda0 > 0; patience <= 0 = max(10, n / 20);
+ * time_limit_s <= 0 = unlimited (at least one iteration always runs).  pi (may be NULL): in, the start (zeros when NULL); out,
+ * pi_best.  *bound = best.  Bad arguments: TSP_DEV_E_ARG with the reason in tsp_dev_last_error(). */
+int tsp_dev_held_karp(tsp_dev_inst *inst, double ub, int max_iters, double lambda0, int patience, double time_limit_s,
+                      double *pi, double *bound, tsp_lb_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,12 @@ int HEU_nl_greedy(instance *inst);        /* HEU_greedy + alg_nl_opt       */
 int HEU_nl_grasp(instance *inst);         /* HEU_Grasp + alg_nl_opt        */
 int HEU_nl_extramileage(instance *inst);  /* HEU_extramileage + alg_nl_opt */
 
+/* ---- Held-Karp lower bound (extension; include/tsp_hip.h, tsp_dev_held_karp).  A library entry point only: no solver_type,
+ * no -method row.  Runs the ascent on the instance's device handle from zero penalties with TSP_HK_DEFAULT_LAMBDA and the
+ * default patience; ub = the cost of any tour (inst->solution.obj_best after a heuristic), max_iters <= 0 =
+ * TSP_HK_DEFAULT_ITERS, time_lim <= 0 = unlimited.  Returns the bound (valid also when the time limit ended the ascent). */
+double tsp_host_lower_bound(instance *inst, double ub, int max_iters, double time_lim);
+
 /* ---- src/tabusearch.c (externally linked there, not in its header) --------------------------- */
 int alg_2opt_tabu(instance *inst, int *skip_edge, int *stored_prev, const int iter, const int tenure); /* :107 */
 
@@ -244,6 +250,8 @@ void tsp_host_last_stats(long long *sweeps, long long *evals, long long *moves, 
 void tsp_host_last_or_stats(tsp_or_opt_stats *out);
 /* Counters of the last alg_nl_opt call of this thread. */
 void tsp_host_last_nl_stats(tsp_nl_opt_stats *out);
+/* Counters of the last tsp_host_lower_bound call of this thread. */
+void tsp_host_last_lb_stats(tsp_lb_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */
 void tsp_host_shutdown(void);
 

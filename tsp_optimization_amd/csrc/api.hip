@@ -25,6 +25,7 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
 
 void tsp_or_scratch_free(void *p);   // or_opt.hip
 void tsp_nl_data_free(void *p);      // nl_opt.hip
+void tsp_hk_data_free(void *p);      // held_karp.hip
 
 void *tsp_io_pool(tsp_dev_inst *inst, size_t bytes) {
     bytes = (bytes + 255) & ~(size_t)255;
@@ -56,6 +57,7 @@ static thread_local char g_last_error[512] = "";
 void set_last_error(const char *what, hipError_t e, const char *file, int line) {
     snprintf(g_last_error, sizeof g_last_error, "%s:%d: %s -> %s", file, line, what, hipGetErrorString(e));
 }
+void set_last_error_text(const char *text) { snprintf(g_last_error, sizeof g_last_error, "%s", text); }
 }  // namespace tsp
 
 // Single-tour calls (alg_2opt in a VNS / tabu / GA loop) reuse one tours handle and one event pair per
@@ -369,6 +371,7 @@ void tsp_dev_inst_destroy(tsp_dev_inst *inst) {
     if (inst->ev0) { (void)hipEventDestroy(inst->ev0); (void)hipEventDestroy(inst->ev1); }
     tsp_or_scratch_free(inst->or_scratch);
     tsp_nl_data_free(inst->nl_data);
+    tsp_hk_data_free(inst->hk_data);
     (void)hipFree(inst->d_coord); (void)hipFree(inst->d_sperm); (void)hipFree(inst->d_gbox); (void)hipFree(inst->d_sxy); (void)hipFree(inst->cons_pool);
     (void)hipFree(inst->d_rcoord); (void)hipFree(inst->d_sinv); (void)hipFree(inst->io_pool);
     delete inst;

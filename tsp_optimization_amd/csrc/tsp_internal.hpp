@@ -125,6 +125,7 @@ struct tsp_dev_inst {
     tsp::Switches sw;           // the TSP_* switches as they stood when this handle was created
     void *or_scratch = nullptr; // Or-opt buffers of the last batch size (or_opt.hip)
     void *nl_data = nullptr;    // neighbour lists and the buffers of their descent (nl_opt.hip)
+    void *hk_data = nullptr;    // 1-tree / Held-Karp buffers (held_karp.hip)
 };
 
 struct tsp_dev_tabu {
@@ -233,6 +234,7 @@ struct tsp_dev_tours {
 // ---- error plumbing ------------------------------------------------------------------------
 namespace tsp {
 void set_last_error(const char *what, hipError_t e, const char *file, int line);
+void set_last_error_text(const char *text);   // for failures that are not a HIP call's
 
 // Call-local device scratch: released when the scope ends, so an early error return leaks nothing.
 template <typename T>

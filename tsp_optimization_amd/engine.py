@@ -15,6 +15,7 @@ OK, WRONG_STARTING_NODE, TIME_LIMIT_EXCEEDED = 0, 1, 2
 E_ARG = -3
 NL_2OPT, NL_OROPT = 1, 2
 NL_MAX_K, NL_DEFAULT_K = 16, 10
+HK_DEFAULT_ITERS, HK_DEFAULT_LAMBDA = 300, 2.0
 
 
 class TspDeviceError(RuntimeError):
@@ -52,6 +53,14 @@ class NlOptStats(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["moves_by_len"] = list(self.moves_by_len)
         return d
+
+
+class LbStats(C.Structure):
+    _fields_ = [("iterations", C.c_int64), ("trees", C.c_int64), ("rounds", C.c_int64), ("dists_executed", C.c_int64),
+                ("tour_found", C.c_int), ("lambda_final", C.c_double), ("seconds", C.c_double), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 _lib = None
@@ -138,6 +147,9 @@ def lib():
         L.tsp_dev_inst_knn_set.argtypes = [vp, C.c_int, ip]
         L.tsp_dev_inst_knn_get.argtypes = [vp, ip, ip]
         L.tsp_dev_nl_opt.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double, C.POINTER(NlOptStats)]
+        lbp = C.POINTER(LbStats)
+        L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
+        L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
         _lib = L
     return _lib
 
@@ -158,6 +170,7 @@ EXPORTED = [
     "tsp_dev_multistart_allreduce_f64", "tsp_dev_multistart_allreduce_f64_group",
     "tsp_dev_or_opt", "tsp_dev_two_opt_or_opt",
     "tsp_dev_inst_knn_build", "tsp_dev_inst_knn_set", "tsp_dev_inst_knn_get", "tsp_dev_nl_opt",
+    "tsp_dev_one_tree", "tsp_dev_held_karp",
 ]
 
 COMM_ID_BYTES = 128
@@ -372,6 +385,43 @@ class Instance:
         if single:
             return rc, succ2[0], float(o[0]), stats[0]
         return rc, succ2, o, stats
+
+    # -- Held-Karp lower bound (extension) ---------------------------------------------------
+    def _pi(self, pi):
+        if pi is None:
+            return None
+        pi = np.array(pi, dtype=np.float64, copy=True, order="C")
+        if pi.shape != (self.n,):
+            raise TspDeviceError("tsp_dev call failed with %d (pi must have n entries)" % E_ARG)
+        return pi
+
+    def one_tree(self, pi=None, want_stats=False):
+        """Minimum 1-tree under the penalties pi (tsp_dev_one_tree) -> (edges [n,2] sorted (lo, hi), deg [n], value W(pi))
+        (+ stats dict with want_stats)"""
+        pi = self._pi(pi)
+        edges = np.zeros((self.n, 2), dtype=np.int32)
+        deg = np.zeros(self.n, dtype=np.int32)
+        val = C.c_double(0)
+        st = LbStats()
+        _check(lib().tsp_dev_one_tree(self._h, _d(pi) if pi is not None else None, _i(edges), _i(deg), C.byref(val), C.byref(st)))
+        if want_stats:
+            return edges, deg, val.value, st.as_dict()
+        return edges, deg, val.value
+
+    def held_karp(self, ub, max_iters=HK_DEFAULT_ITERS, lambda0=HK_DEFAULT_LAMBDA, patience=0, time_limit=-1.0, pi=None):
+        """Subgradient ascent over 1-trees (tsp_dev_held_karp) -> (bound, pi_best [n], stats dict); stats["status"] is OK or
+        TIME_LIMIT_EXCEEDED (the bound is valid either way)."""
+        pi = self._pi(pi)
+        if pi is None:
+            pi = np.zeros(self.n, dtype=np.float64)
+        bound = C.c_double(0)
+        st = LbStats()
+        rc = lib().tsp_dev_held_karp(self._h, float(ub), int(max_iters), float(lambda0), int(patience), float(time_limit), _d(pi),
+                                     C.byref(bound), C.byref(st))
+        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
+        stats = st.as_dict()
+        stats["status"] = rc
+        return bound.value, pi, stats
 
     def perm_cost(self, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

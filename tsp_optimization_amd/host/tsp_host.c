@@ -561,6 +561,29 @@ int HEU_nl_greedy(instance *inst) { (void)HEU_greedy(inst); return alg_nl_opt(in
 int HEU_nl_grasp(instance *inst) { (void)HEU_Grasp(inst); return alg_nl_opt(inst); }
 int HEU_nl_extramileage(instance *inst) { (void)HEU_extramileage(inst); return alg_nl_opt(inst); }
 
+/* ---- Held-Karp lower bound (extension) -------------------------------------------------------------------- */
+
+static __thread tsp_lb_stats t_lb_stats;
+
+void tsp_host_last_lb_stats(tsp_lb_stats *out) {
+    if (out) *out = t_lb_stats;
+}
+
+double tsp_host_lower_bound(instance *inst, double ub, int max_iters, double time_lim) {
+    tsp_lb_stats st;
+    memset(&st, 0, sizeof st);
+    double bound = 0.0;
+    pthread_mutex_lock(&g_lock);
+    tsp_dev_inst *dev = dev_inst_locked(inst);
+    int rc = tsp_dev_held_karp(dev, ub, max_iters > 0 ? max_iters : TSP_HK_DEFAULT_ITERS, TSP_HK_DEFAULT_LAMBDA, 0, time_lim, NULL,
+                               &bound, &st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_held_karp", rc);
+    t_lb_stats = st;
+    if (rc == TIME_LIMIT_EXCEEDED) LOG_I("lower bound time exceeded");
+    return bound;
+}
+
 /* ---- VNS (src/vns.c) ------------------------------------------------------------------------------------- */
 
 /* vns.c:11-100: three random tour positions, segments b..c and d..e swap places, cost recomputed.
