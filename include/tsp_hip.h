@@ -420,6 +420,38 @@ int tsp_dev_one_tree(tsp_dev_inst *inst, const double *pi, int *edges, int *deg,
 int tsp_dev_held_karp(tsp_dev_inst *inst, double ub, int max_iters, double lambda0, int patience, double time_limit_s,
                       double *pi, double *bound, tsp_lb_stats *stats);
 
+/* ---- alpha-nearness candidate lists (extension; Helsgaun's LKH): what the minimum 1-tree says about an edge ------------------
+ * (DESIGN.md 4.13 has the kernels and times.)  d, pi, the edge weight w, the edge order (w, lo, hi) and the minimum 1-tree T(pi)
+ * with special node 0 are those of the Held-Karp section above.  For two nodes i != j:
+ *   {i,j} an edge of T:    alpha(i,j) = 0;
+ *   else i = 0 or j = 0:   alpha(i,j) = w(i,j) - w0, w0 = the weight of the larger (in the edge order) of the two 1-tree edges at
+ *                          node 0;
+ *   else:                  alpha(i,j) = w(i,j) - beta(i,j), beta = the weight of the largest edge (in the edge order) on the path
+ *                          from i to j in the spanning tree of nodes 1 .. n-1.
+ * One fp64 subtraction of two weights, each evaluated as above.  alpha >= 0 without clamping (the tree is minimal under the
+ * order), alpha is symmetric, and it equals W(minimum 1-tree forced to contain {i,j}) - W(T).
+ * Alpha lists: for 1 <= K <= min(TSP_NL_MAX_K, n - 1), nbr[v][0 .. K-1] are the K nodes u != v smallest by
+ * (alpha(v,u), w(v,u), u), in that order; the tree neighbours of v (alpha 0) therefore come first, by weight.
+ * TSP_ALPHA_DEFAULT_K is Helsgaun's default: a convention, not a number measured here.  No floating-point atomics: two runs
+ * return the same bits. */
+#define TSP_ALPHA_DEFAULT_K 5
+typedef struct {
+    int64_t trees;          /* 1-trees built (1)                                                                            */
+    int64_t rounds;         /* Boruvka rounds of the tree                                                                   */
+    int64_t pairs_executed; /* alpha values the scan evaluated (lanes of the launched grid x n columns)                      */
+    double tree_value;      /* W(pi) of the tree                                                                            */
+    double seconds;         /* wall time of the call, host clock                                                            */
+    double device_ms;       /* device time of the call: the tree + the alpha kernels, HIP events on the engine's stream     */
+} tsp_alpha_stats;
+/* Builds T(pi) (pi NULL = zeros), then the alpha lists, and stores them in the handle's list slot: tsp_dev_inst_knn_get returns
+ * them and tsp_dev_nl_opt uses them.  alpha (may be NULL): n x K out, alpha(v, nbr[v][k]).  stats may be NULL.  Bad K, n < 3 or
+ * a penalty that is not finite: TSP_DEV_E_ARG with the reason in tsp_dev_last_error(), and the lists the handle had stay in
+ * place. */
+int tsp_dev_inst_alpha_build(tsp_dev_inst *inst, int K, const double *pi, double *alpha, tsp_alpha_stats *stats);
+/* Whole alpha rows for inspection and thresholds: out[r][u] = alpha(rows[r], u) for r < m (m >= 1), out[r][rows[r]] = 0.  A row
+ * index out of range or a penalty that is not finite: TSP_DEV_E_ARG as above.  The handle's lists are left alone. */
+int tsp_dev_alpha_rows(tsp_dev_inst *inst, const double *pi, int m, const int *rows, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,12 @@ int alg_nl_opt(instance *inst);       /* 2-opt + Or-opt over the lists of the mi
 int HEU_nl_greedy(instance *inst);        /* HEU_greedy + alg_nl_opt       */
 int HEU_nl_grasp(instance *inst);         /* HEU_Grasp + alg_nl_opt        */
 int HEU_nl_extramileage(instance *inst);  /* HEU_extramileage + alg_nl_opt */
+/* Alpha-nearness lists (include/tsp_hip.h, tsp_dev_inst_alpha_build) for alg_nl_opt and HEU_nl_*.  K = 0 (the default): the
+ * nearest-neighbour lists of tsp_host_set_knn, as before.  1 <= K <= TSP_NL_MAX_K: the min(K, n - 1) alpha-nearest nodes, rebuilt
+ * by every call; ascent_iters = 0: from the 1-tree of zero penalties; ascent_iters > 0: from pi_best of
+ * tsp_dev_held_karp(ub = inst->solution.obj_best, ascent_iters, TSP_HK_DEFAULT_LAMBDA, default patience, no time limit, from
+ * zeros).  Anything else (also ascent_iters != 0 with K = 0): TSP_DEV_E_ARG, and the setting stays. */
+int tsp_host_set_alpha(int K, int ascent_iters);
 
 /* ---- Held-Karp lower bound (extension; include/tsp_hip.h, tsp_dev_held_karp).  A library entry point only: no solver_type,
  * no -method row.  Runs the ascent on the instance's device handle from zero penalties with TSP_HK_DEFAULT_LAMBDA and the

@@ -462,15 +462,9 @@ void fill_stats(tsp_lb_stats *st, const HkCtl &c, double t0, float ms) {
 
 void tsp_hk_data_free(void *p) { delete static_cast<HkData *>(p); }
 
-extern "C" {
-
-int tsp_dev_one_tree(tsp_dev_inst *inst, const double *pi, int *edges, int *deg, double *value, tsp_lb_stats *stats) {
-    if (!inst || inst->n < 3 || !pi_finite(pi, inst->n)) {
-        tsp::set_last_error_text("tsp_dev_one_tree: no instance, fewer than 3 nodes or a penalty that is not finite");
-        return TSP_DEV_E_ARG;
-    }
+// The minimum 1-tree of pi (NULL = zeros; the caller has checked it) built and waited for: what alpha.hip works from.
+int tsp_hk_tree(tsp_dev_inst *inst, const double *pi, tsp::HkTree *out, tsp_lb_stats *stats) {
     const double t0 = wall_s();
-    const int n = inst->n;
     TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
     hipStream_t s = inst->ctx->stream;
     HkData *x = nullptr;
@@ -492,6 +486,24 @@ int tsp_dev_one_tree(tsp_dev_inst *inst, const double *pi, int *edges, int *deg,
         tsp::set_last_error_text("tsp_dev_one_tree: the Boruvka rounds did not end in one component");
         return TSP_DEV_E_HIP;
     }
+    out->d_elo = x->d_elo; out->d_ehi = x->d_ehi; out->d_ew = x->d_ew; out->d_pi = x->d_pi;
+    out->W = x->h_ctl->W; out->rounds = x->h_ctl->rounds; out->device_ms = ms;
+    fill_stats(stats, *x->h_ctl, t0, ms);
+    return TSP_OK;
+}
+
+extern "C" {
+
+int tsp_dev_one_tree(tsp_dev_inst *inst, const double *pi, int *edges, int *deg, double *value, tsp_lb_stats *stats) {
+    if (!inst || inst->n < 3 || !pi_finite(pi, inst->n)) {
+        tsp::set_last_error_text("tsp_dev_one_tree: no instance, fewer than 3 nodes or a penalty that is not finite");
+        return TSP_DEV_E_ARG;
+    }
+    const int n = inst->n;
+    tsp::HkTree tr;
+    int rc = tsp_hk_tree(inst, pi, &tr, stats);
+    if (rc) return rc;
+    HkData *x = static_cast<HkData *>(inst->hk_data);
     if (value) *value = x->h_ctl->W;
     if (deg) TSP_HIP_TRY(hipMemcpy(deg, x->d_deg, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     if (edges) {
@@ -509,7 +521,6 @@ int tsp_dev_one_tree(tsp_dev_inst *inst, const double *pi, int *edges, int *deg,
         std::sort(e.begin(), e.end());
         for (int k = 0; k < n; ++k) { edges[2 * k] = (int)(e[k] >> 32); edges[2 * k + 1] = (int)(e[k] & 0xffffffffll); }
     }
-    fill_stats(stats, *x->h_ctl, t0, ms);
     return TSP_OK;
 }
 

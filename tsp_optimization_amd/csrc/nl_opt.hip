@@ -354,6 +354,16 @@ int tsp_grid_tour_cost(tsp_dev_tours *t, double *d_out);                        
 
 void tsp_nl_data_free(void *p) { delete static_cast<NlData *>(p); }
 
+// Lists built elsewhere on the device (alpha.hip) become the handle's lists; nothing queued may still read the old ones.
+int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr) {
+    TSP_HIP_TRY(hipStreamSynchronize(inst->ctx->stream));
+    NlData *x = nl_data(inst);
+    (void)hipFree(x->d_nbr);
+    x->d_nbr = d_nbr;
+    x->K = K;
+    return TSP_OK;
+}
+
 extern "C" {
 
 int tsp_dev_inst_knn_build(tsp_dev_inst *inst, int K, float *kernel_ms) {

@@ -248,6 +248,21 @@ struct DevBuf {
     operator T *() const { return p; }
 };
 }
+// ---- hooks between the extension files ---------------------------------------------------------
+namespace tsp {
+// The 1-tree that held_karp.hip built last, resident on the device: edge slots 0 .. n (slot 0 / n: the smaller / larger edge
+// at node 0; slots 1 .. n-1: the spanning tree's edges, lo = -1 in the one empty slot) and the penalties it was built for.
+struct HkTree {
+    const int *d_elo = nullptr, *d_ehi = nullptr;
+    const double *d_ew = nullptr, *d_pi = nullptr;
+    double W = 0.0;
+    long long rounds = 0;
+    float device_ms = 0.f;
+};
+}
+int tsp_hk_tree(tsp_dev_inst *inst, const double *pi, tsp::HkTree *out, tsp_lb_stats *stats);   // held_karp.hip
+int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr);                                  // nl_opt.hip: takes d_nbr over
+
 // Per-instance scratch for the host-array entry points (not for concurrent use, like every handle): >= bytes, 256-aligned.
 void *tsp_io_pool(tsp_dev_inst *inst, size_t bytes);
 

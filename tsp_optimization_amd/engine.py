@@ -16,6 +16,7 @@ E_ARG = -3
 NL_2OPT, NL_OROPT = 1, 2
 NL_MAX_K, NL_DEFAULT_K = 16, 10
 HK_DEFAULT_ITERS, HK_DEFAULT_LAMBDA = 300, 2.0
+ALPHA_DEFAULT_K = 5
 
 
 class TspDeviceError(RuntimeError):
@@ -58,6 +59,14 @@ class NlOptStats(C.Structure):
 class LbStats(C.Structure):
     _fields_ = [("iterations", C.c_int64), ("trees", C.c_int64), ("rounds", C.c_int64), ("dists_executed", C.c_int64),
                 ("tour_found", C.c_int), ("lambda_final", C.c_double), ("seconds", C.c_double), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AlphaStats(C.Structure):
+    _fields_ = [("trees", C.c_int64), ("rounds", C.c_int64), ("pairs_executed", C.c_int64), ("tree_value", C.c_double),
+                ("seconds", C.c_double), ("device_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -150,6 +159,8 @@ def lib():
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
+        L.tsp_dev_inst_alpha_build.argtypes = [vp, C.c_int, dp, dp, C.POINTER(AlphaStats)]
+        L.tsp_dev_alpha_rows.argtypes = [vp, dp, C.c_int, ip, dp]
         _lib = L
     return _lib
 
@@ -171,6 +182,7 @@ EXPORTED = [
     "tsp_dev_or_opt", "tsp_dev_two_opt_or_opt",
     "tsp_dev_inst_knn_build", "tsp_dev_inst_knn_set", "tsp_dev_inst_knn_get", "tsp_dev_nl_opt",
     "tsp_dev_one_tree", "tsp_dev_held_karp",
+    "tsp_dev_inst_alpha_build", "tsp_dev_alpha_rows",
 ]
 
 COMM_ID_BYTES = 128
@@ -422,6 +434,32 @@ class Instance:
         stats = st.as_dict()
         stats["status"] = rc
         return bound.value, pi, stats
+
+    # -- alpha-nearness candidate lists (extension) ------------------------------------------
+    def alpha_build(self, K=ALPHA_DEFAULT_K, pi=None, want_alpha=False, want_stats=False):
+        """Alpha-nearness lists from the minimum 1-tree of pi, built on the device and kept in the handle
+        (tsp_dev_inst_alpha_build) -> the (n, K) int32 lists (+ the (n, K) alpha values with want_alpha, + a stats dict with
+        want_stats)"""
+        pi = self._pi(pi)
+        K = int(K)
+        alpha = np.zeros((self.n, max(K, 0)), dtype=np.float64) if want_alpha else None
+        st = AlphaStats()
+        _check(lib().tsp_dev_inst_alpha_build(self._h, K, _d(pi) if pi is not None else None,
+                                              _d(alpha) if want_alpha else None, C.byref(st)))
+        out = (self.knn(),)
+        if want_alpha:
+            out += (alpha,)
+        if want_stats:
+            out += (st.as_dict(),)
+        return out[0] if len(out) == 1 else out
+
+    def alpha_rows(self, rows, pi=None):
+        """Whole alpha rows (tsp_dev_alpha_rows) -> (len(rows), n) float64; the rows' own entries are 0"""
+        pi = self._pi(pi)
+        rows = np.ascontiguousarray(np.atleast_1d(rows), dtype=np.int32)
+        out = np.zeros((len(rows), self.n), dtype=np.float64)
+        _check(lib().tsp_dev_alpha_rows(self._h, _d(pi) if pi is not None else None, len(rows), _i(rows), _d(out)))
+        return out
 
     def perm_cost(self, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

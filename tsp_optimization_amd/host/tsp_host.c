@@ -112,6 +112,7 @@ typedef struct {
     double checksum;    /* guards against a reused pointer with different content */
     tsp_dev_inst *dev;
     unsigned long stamp;
+    int lists_alpha;    /* the handle's neighbour lists are alpha lists (alg_nl_opt) */
 } cache_slot;
 
 #define CACHE_SLOTS 8
@@ -139,6 +140,7 @@ static __thread double t_device_ms;
 static __thread tsp_or_opt_stats t_or_stats;   /* the Or-opt phases of the last alg_oropt / alg_2opt_oropt */
 static __thread tsp_nl_opt_stats t_nl_stats;   /* the last alg_nl_opt */
 static int g_knn_k = TSP_NL_DEFAULT_K;         /* list length of alg_nl_opt (tsp_host_set_knn) */
+static int g_alpha_k = 0, g_alpha_iters = 0;   /* alpha lists instead (tsp_host_set_alpha); 0 = nearest-neighbour lists */
 
 static void dev_fail(const char *what, int rc) {
     LOG_E("%s failed with %d %s (this build has no CPU path: an MI355X and libtsp_hip.so are required)", what, rc,
@@ -534,17 +536,50 @@ void tsp_host_last_nl_stats(tsp_nl_opt_stats *out) {
     if (out) *out = t_nl_stats;
 }
 
-/* 2-opt + Or-opt over the lists of the min(K, n - 1) nearest nodes (built when the cached instance has none of that length) */
+int tsp_host_set_alpha(int K, int ascent_iters) {
+    if (K < 0 || K > TSP_NL_MAX_K || ascent_iters < 0 || (K == 0 && ascent_iters != 0)) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_alpha_k = K;
+    g_alpha_iters = ascent_iters;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+/* the alpha lists of the cached handle, from zero penalties or from the ascent's pi_best (ub = the cost of the tour) */
+static int alpha_lists_locked(tsp_dev_inst *dev, int n, double ub) {
+    const int K = g_alpha_k < n - 1 ? g_alpha_k : n - 1;
+    if (g_alpha_iters == 0) return tsp_dev_inst_alpha_build(dev, K, NULL, NULL, NULL);
+    double *pi = (double *)calloc((size_t)n, sizeof *pi);
+    if (!pi) LOG_E("out of memory");
+    double bound = 0.0;
+    int rc = tsp_dev_held_karp(dev, ub, g_alpha_iters, TSP_HK_DEFAULT_LAMBDA, 0, -1.0, pi, &bound, NULL);
+    if (rc == 0) rc = tsp_dev_inst_alpha_build(dev, K, pi, NULL, NULL);
+    free(pi);
+    return rc;
+}
+
+/* 2-opt + Or-opt over the lists of the min(K, n - 1) nearest nodes (built when the cached instance has none of that length or
+ * holds alpha lists), or over alpha lists (tsp_host_set_alpha; rebuilt by every call: they depend on the tour's cost) */
 int alg_nl_opt(instance *inst) {
     tsp_nl_opt_stats st;
     memset(&st, 0, sizeof st);
     double obj = inst->solution.obj_best;
     pthread_mutex_lock(&g_lock);
     tsp_dev_inst *dev = dev_inst_locked(inst);
-    const int want = g_knn_k < inst->num_nodes - 1 ? g_knn_k : inst->num_nodes - 1;
-    int have = 0;
-    int rc = tsp_dev_inst_knn_get(dev, &have, NULL);
-    if (rc == 0 && have != want) rc = tsp_dev_inst_knn_build(dev, want, NULL);
+    cache_slot *slot = NULL;
+    for (int k = 0; k < CACHE_SLOTS; k++)
+        if (g_cache[k].dev == dev) slot = &g_cache[k];
+    int rc;
+    if (g_alpha_k > 0) {
+        rc = alpha_lists_locked(dev, inst->num_nodes, obj);
+        slot->lists_alpha = 1;
+    } else {
+        const int want = g_knn_k < inst->num_nodes - 1 ? g_knn_k : inst->num_nodes - 1;
+        int have = 0;
+        rc = tsp_dev_inst_knn_get(dev, &have, NULL);
+        if (rc == 0 && (have != want || slot->lists_alpha)) rc = tsp_dev_inst_knn_build(dev, want, NULL);
+        if (rc == 0) slot->lists_alpha = 0;
+    }
     if (rc == 0)
         rc = tsp_dev_nl_opt(dev, TSP_NL_2OPT | TSP_NL_OROPT, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)inst->num_nodes, &obj,
                             -1, limit_of(inst), &st);
