@@ -383,6 +383,40 @@ typedef struct {
 int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride,
                    double *obj, int64_t max_moves, double time_limit_s, tsp_nl_opt_stats *stats);
 
+/* ---- candidate-list 3-opt (extension): the general segment move as a third kind of the list descent -------------------------
+ * (The reference declares HEU_3opt, include/heuristics.h:51-56, and never defines it; Or-opt above is the case of a segment of
+ * at most 3 nodes.  DESIGN.md 4.14 has the kernels.)
+ * Labels.  Three distinct tour edges are removed, named by their tails a, b, c with heads a1 = succ a, b1 = succ b, c1 = succ c:
+ * a is the tail with the lowest node id, b and c follow a in tour order.  Segments S1 = a1 .. b, S2 = b1 .. c, S3 = c1 .. a; a
+ * segment may be one node.
+ * Types.  The four pure reconnections, new edges (e1, e2, e3) and the new tour from a (S3 always keeps its direction):
+ *     0: (a,b1) (c,a1) (b,c1)   a, S2, S1, c1 ..                     1: (a,b) (a1,c) (b1,c1)   a, S1 reversed, S2 reversed, c1 ..
+ *     2: (a,c) (b1,a1) (b,c1)   a, S2 reversed, S1, c1 ..            3: (a,b1) (c,b) (a1,c1)   a, S2, S1 reversed, c1 ..
+ * (a, b, c, type) is a move iff none of its three new edges is an edge of the current tour (that leaves out the reconnections
+ * that are 2-opt moves because two removed edges are adjacent): 2n(n-2)(n-4)/3 moves per tour, none for n < 5.  A move with a
+ * segment of one node has the same new edges as a second type (the one that reverses that segment); both are moves.
+ *     delta = ((d(e1) + d(e2)) + d(e3)) - ((d(a,a1) + d(b,b1)) + d(c,c1)), every d with the lower node id first, evaluated in
+ * exactly this order;  key = ((a*n + b)*n + c)*4 + type.
+ * List neighbourhood.  A move is in it iff it has a removed edge (p, q = succ p) and two different new edges {p,u} and {q,w} with
+ * u in N(p) and w in N(q): the lists as stored, directed, without the closure u ~ v of the two kinds above (LKH's step
+ * t2 -> t3, t4 -> t5 without the gain rule).  With K = n - 1 every move is in it.
+ * Apply.  The new tour of the table in forward orientation; order/pos by at most three reversals of forward paths.
+ * Decision.  As above over the enabled kinds: smallest delta < 0, ties -> lower kind (2-opt 0, Or-opt 1, 3-opt 2), then lower
+ * key.  The key takes 4n^3 below the kind bits: with TSP_NL_3OPT enabled, n > 2^20 is TSP_DEV_E_ARG. */
+enum { TSP_NL_3OPT = 4 }; /* kinds mask of tsp_dev_nl_3opt, beside TSP_NL_2OPT and TSP_NL_OROPT */
+typedef struct {
+    int64_t decisions, moves, moves_2opt, moves_oropt, moves_by_len[3], moves_reversed, reversed, deltas_executed;
+    double seconds, device_ms; /* the fields of tsp_nl_opt_stats, in its layout; moves and deltas_executed count all kinds */
+    int64_t moves_3opt;        /* applied moves of kind 2                                                                  */
+    int64_t moves_by_type[4];  /* ... of types 0 .. 3                                                                      */
+} tsp_nl3_opt_stats;
+/* tsp_dev_nl_opt with the third kind: kinds is any non-empty subset of TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT (tsp_dev_nl_opt
+ * keeps refusing TSP_NL_3OPT); the 3-opt kind has no move for n < 5 and is then left out.  Lists, the default lists, obj,
+ * max_moves, time_limit_s and the status as there.  With kinds inside TSP_NL_2OPT | TSP_NL_OROPT it follows tsp_dev_nl_opt move
+ * for move. */
+int tsp_dev_nl_3opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride,
+                    double *obj, int64_t max_moves, double time_limit_s, tsp_nl3_opt_stats *stats);
+
 /* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
  * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
  * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.

@@ -144,6 +144,11 @@ int HEU_nl_extramileage(instance *inst);  /* HEU_extramileage + alg_nl_opt */
  * tsp_dev_held_karp(ub = inst->solution.obj_best, ascent_iters, TSP_HK_DEFAULT_LAMBDA, default patience, no time limit, from
  * zeros).  Anything else (also ascent_iters != 0 with K = 0): TSP_DEV_E_ARG, and the setting stays. */
 int tsp_host_set_alpha(int K, int ascent_iters);
+/* The list descent with the 3-opt kind (include/tsp_hip.h, tsp_dev_nl_3opt).  Library entry points only, as above. */
+int alg_3opt(instance *inst);         /* 2-opt + Or-opt + 3-opt on inst->solution over the lists tsp_host_set_knn /
+                                         tsp_host_set_alpha select; obj_best receives the recomputed cost                    */
+/* The library still exports no HEU_3opt, the name the reference declares and never defines (tests/test_cpu_or_opt.py holds
+ * that): HEU_greedy followed by alg_3opt is that heuristic. */
 
 /* ---- Held-Karp lower bound (extension; include/tsp_hip.h, tsp_dev_held_karp).  A library entry point only: no solver_type,
  * no -method row.  Runs the ascent on the instance's device handle from zero penalties with TSP_HK_DEFAULT_LAMBDA and the
@@ -256,6 +261,8 @@ void tsp_host_last_stats(long long *sweeps, long long *evals, long long *moves, 
 void tsp_host_last_or_stats(tsp_or_opt_stats *out);
 /* Counters of the last alg_nl_opt call of this thread. */
 void tsp_host_last_nl_stats(tsp_nl_opt_stats *out);
+/* Counters of the last alg_3opt call of this thread. */
+void tsp_host_last_nl3_stats(tsp_nl3_opt_stats *out);
 /* Counters of the last tsp_host_lower_bound call of this thread. */
 void tsp_host_last_lb_stats(tsp_lb_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */

@@ -9,7 +9,7 @@
 // Every distance goes through dsym(): the lower node id first, so that a move reached through several (v, u, role)
 // combinations has the same delta bits each time.  A 2-opt move always reverses the forward path i1 .. j in place, so that
 // order/pos keep the orientation of succ and the Or-opt shift works unchanged.
-#include "or_opt_shift.hpp"
+#include "nl_common.hpp"
 
 #include <time.h>
 #include <algorithm>
@@ -23,30 +23,8 @@ namespace {
 constexpr int kK = TSP_NL_MAX_K;     // k_knn_scan keeps this many per row whatever K is asked for: the K best are a prefix
 constexpr int kKnnChunks = 16;       // k_knn_scan: most column chunks per row
 constexpr int kKnnWaves = 4096;      // ... chosen so that about this many waves exist
-constexpr int kPickThreads = 1024;
-constexpr u64 kKindBit = 1ull << 62; // decision key: kind in bit 62, the kind's own key below (6 n^2 < 2^62)
-
-struct alignas(16) NlBest {
-    double d;
-    u64 k;
-};
-
-struct alignas(16) NlState {
-    long long max_moves;   // < 0: unlimited
-    long long decisions, moves, moves_2opt, moves_oropt, moves_len[3], moves_rev, reversed, deltas;
-    int done, pad;
-};
-
-__device__ __forceinline__ void offer(double delta, u64 key, double &bd, u64 &bk) {
-    if (delta < 0.0 && better(delta, key, bd, bk)) { bd = delta; bk = key; }
-}
-
-// calc_dist of two nodes, the lower id first
-template <int WT, bool INT>
-__device__ __forceinline__ double dsym(const double2 *coord, int u, int v) {
-    const double2 a = coord[min(u, v)], b = coord[max(u, v)];
-    return dist_xy<WT, INT>(a.x, a.y, b.x, b.y);
-}
+constexpr int kPickThreads = kNlPickThreads;
+constexpr u64 kKindBit = kNlOrBit;   // decision key: kind in bit 62, the kind's own key below (nl_common.hpp)
 
 // (d, id) into the sorted list; d == a held distance goes behind it (the callers offer equal distances in id order)
 __device__ __forceinline__ void knn_insert(double (&kd)[kK], int (&ki)[kK], double d, int id) {
@@ -153,7 +131,7 @@ struct NlView {
         const double dij = known == 0 ? dk : d(x, y), d11 = known == 1 ? dk : d(i1, j1);
         const double delta = ((dij + d11) - E[x]) - E[y];
         cnt += 1;
-        offer(delta, (u64)x * (u64)n + (u64)y, bd, bk);
+        nl_offer(delta, (u64)x * (u64)n + (u64)y, bd, bk);
     }
 
     // Or-opt move (f, L, a, o); `known` says which attaching edge has the length dk: 0 = the one at a, 1 = the one at b
@@ -167,7 +145,7 @@ struct NlView {
         const double d2 = known == 1 ? dk : (o ? d(f, bb) : d(l, bb));
         const double delta = ((d1 + d2) - E[a]) - rem[(size_t)(L - 1) * n + f];
         cnt += 1;
-        offer(delta, kKindBit | (u64)((((long long)f * 3 + (L - 1)) * n + a) * 2 + o), bd, bk);
+        nl_offer(delta, kKindBit | (u64)((((long long)f * 3 + (L - 1)) * n + a) * 2 + o), bd, bk);
     }
 
     // the ten Or-opt moves that attach the segment with the edge x -> y (x ahead of y in the new tour)
@@ -264,12 +242,7 @@ __global__ __launch_bounds__(kPickThreads) void k_nl_pick_apply(int *__restrict_
             S.moves += 1; S.moves_2opt += 1; S.reversed += len - 1;   // the successors rewritten: all of the path but i1's
             if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
         }
-        for (int q = tid; q < len / 2; q += kPickThreads) {
-            const int pa = or_wrap(pi + 1 + q, n), pb = or_wrap(pi + len - q, n);
-            const int va = order[pa], vb = order[pb];
-            order[pa] = vb; pos[vb] = pa;
-            order[pb] = va; pos[va] = pb;
-        }
+        nl_reverse_path<kPickThreads>(order, pos, n, or_wrap(pi + 1, n), len);
         return;
     }
     const u64 key = bk & (kKindBit - 1);
@@ -289,29 +262,6 @@ __global__ __launch_bounds__(kPickThreads) void k_nl_pick_apply(int *__restrict_
     or_shift_apply<kPickThreads>(order, pos, n, i, ja, L, o, x);
 }
 
-double wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
-// Lists and scratch of one instance.
-struct NlData {
-    int K = 0;                 // 0: no lists
-    int *d_nbr = nullptr;      // n x K
-    int B = 0, nparts = 0, parts_K = 0;
-    NlState *d_st = nullptr;
-    NlState *h_st = nullptr;   // pinned
-    double *d_E = nullptr, *d_rem = nullptr, *d_cost = nullptr;
-    NlBest *d_part = nullptr;
-    void free_scratch() {
-        (void)hipFree(d_st); (void)hipHostFree(h_st); (void)hipFree(d_E); (void)hipFree(d_rem); (void)hipFree(d_cost);
-        (void)hipFree(d_part);
-        d_st = nullptr; h_st = nullptr; d_E = d_rem = d_cost = nullptr; d_part = nullptr; B = 0;
-    }
-    ~NlData() { free_scratch(); (void)hipFree(d_nbr); }
-};
-
 NlData *nl_data(tsp_dev_inst *inst) {
     if (!inst->nl_data) inst->nl_data = new NlData();
     return static_cast<NlData *>(inst->nl_data);
@@ -319,7 +269,7 @@ NlData *nl_data(tsp_dev_inst *inst) {
 
 int scratch_alloc(NlData *x, int B, int n, int K) {
     x->free_scratch();
-    x->nparts = (int)(((long long)n * K + 255) / 256);
+    x->nparts = (int)(((long long)n * K + 255) / 256);   // of k_nl_scan and of k_nl3_scan: both have one lane per list entry
     x->parts_K = K;
     const size_t Bn = (size_t)B * n;
     TSP_HIP_TRY(hipMalloc(&x->d_st, sizeof(NlState) * B));
@@ -327,23 +277,41 @@ int scratch_alloc(NlData *x, int B, int n, int K) {
     TSP_HIP_TRY(hipMalloc(&x->d_E, sizeof(double) * Bn));
     TSP_HIP_TRY(hipMalloc(&x->d_rem, sizeof(double) * 3 * Bn));
     TSP_HIP_TRY(hipMalloc(&x->d_cost, sizeof(double) * B));
-    TSP_HIP_TRY(hipMalloc(&x->d_part, sizeof(NlBest) * (size_t)B * x->nparts));
+    TSP_HIP_TRY(hipMalloc(&x->d_part, sizeof(NlBest) * 2 * (size_t)B * x->nparts));
     x->B = B;
     return TSP_OK;
 }
 
 void launch_decision(tsp_dev_tours *t, NlData *x, int kinds) {
+    tsp_nl_launch_scan(t, x, kinds);
+    hipLaunchKernelGGL(k_nl_pick_apply, dim3(t->B), dim3(kPickThreads), 0, t->inst->ctx->stream, t->d_order, t->d_pos, x->d_st,
+                       t->n, x->nparts, x->d_part);
+}
+
+}  // namespace
+
+double tsp_nl_wall_s() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+void tsp_nl_launch_scan(tsp_dev_tours *t, NlData *x, int kinds) {
     tsp_dev_inst *inst = t->inst;
     hipStream_t s = inst->ctx->stream;
     const int n = t->n, B = t->B;
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         hipLaunchKernelGGL((k_nl_prep<WTC, INTC>), dim3((n + 255) / 256, B), dim3(256), 0, s, inst->d_coord, t->d_order, x->d_st, n,
                            x->d_E, x->d_rem);
-        hipLaunchKernelGGL((k_nl_scan<WTC, INTC>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
-                           x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part);
+        if (kinds & (TSP_NL_2OPT | TSP_NL_OROPT))
+            hipLaunchKernelGGL((k_nl_scan<WTC, INTC>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
+                               x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part);
     });
-    hipLaunchKernelGGL(k_nl_pick_apply, dim3(B), dim3(kPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts, x->d_part);
 }
+
+namespace {
+
+double wall_s() { return tsp_nl_wall_s(); }
 
 bool bad_k(const tsp_dev_inst *inst, int K) { return K < 1 || K > TSP_NL_MAX_K || K > inst->n - 1; }
 
@@ -429,13 +397,14 @@ int tsp_dev_inst_knn_get(tsp_dev_inst *inst, int *K, int *nbr) {
     return TSP_OK;
 }
 
-int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
-                   int64_t max_moves, double time_limit_s, tsp_nl_opt_stats *stats) {
-    if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
-    if (kinds < 1 || kinds > (TSP_NL_2OPT | TSP_NL_OROPT)) return TSP_DEV_E_ARG;
+
+}  // extern "C"
+
+int tsp_nl_descend(tsp_dev_inst *inst, int kinds, tsp_nl_decision_fn decision, int B, int *succ, int succ_stride,
+                   int64_t tour_stride, double *obj, int64_t max_moves, double time_limit_s, NlData **xo, double *t0o, float *ms) {
     const int n = inst->n;
-    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
     const double t0 = wall_s();
+    *t0o = t0;
     TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
     hipStream_t s = inst->ctx->stream;
     bool owned = false;
@@ -446,6 +415,7 @@ int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_str
     rc = tsp_dev_tours_upload(t, succ, succ_stride, tour_stride, obj);   // checks every successor list
     if (rc) return rc;
     NlData *x = nl_data(inst);
+    *xo = x;
     if (x->K == 0) {
         rc = tsp_dev_inst_knn_build(inst, std::min(TSP_NL_DEFAULT_K, n - 1), nullptr);
         if (rc) return rc;
@@ -454,9 +424,6 @@ int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_str
         rc = scratch_alloc(x, B, n, x->K);
         if (rc) { x->free_scratch(); return rc; }
     }
-    // a kind without any move at this size is left out: 2-opt needs four nodes, Or-opt five
-    if (n < 4) kinds &= ~TSP_NL_2OPT;
-    if (n < 5) kinds &= ~TSP_NL_OROPT;
     const bool trivial = kinds == 0 || max_moves == 0;
     for (int b = 0; b < B; ++b) {
         NlState z;
@@ -471,7 +438,7 @@ int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_str
     int status = TSP_OK;
     if (!trivial) {
         double tq = wall_s();
-        launch_decision(t, x, kinds);
+        decision(t, x, kinds);
         int batch = 4, queued = 1;
         for (;;) {
             TSP_HIP_TRY(hipMemcpyAsync(x->h_st, x->d_st, sizeof(NlState) * B, hipMemcpyDeviceToHost, s));
@@ -490,7 +457,7 @@ int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_str
             }
             // decisions queued back to back; those behind a tour's last one return at once (done)
             tq = now;
-            for (int k = 0; k < next; ++k) launch_decision(t, x, kinds);
+            for (int k = 0; k < next; ++k) decision(t, x, kinds);
             queued = next;
             batch = std::min(batch * 2, 256);
         }
@@ -502,24 +469,42 @@ int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_str
     TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
     TSP_HIP_TRY(hipEventSynchronize(inst->ev1));
     TSP_HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    TSP_HIP_TRY(hipEventElapsedTime(&ms, inst->ev0, inst->ev1));
+    *ms = 0.f;
+    TSP_HIP_TRY(hipEventElapsedTime(ms, inst->ev0, inst->ev1));
     std::vector<double> cost((size_t)B);
     TSP_HIP_TRY(hipMemcpyAsync(cost.data(), x->d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, s));
     TSP_HIP_TRY(hipMemcpyAsync(x->h_st, x->d_st, sizeof(NlState) * B, hipMemcpyDeviceToHost, s));
     rc = tsp_dev_tours_download(t, succ, succ_stride, tour_stride, nullptr, nullptr);   // (synchronises the stream)
     if (rc) return rc;
-    for (int b = 0; b < B; ++b) {
-        obj[b] = cost[b];
-        if (stats) {
-            const NlState &z = x->h_st[b];
-            tsp_nl_opt_stats &o = stats[b];
-            memset(&o, 0, sizeof o);
-            o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
-            for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
-            o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
-            o.seconds = wall_s() - t0; o.device_ms = ms;
-        }
+    for (int b = 0; b < B; ++b) obj[b] = cost[b];
+    return status;
+}
+
+extern "C" {
+
+int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                   int64_t max_moves, double time_limit_s, tsp_nl_opt_stats *stats) {
+    if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
+    if (kinds < 1 || kinds > (TSP_NL_2OPT | TSP_NL_OROPT)) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
+    // a kind without any move at this size is left out: 2-opt needs four nodes, Or-opt five
+    if (n < 4) kinds &= ~TSP_NL_2OPT;
+    if (n < 5) kinds &= ~TSP_NL_OROPT;
+    NlData *x = nullptr;
+    double t0 = 0.0;
+    float ms = 0.f;
+    const int status = tsp_nl_descend(inst, kinds, launch_decision, B, succ, succ_stride, tour_stride, obj, max_moves, time_limit_s,
+                                      &x, &t0, &ms);
+    if (status < 0 || (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED)) return status;
+    for (int b = 0; b < B && stats; ++b) {
+        const NlState &z = x->h_st[b];
+        tsp_nl_opt_stats &o = stats[b];
+        memset(&o, 0, sizeof o);
+        o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
+        for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
+        o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
+        o.seconds = wall_s() - t0; o.device_ms = ms;
     }
     return status;
 }

@@ -14,6 +14,7 @@ ENGINE_AUTO, ENGINE_GRID, ENGINE_LDS, ENGINE_CLUSTER = 0, 1, 2, 3
 OK, WRONG_STARTING_NODE, TIME_LIMIT_EXCEEDED = 0, 1, 2
 E_ARG = -3
 NL_2OPT, NL_OROPT = 1, 2
+NL_3OPT = 4   # tsp_dev_nl_3opt only
 NL_MAX_K, NL_DEFAULT_K = 16, 10
 HK_DEFAULT_ITERS, HK_DEFAULT_LAMBDA = 300, 2.0
 ALPHA_DEFAULT_K = 5
@@ -53,6 +54,16 @@ class NlOptStats(C.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["moves_by_len"] = list(self.moves_by_len)
+        return d
+
+
+class Nl3OptStats(C.Structure):
+    _fields_ = NlOptStats._fields_ + [("moves_3opt", C.c_int64), ("moves_by_type", C.c_int64 * 4)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["moves_by_len"] = list(self.moves_by_len)
+        d["moves_by_type"] = list(self.moves_by_type)
         return d
 
 
@@ -156,6 +167,7 @@ def lib():
         L.tsp_dev_inst_knn_set.argtypes = [vp, C.c_int, ip]
         L.tsp_dev_inst_knn_get.argtypes = [vp, ip, ip]
         L.tsp_dev_nl_opt.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double, C.POINTER(NlOptStats)]
+        L.tsp_dev_nl_3opt.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double, C.POINTER(Nl3OptStats)]
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
@@ -180,7 +192,7 @@ EXPORTED = [
     "tsp_dev_multistart_allreduce_group", "tsp_dev_multistart_bcast_tour_group",
     "tsp_dev_multistart_allreduce_f64", "tsp_dev_multistart_allreduce_f64_group",
     "tsp_dev_or_opt", "tsp_dev_two_opt_or_opt",
-    "tsp_dev_inst_knn_build", "tsp_dev_inst_knn_set", "tsp_dev_inst_knn_get", "tsp_dev_nl_opt",
+    "tsp_dev_inst_knn_build", "tsp_dev_inst_knn_set", "tsp_dev_inst_knn_get", "tsp_dev_nl_opt", "tsp_dev_nl_3opt",
     "tsp_dev_one_tree", "tsp_dev_held_karp",
     "tsp_dev_inst_alpha_build", "tsp_dev_alpha_rows",
 ]
@@ -392,6 +404,21 @@ class Instance:
         o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
         st = (NlOptStats * B)()
         rc = lib().tsp_dev_nl_opt(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
+        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
+        stats = [s.as_dict() for s in st]
+        if single:
+            return rc, succ2[0], float(o[0]), stats[0]
+        return rc, succ2, o, stats
+
+    def nl_3opt(self, succ, obj=None, kinds=NL_2OPT | NL_OROPT | NL_3OPT, max_moves=-1, time_limit=-1.0):
+        """The list descent with the 3-opt kind (tsp_dev_nl_3opt): kinds is any non-empty subset of NL_2OPT | NL_OROPT | NL_3OPT.
+        succ [n] or [B,n].  -> (status, succ', obj' (recomputed cost), stats dict(s)) as nl_opt, the stats with moves_3opt and
+        moves_by_type"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
+        st = (Nl3OptStats * B)()
+        rc = lib().tsp_dev_nl_3opt(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
         _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
         stats = [s.as_dict() for s in st]
         if single:

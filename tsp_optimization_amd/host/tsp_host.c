@@ -139,6 +139,7 @@ static __thread double t_driver_loop_s;   /* seconds the last tsp_host_tabu / ts
 static __thread double t_device_ms;
 static __thread tsp_or_opt_stats t_or_stats;   /* the Or-opt phases of the last alg_oropt / alg_2opt_oropt */
 static __thread tsp_nl_opt_stats t_nl_stats;   /* the last alg_nl_opt */
+static __thread tsp_nl3_opt_stats t_nl3_stats; /* the last alg_3opt */
 static int g_knn_k = TSP_NL_DEFAULT_K;         /* list length of alg_nl_opt (tsp_host_set_knn) */
 static int g_alpha_k = 0, g_alpha_iters = 0;   /* alpha lists instead (tsp_host_set_alpha); 0 = nearest-neighbour lists */
 
@@ -558,14 +559,13 @@ static int alpha_lists_locked(tsp_dev_inst *dev, int n, double ub) {
     return rc;
 }
 
-/* 2-opt + Or-opt over the lists of the min(K, n - 1) nearest nodes (built when the cached instance has none of that length or
- * holds alpha lists), or over alpha lists (tsp_host_set_alpha; rebuilt by every call: they depend on the tour's cost) */
-int alg_nl_opt(instance *inst) {
-    tsp_nl_opt_stats st;
-    memset(&st, 0, sizeof st);
-    double obj = inst->solution.obj_best;
-    pthread_mutex_lock(&g_lock);
-    tsp_dev_inst *dev = dev_inst_locked(inst);
+void tsp_host_last_nl3_stats(tsp_nl3_opt_stats *out) {
+    if (out) *out = t_nl3_stats;
+}
+
+/* the lists of a list descent in the cached handle: the min(K, n - 1) nearest nodes (built when the handle has none of that
+ * length or holds alpha lists), or alpha lists (tsp_host_set_alpha; rebuilt by every call: they depend on the tour's cost) */
+static int lists_locked(instance *inst, tsp_dev_inst *dev, double obj) {
     cache_slot *slot = NULL;
     for (int k = 0; k < CACHE_SLOTS; k++)
         if (g_cache[k].dev == dev) slot = &g_cache[k];
@@ -580,6 +580,36 @@ int alg_nl_opt(instance *inst) {
         if (rc == 0 && (have != want || slot->lists_alpha)) rc = tsp_dev_inst_knn_build(dev, want, NULL);
         if (rc == 0) slot->lists_alpha = 0;
     }
+    return rc;
+}
+
+/* 2-opt + Or-opt + 3-opt over the lists alg_nl_opt would use */
+int alg_3opt(instance *inst) {
+    tsp_nl3_opt_stats st;
+    memset(&st, 0, sizeof st);
+    double obj = inst->solution.obj_best;
+    pthread_mutex_lock(&g_lock);
+    tsp_dev_inst *dev = dev_inst_locked(inst);
+    int rc = lists_locked(inst, dev, obj);
+    if (rc == 0)
+        rc = tsp_dev_nl_3opt(dev, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, 1, &inst->solution.edges[0].j, 2,
+                             2 * (int64_t)inst->num_nodes, &obj, -1, limit_of(inst), &st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_nl_3opt", rc);
+    inst->solution.obj_best = obj;
+    t_nl3_stats = st;
+    if (rc == TIME_LIMIT_EXCEEDED) LOG_I("3-opt heuristics time exceeded");
+    return rc;
+}
+
+/* 2-opt + Or-opt over the lists of lists_locked */
+int alg_nl_opt(instance *inst) {
+    tsp_nl_opt_stats st;
+    memset(&st, 0, sizeof st);
+    double obj = inst->solution.obj_best;
+    pthread_mutex_lock(&g_lock);
+    tsp_dev_inst *dev = dev_inst_locked(inst);
+    int rc = lists_locked(inst, dev, obj);
     if (rc == 0)
         rc = tsp_dev_nl_opt(dev, TSP_NL_2OPT | TSP_NL_OROPT, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)inst->num_nodes, &obj,
                             -1, limit_of(inst), &st);
