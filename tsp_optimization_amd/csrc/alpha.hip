@@ -19,7 +19,6 @@
 #include "tsp_internal.hpp"
 
 #include <math.h>
-#include <time.h>
 #include <algorithm>
 #include <numeric>
 
@@ -220,12 +219,6 @@ __global__ __launch_bounds__(256) void k_alpha_merge(int n, int Cc, int K, const
         if (s < K) { nbr[(size_t)v * K + s] = ki[s]; alpha[(size_t)v * K + s] = ka[s]; }
 }
 
-double wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 bool pi_finite(const double *pi, int n) {
     if (pi)
         for (int v = 0; v < n; ++v)
@@ -316,7 +309,7 @@ int prepare(tsp_dev_inst *inst, const double *pi, AlPrep *P) {
     TSP_HIP_TRY(P->ids.alloc((size_t)n));
     TSP_HIP_TRY(hipMemcpy(P->ids.p, ids.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     TSP_HIP_TRY(hipMemcpy(P->h.p, h.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    if (int e = tsp_inst_events(inst)) return e;
     TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
     hipLaunchKernelGGL(k_alpha_cols, dim3((n + 255) / 256), dim3(256), 0, s, inst->d_coord, tr.d_pi, P->ids.p, n, P->col.p);
     hipLaunchKernelGGL(k_alpha_bounds, dim3(P->Cc), dim3(256), 0, s, P->h.p, n, P->CH, P->T.p);

@@ -5,7 +5,6 @@
 #include <mutex>
 
 #include <algorithm>
-#include <time.h>
 
 #pragma clang fp contract(off)
 
@@ -93,12 +92,6 @@ unsigned hilbert_rank16(unsigned x, unsigned y) {
     }
     return d;
 }
-double wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 template <int WT, bool INT>
 __global__ void k_dist_pairs(const double2 *__restrict__ coord, const int *__restrict__ pi,
                              const int *__restrict__ pj, int count, double *__restrict__ out) {
@@ -502,7 +495,7 @@ int tsp_dev_two_opt(tsp_dev_inst *inst, int mode, int engine, int B, int *succ, 
         engine = cluster ? TSP_ENGINE_CLUSTER : (lds ? TSP_ENGINE_LDS : TSP_ENGINE_GRID);
         cluster_C = std::max(1, C);
     }
-    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    if (int e = tsp_inst_events(inst)) return e;
     hipEvent_t e0 = inst->ev0, e1 = inst->ev1;
     TSP_HIP_TRY(hipEventRecord(e0, s));
     int done = 0;
@@ -567,7 +560,7 @@ int tsp_dev_tours_run_engine(tsp_dev_tours *t, int mode, int engine, int64_t max
     TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
     if (all_done) *all_done = 0;
     // device time of the run, HIP events on the engine's stream (reported as stats.device_ms by the next download)
-    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    if (int e = tsp_inst_events(inst)) return e;
     TSP_HIP_TRY(hipEventRecord(inst->ev0, inst->ctx->stream));
     const int status = run_engine_untimed(t, mode, engine, max_steps, time_limit_s, all_done);
     if (status < 0) return status;

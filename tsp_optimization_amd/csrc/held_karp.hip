@@ -18,7 +18,6 @@
 #include "tsp_internal.hpp"
 
 #include <math.h>
-#include <time.h>
 #include <algorithm>
 
 #pragma clang fp contract(off)
@@ -337,12 +336,6 @@ __global__ __launch_bounds__(kFinThreads) void k_hk_finish(const HkCol *__restri
     }
 }
 
-double wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 // Scratch of one instance.
 struct HkData {
     int n = 0, Cc = 0, CH = 0, Rmax = 0;
@@ -474,7 +467,7 @@ int tsp_hk_tree(tsp_dev_inst *inst, const double *pi, tsp::HkTree *out, tsp_lb_s
     memset(&c0, 0, sizeof c0);
     rc = hk_begin(inst, x, pi, c0);
     if (rc) return rc;
-    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    if (int e = tsp_inst_events(inst)) return e;
     TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
     queue_tree(inst, x, x->Rmax, 0);
     TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
@@ -545,7 +538,7 @@ int tsp_dev_held_karp(tsp_dev_inst *inst, double ub, int max_iters, double lambd
     c0.patience = patience > 0 ? patience : std::max(10, n / 20);
     rc = hk_begin(inst, x, pi, c0);
     if (rc) return rc;
-    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    if (int e = tsp_inst_events(inst)) return e;
     TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
     int status = TSP_OK, R = x->Rmax, batch = 1;
     long long left = max_iters;

@@ -2,14 +2,14 @@
 //
 // Decision k_nl_prep and k_nl_scan of nl_opt.hip (edge lengths; the 2-opt and Or-opt candidates) -> k_nl3_scan (one lane = one
 //          list entry (p, u): with q = succ p it walks w over the list of q, and for each (u, w) the <= 4 choices of the removed
-//          edges at u and at w; one (delta, key) per workgroup) -> k_nl3_pick_apply (the candidates of both scans, then the move
-//          of whichever kind on order/pos; one workgroup per tour).
+//          edges at u and at w; one (delta, key) per workgroup) -> k_nl_pick_apply of nl_opt.hip (the candidates of both scans,
+//          then the move of whichever kind on order/pos; one workgroup per tour).
 // A lane works on the six ends of the three removed edges ("slots": tail and head of a, b, c) and not on node ids, because a
 // segment of one node puts two slots on one node.  Such a move has the same new edges as a second type with the segment
 // reversed, and both are moves of the neighbourhood, so the lane offers both, each summed in its own order.
 #include "nl_common.hpp"
 
-#include <algorithm>
+#include <cstddef>
 
 #pragma clang fp contract(off)
 
@@ -17,18 +17,11 @@ using namespace tsp;
 
 namespace {
 
-constexpr int kMaxN3 = 1 << 20;   // 4 n^3 must stay below the kind bits of the decision key
-
 // two positions that hold different nodes which are not tour neighbours
 __device__ __forceinline__ bool apart(int px, int py, int n) {
     int g = px - py;
     if (g < 0) g += n;
     return g != 0 && g != 1 && g != n - 1;
-}
-
-__device__ __forceinline__ int ahead(int px, int from, int n) {   // px - from mod n
-    const int g = px - from;
-    return g < 0 ? g + n : g;
 }
 
 __device__ __forceinline__ unsigned pair_slots(int s, int t) { return ((unsigned)t << (3 * s)) | ((unsigned)s << (3 * t)); }
@@ -114,7 +107,7 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
                         const double e3 = same_edge(x3, y3, p, u) ? dk : (same_edge(x3, y3, q, w) ? dqw : d3);
                         const double delta = ((e1 + e2) + e3) - old;
                         cnt += 1;
-                        nl_offer(delta, kNl3Bit | (key0 + (u64)Tq), bd, bk);
+                        offer(delta, kNl3Bit | (key0 + (u64)Tq), bd, bk);
                     }
                 }
             }
@@ -127,143 +120,29 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
     if ((threadIdx.x & 63) == 0 && c64) atomicAdd((unsigned long long *)&st[bt].deltas, c64);
 }
 
-// Decision over the candidates of k_nl_scan (parts2) and k_nl3_scan (parts3; either may be NULL: no kind of it is enabled), then
-// the move.  One workgroup per tour.
-__global__ __launch_bounds__(kNlPickThreads) void k_nl3_pick_apply(int *__restrict__ orders, int *__restrict__ poss,
-                                                                   NlState *__restrict__ st, int n, int nparts,
-                                                                   const NlBest *__restrict__ parts2,
-                                                                   const NlBest *__restrict__ parts3) {
-    constexpr int NT = kNlPickThreads;
-    const int bt = blockIdx.x;
-    NlState &S = st[bt];
-    if (S.done) return;
-    __shared__ double sd[NT / 64];
-    __shared__ u64 sk[NT / 64];
-    const int tid = threadIdx.x;
-    if (S.max_moves >= 0 && S.moves >= S.max_moves) {
-        if (tid == 0) S.done = 1;
-        return;
-    }
-    double bd = INFINITY; u64 bk = kNoKey;
-    for (int h = 0; h < 2; ++h) {
-        const NlBest *part = h ? parts3 : parts2;
-        if (!part) continue;
-        part += (size_t)bt * nparts;
-        for (int r = tid; r < nparts; r += NT) {
-            const NlBest q = part[r];
-            if (q.k != kNoKey && better(q.d, q.k, bd, bk)) { bd = q.d; bk = q.k; }
-        }
-    }
-    block_argmin<true>(bd, bk, sd, sk);
-    __syncthreads();
-    if (tid == 0) { S.decisions += 1; if (bk == kNoKey) S.done = 1; }
-    if (bk == kNoKey) return;
-    int *order = orders + (size_t)bt * n, *pos = poss + (size_t)bt * n;
-    if (bk & kNl3Bit) {
-        const u64 key = bk & (kNl3Bit - 1);
-        const int T = (int)(key & 3);
-        const u64 abc = key >> 2;
-        const int c = (int)(abc % (u64)n), b = (int)((abc / (u64)n) % (u64)n), a = (int)(abc / ((u64)n * (u64)n));
-        const int pa = pos[a];
-        const int s1 = ahead(pos[b], pa, n), s2 = ahead(pos[c], pa, n) - s1;
-        const int at1 = or_wrap(pa + 1, n), at2 = or_wrap(at1 + s1, n);   // where S1 = a1 .. b and S2 = b1 .. c start
-        __syncthreads();   // every thread has read the tour before anything moves
-        if (tid == 0) {
-            S.moves += 1; S.moves_3opt += 1; S.moves_type[T] += 1;
-            if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
-        }
-        if (T <= 1) {          // S1 and S2 each reversed; type 0: then the two together, which leaves S2 S1
-            nl_reverse_path<NT>(order, pos, n, at1, s1);
-            nl_reverse_path<NT>(order, pos, n, at2, s2);
-            if (T == 0) {
-                __syncthreads();
-                nl_reverse_path<NT>(order, pos, n, at1, s1 + s2);
-            }
-        } else {               // the two together (S2' S1'), then its second part (type 2: S2' S1) or its first (type 3: S2 S1')
-            nl_reverse_path<NT>(order, pos, n, at1, s1 + s2);
-            __syncthreads();
-            if (T == 2) nl_reverse_path<NT>(order, pos, n, or_wrap(at1 + s2, n), s1);
-            else nl_reverse_path<NT>(order, pos, n, at1, s2);
-        }
-        return;
-    }
-    if (!(bk & kNlOrBit)) {
-        // 2-opt: the forward path i1 .. j (positions pi + 1 .. pi + len) is reversed in place
-        const int i = (int)(bk / (u64)n), j = (int)(bk % (u64)n);
-        const int pi = pos[i];
-        const int len = ahead(pos[j], pi, n);
-        __syncthreads();
-        if (tid == 0) {
-            S.moves += 1; S.moves_2opt += 1; S.reversed += len - 1;   // the successors rewritten: all of the path but i1's
-            if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
-        }
-        nl_reverse_path<NT>(order, pos, n, or_wrap(pi + 1, n), len);
-        return;
-    }
-    const u64 key = bk & (kNlOrBit - 1);
-    const int o = (int)(key & 1);
-    const u64 t = key >> 1;
-    const int a = (int)(t % (u64)n);
-    const int fl = (int)(t / (u64)n);
-    const int L = fl % 3 + 1, f = fl / 3;
-    const int i = pos[f], ja = pos[a];
-    int x[3] = {0, 0, 0};
-    for (int q = 0; q < L; ++q) x[q] = order[or_wrap(i + q, n)];
-    __syncthreads();   // every thread has read the tour before anything moves
-    if (tid == 0) {
-        S.moves += 1; S.moves_oropt += 1; S.moves_len[L - 1] += 1; S.moves_rev += o;
-        if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
-    }
-    or_shift_apply<NT>(order, pos, n, i, ja, L, o, x);
-}
-
-void launch_decision3(tsp_dev_tours *t, NlData *x, int kinds) {
-    tsp_dev_inst *inst = t->inst;
-    hipStream_t s = inst->ctx->stream;
-    const int n = t->n, B = t->B;
-    const bool low = kinds & (TSP_NL_2OPT | TSP_NL_OROPT), three = kinds & TSP_NL_3OPT;
-    NlBest *parts3 = x->d_part + (size_t)B * x->nparts;
-    tsp_nl_launch_scan(t, x, kinds);
-    if (three) {
-        TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-            hipLaunchKernelGGL((k_nl3_scan<WTC, INTC>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
-                               x->d_st, n, x->K, x->d_nbr, x->d_E, parts3);
-        });
-    }
-    hipLaunchKernelGGL(k_nl3_pick_apply, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
-                       low ? x->d_part : nullptr, three ? parts3 : nullptr);
-}
-
 }  // namespace
+
+void tsp_nl3_launch_scan(tsp_dev_tours *t, NlData *x, NlBest *parts3) {
+    tsp_dev_inst *inst = t->inst;
+    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
+        hipLaunchKernelGGL((k_nl3_scan<WTC, INTC>), dim3(x->nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord, t->d_order,
+                           t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3);
+    });
+}
+
+static_assert(offsetof(tsp_nl3_opt_stats, moves_3opt) == sizeof(tsp_nl_opt_stats), "tsp_nl3_opt_stats starts as tsp_nl_opt_stats");
 
 extern "C" {
 
 int tsp_dev_nl_3opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
                     int64_t max_moves, double time_limit_s, tsp_nl3_opt_stats *stats) {
-    if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
-    if (kinds < 1 || kinds > (TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT)) return TSP_DEV_E_ARG;
-    const int n = inst->n;
-    if ((kinds & TSP_NL_3OPT) && n > kMaxN3) return TSP_DEV_E_ARG;
-    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
-    // a kind without any move at this size is left out: 2-opt needs four nodes, Or-opt and 3-opt five
-    if (n < 4) kinds &= ~TSP_NL_2OPT;
-    if (n < 5) kinds &= ~(TSP_NL_OROPT | TSP_NL_3OPT);
-    NlData *x = nullptr;
-    double t0 = 0.0;
-    float ms = 0.f;
-    const int status = tsp_nl_descend(inst, kinds, launch_decision3, B, succ, succ_stride, tour_stride, obj, max_moves,
-                                      time_limit_s, &x, &t0, &ms);
+    const NlState *st = nullptr;
+    const int status = tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj,
+                                  max_moves, time_limit_s, stats, sizeof *stats, &st);
     if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
     for (int b = 0; b < B && stats; ++b) {
-        const NlState &z = x->h_st[b];
-        tsp_nl3_opt_stats &o = stats[b];
-        memset(&o, 0, sizeof o);
-        o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
-        for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
-        o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
-        o.seconds = tsp_nl_wall_s() - t0; o.device_ms = ms;
-        o.moves_3opt = z.moves_3opt;
-        for (int q = 0; q < 4; ++q) o.moves_by_type[q] = z.moves_type[q];
+        stats[b].moves_3opt = st[b].moves_3opt;
+        for (int q = 0; q < 4; ++q) stats[b].moves_by_type[q] = st[b].moves_type[q];
     }
     return status;
 }

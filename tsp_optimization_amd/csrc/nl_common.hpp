@@ -1,6 +1,6 @@
 // nl_common.hpp -- what the list descents share: nl_opt.hip (2-opt + Or-opt, tsp_dev_nl_opt) and nl3_opt.hip (those two and the
 // 3-opt kind, tsp_dev_nl_3opt).  The decision word, the per-tour state, the symmetric distance, the reversal of a forward path on
-// order/pos, the lists and scratch of an instance, and the host functions of nl_opt.hip that nl3_opt.hip drives.
+// order/pos, the lists and scratch of an instance, and the host functions the two files call in each other.
 #pragma once
 #include "or_opt_shift.hpp"
 
@@ -13,6 +13,7 @@ constexpr int kNlPickThreads = 1024;
 // 3-opt bit 63 (6 n^2 < 2^62; 4 n^3 <= 2^62 for n <= 2^20).  kNoKey (all ones) is no key of any kind.
 constexpr u64 kNlOrBit = 1ull << 62;
 constexpr u64 kNl3Bit = 1ull << 63;
+constexpr int kNlMaxN3 = 1 << 20;   // 4 n^3 must stay below the kind bits of the decision key
 
 struct alignas(16) NlBest {
     double d;
@@ -26,8 +27,9 @@ struct alignas(16) NlState {
     int done, pad;
 };
 
-__device__ __forceinline__ void nl_offer(double delta, u64 key, double &bd, u64 &bk) {
-    if (delta < 0.0 && better(delta, key, bd, bk)) { bd = delta; bk = key; }
+__device__ __forceinline__ int ahead(int px, int from, int n) {   // px - from mod n
+    const int g = px - from;
+    return g < 0 ? g + n : g;
 }
 
 // calc_dist of two nodes, the lower id first
@@ -69,15 +71,10 @@ struct NlData {
 
 }  // namespace tsp
 
-// nl_opt.hip
-double tsp_nl_wall_s();
-// k_nl_prep, then k_nl_scan when kinds has one of its two: the edge lengths E, and one candidate per workgroup in the first
-// B x nparts entries of d_part
-void tsp_nl_launch_scan(tsp_dev_tours *t, tsp::NlData *x, int kinds);
-// One whole decision (scans, pick, apply) of every tour that is not done, queued on the engine's stream.
-typedef void (*tsp_nl_decision_fn)(tsp_dev_tours *t, tsp::NlData *x, int kinds);
-// The descent both entry points run: upload, the default lists, `decision` queued in growing batches until every tour is done,
-// the cost of the final tours, download.  `kinds` already holds only kinds that have a move at this size.  On return (>= 0)
-// x->h_st[0 .. B-1] are the final states, *t0 the call's start on the host clock, *ms the device time.
-int tsp_nl_descend(tsp_dev_inst *inst, int kinds, tsp_nl_decision_fn decision, int B, int *succ, int succ_stride,
-                   int64_t tour_stride, double *obj, int64_t max_moves, double time_limit_s, tsp::NlData **xo, double *t0o, float *ms);
+// nl3_opt.hip: k_nl3_scan of every tour that is not done, one candidate per workgroup in parts3 (B x nparts)
+void tsp_nl3_launch_scan(tsp_dev_tours *t, tsp::NlData *x, tsp::NlBest *parts3);
+// nl_opt.hip: what both entry points do.  `allowed` is the kinds mask the entry point takes.  stats (may be NULL): B records
+// `stats_stride` bytes apart that start with the layout of tsp_nl_opt_stats; that part of each is filled here.  With TSP_OK or
+// TSP_TIME_LIMIT_EXCEEDED *states (unless NULL) are the B final states, for what the caller's records hold beyond it.
+int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+               int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const tsp::NlState **states);

@@ -9,10 +9,8 @@
 // Every distance goes through dsym(): the lower node id first, so that a move reached through several (v, u, role)
 // combinations has the same delta bits each time.  A 2-opt move always reverses the forward path i1 .. j in place, so that
 // order/pos keep the orientation of succ and the Or-opt shift works unchanged.
+#include "descent.hpp"
 #include "nl_common.hpp"
-
-#include <time.h>
-#include <algorithm>
 
 #pragma clang fp contract(off)
 
@@ -23,8 +21,6 @@ namespace {
 constexpr int kK = TSP_NL_MAX_K;     // k_knn_scan keeps this many per row whatever K is asked for: the K best are a prefix
 constexpr int kKnnChunks = 16;       // k_knn_scan: most column chunks per row
 constexpr int kKnnWaves = 4096;      // ... chosen so that about this many waves exist
-constexpr int kPickThreads = kNlPickThreads;
-constexpr u64 kKindBit = kNlOrBit;   // decision key: kind in bit 62, the kind's own key below (nl_common.hpp)
 
 // (d, id) into the sorted list; d == a held distance goes behind it (the callers offer equal distances in id order)
 __device__ __forceinline__ void knn_insert(double (&kd)[kK], int (&ki)[kK], double d, int id) {
@@ -131,7 +127,7 @@ struct NlView {
         const double dij = known == 0 ? dk : d(x, y), d11 = known == 1 ? dk : d(i1, j1);
         const double delta = ((dij + d11) - E[x]) - E[y];
         cnt += 1;
-        nl_offer(delta, (u64)x * (u64)n + (u64)y, bd, bk);
+        offer(delta, (u64)x * (u64)n + (u64)y, bd, bk);
     }
 
     // Or-opt move (f, L, a, o); `known` says which attaching edge has the length dk: 0 = the one at a, 1 = the one at b
@@ -145,7 +141,7 @@ struct NlView {
         const double d2 = known == 1 ? dk : (o ? d(f, bb) : d(l, bb));
         const double delta = ((d1 + d2) - E[a]) - rem[(size_t)(L - 1) * n + f];
         cnt += 1;
-        nl_offer(delta, kKindBit | (u64)((((long long)f * 3 + (L - 1)) * n + a) * 2 + o), bd, bk);
+        offer(delta, kNlOrBit | or_key(f, L, a, o, n), bd, bk);
     }
 
     // the ten Or-opt moves that attach the segment with the edge x -> y (x ahead of y in the new tour)
@@ -206,52 +202,82 @@ __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coo
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd((unsigned long long *)&st[b].deltas, cnt);
 }
 
-// Decision over the workgroups' candidates, then the move.  One workgroup per tour.
-__global__ __launch_bounds__(kPickThreads) void k_nl_pick_apply(int *__restrict__ orders, int *__restrict__ poss,
-                                                                NlState *__restrict__ st, int n, int nparts,
-                                                                const NlBest *__restrict__ parts) {
-    const int b = blockIdx.x;
-    NlState &S = st[b];
+// Decision over the candidates of k_nl_scan (parts2) and k_nl3_scan (parts3; either may be NULL: no kind of it is enabled), then
+// the move.  One workgroup per tour.
+__global__ __launch_bounds__(kNlPickThreads) void k_nl_pick_apply(int *__restrict__ orders, int *__restrict__ poss,
+                                                                  NlState *__restrict__ st, int n, int nparts,
+                                                                  const NlBest *__restrict__ parts2,
+                                                                  const NlBest *__restrict__ parts3) {
+    constexpr int NT = kNlPickThreads;
+    const int bt = blockIdx.x;
+    NlState &S = st[bt];
     if (S.done) return;
-    __shared__ double sd[kPickThreads / 64];
-    __shared__ u64 sk[kPickThreads / 64];
+    __shared__ double sd[NT / 64];
+    __shared__ u64 sk[NT / 64];
     const int tid = threadIdx.x;
     if (S.max_moves >= 0 && S.moves >= S.max_moves) {
         if (tid == 0) S.done = 1;
         return;
     }
-    const NlBest *part = parts + (size_t)b * nparts;
     double bd = INFINITY; u64 bk = kNoKey;
-    for (int r = tid; r < nparts; r += kPickThreads) {
-        const NlBest q = part[r];
-        if (q.k != kNoKey && better(q.d, q.k, bd, bk)) { bd = q.d; bk = q.k; }
+    for (int h = 0; h < 2; ++h) {
+        const NlBest *part = h ? parts3 : parts2;
+        if (!part) continue;
+        part += (size_t)bt * nparts;
+        for (int r = tid; r < nparts; r += NT) {
+            const NlBest q = part[r];
+            if (q.k != kNoKey && better(q.d, q.k, bd, bk)) { bd = q.d; bk = q.k; }
+        }
     }
     block_argmin<true>(bd, bk, sd, sk);
     __syncthreads();
     if (tid == 0) { S.decisions += 1; if (bk == kNoKey) S.done = 1; }
     if (bk == kNoKey) return;
-    int *order = orders + (size_t)b * n, *pos = poss + (size_t)b * n;
-    if (!(bk & kKindBit)) {
+    int *order = orders + (size_t)bt * n, *pos = poss + (size_t)bt * n;
+    if (bk & kNl3Bit) {
+        const u64 key = bk & (kNl3Bit - 1);
+        const int T = (int)(key & 3);
+        const u64 abc = key >> 2;
+        const int c = (int)(abc % (u64)n), b = (int)((abc / (u64)n) % (u64)n), a = (int)(abc / ((u64)n * (u64)n));
+        const int pa = pos[a];
+        const int s1 = ahead(pos[b], pa, n), s2 = ahead(pos[c], pa, n) - s1;
+        const int at1 = or_wrap(pa + 1, n), at2 = or_wrap(at1 + s1, n);   // where S1 = a1 .. b and S2 = b1 .. c start
+        __syncthreads();   // every thread has read the tour before anything moves
+        if (tid == 0) {
+            S.moves += 1; S.moves_3opt += 1; S.moves_type[T] += 1;
+            if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
+        }
+        if (T <= 1) {          // S1 and S2 each reversed; type 0: then the two together, which leaves S2 S1
+            nl_reverse_path<NT>(order, pos, n, at1, s1);
+            nl_reverse_path<NT>(order, pos, n, at2, s2);
+            if (T == 0) {
+                __syncthreads();
+                nl_reverse_path<NT>(order, pos, n, at1, s1 + s2);
+            }
+        } else {               // the two together (S2' S1'), then its second part (type 2: S2' S1) or its first (type 3: S2 S1')
+            nl_reverse_path<NT>(order, pos, n, at1, s1 + s2);
+            __syncthreads();
+            if (T == 2) nl_reverse_path<NT>(order, pos, n, or_wrap(at1 + s2, n), s1);
+            else nl_reverse_path<NT>(order, pos, n, at1, s2);
+        }
+        return;
+    }
+    if (!(bk & kNlOrBit)) {
         // 2-opt: the forward path i1 .. j (positions pi + 1 .. pi + len) is reversed in place
         const int i = (int)(bk / (u64)n), j = (int)(bk % (u64)n);
         const int pi = pos[i];
-        int len = pos[j] - pi;
-        if (len < 0) len += n;
+        const int len = ahead(pos[j], pi, n);
         __syncthreads();
         if (tid == 0) {
             S.moves += 1; S.moves_2opt += 1; S.reversed += len - 1;   // the successors rewritten: all of the path but i1's
             if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
         }
-        nl_reverse_path<kPickThreads>(order, pos, n, or_wrap(pi + 1, n), len);
+        nl_reverse_path<NT>(order, pos, n, or_wrap(pi + 1, n), len);
         return;
     }
-    const u64 key = bk & (kKindBit - 1);
-    const int o = (int)(key & 1);
-    const u64 t = key >> 1;
-    const int a = (int)(t % (u64)n);
-    const int fl = (int)(t / (u64)n);
-    const int L = fl % 3 + 1, f = fl / 3;
-    const int i = pos[f], ja = pos[a];
+    const OrMove mv = or_unkey(bk & (kNlOrBit - 1), n);
+    const int L = mv.L, o = mv.o;
+    const int i = pos[mv.f], ja = pos[mv.a];
     int x[3] = {0, 0, 0};
     for (int q = 0; q < L; ++q) x[q] = order[or_wrap(i + q, n)];
     __syncthreads();   // every thread has read the tour before anything moves
@@ -259,7 +285,7 @@ __global__ __launch_bounds__(kPickThreads) void k_nl_pick_apply(int *__restrict_
         S.moves += 1; S.moves_oropt += 1; S.moves_len[L - 1] += 1; S.moves_rev += o;
         if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
     }
-    or_shift_apply<kPickThreads>(order, pos, n, i, ja, L, o, x);
+    or_shift_apply<NT>(order, pos, n, i, ja, L, o, x);
 }
 
 NlData *nl_data(tsp_dev_inst *inst) {
@@ -282,43 +308,29 @@ int scratch_alloc(NlData *x, int B, int n, int K) {
     return TSP_OK;
 }
 
+// One whole decision of every tour that is not done, queued on the engine's stream: k_nl_prep, k_nl_scan when kinds has one of
+// its two (candidates in the first B x nparts entries of d_part), k_nl3_scan when it has the third (in the second), the pick.
 void launch_decision(tsp_dev_tours *t, NlData *x, int kinds) {
-    tsp_nl_launch_scan(t, x, kinds);
-    hipLaunchKernelGGL(k_nl_pick_apply, dim3(t->B), dim3(kPickThreads), 0, t->inst->ctx->stream, t->d_order, t->d_pos, x->d_st,
-                       t->n, x->nparts, x->d_part);
-}
-
-}  // namespace
-
-double tsp_nl_wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
-void tsp_nl_launch_scan(tsp_dev_tours *t, NlData *x, int kinds) {
     tsp_dev_inst *inst = t->inst;
     hipStream_t s = inst->ctx->stream;
     const int n = t->n, B = t->B;
+    const bool low = kinds & (TSP_NL_2OPT | TSP_NL_OROPT), three = kinds & TSP_NL_3OPT;
+    NlBest *parts3 = x->d_part + (size_t)B * x->nparts;
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         hipLaunchKernelGGL((k_nl_prep<WTC, INTC>), dim3((n + 255) / 256, B), dim3(256), 0, s, inst->d_coord, t->d_order, x->d_st, n,
                            x->d_E, x->d_rem);
-        if (kinds & (TSP_NL_2OPT | TSP_NL_OROPT))
+        if (low)
             hipLaunchKernelGGL((k_nl_scan<WTC, INTC>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
                                x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part);
     });
+    if (three) tsp_nl3_launch_scan(t, x, parts3);
+    hipLaunchKernelGGL(k_nl_pick_apply, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
+                       low ? x->d_part : nullptr, three ? parts3 : nullptr);
 }
-
-namespace {
-
-double wall_s() { return tsp_nl_wall_s(); }
 
 bool bad_k(const tsp_dev_inst *inst, int K) { return K < 1 || K > TSP_NL_MAX_K || K > inst->n - 1; }
 
 }  // namespace
-
-tsp_dev_tours *tsp_scratch_tours(tsp_dev_inst *inst, int B, bool *owned, int *rc);   // api.hip
-int tsp_grid_tour_cost(tsp_dev_tours *t, double *d_out);                          // two_opt_grid.hip
 
 void tsp_nl_data_free(void *p) { delete static_cast<NlData *>(p); }
 
@@ -330,6 +342,45 @@ int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr) {
     x->d_nbr = d_nbr;
     x->K = K;
     return TSP_OK;
+}
+
+int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+               int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const NlState **states) {
+    if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
+    if (kinds < 1 || (kinds & ~allowed)) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    if ((kinds & TSP_NL_3OPT) && n > kNlMaxN3) return TSP_DEV_E_ARG;
+    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
+    // a kind without any move at this size is left out: 2-opt needs four nodes, Or-opt and 3-opt five
+    if (n < 4) kinds &= ~TSP_NL_2OPT;
+    if (n < 5) kinds &= ~(TSP_NL_OROPT | TSP_NL_3OPT);
+    Descent run;
+    int rc = run.open(inst, B, succ, succ_stride, tour_stride, obj);
+    if (rc) return rc;
+    NlData *x = nl_data(inst);
+    if (x->K == 0) {
+        rc = tsp_dev_inst_knn_build(inst, std::min(TSP_NL_DEFAULT_K, n - 1), nullptr);
+        if (rc) return rc;
+    }
+    if (x->B != B || x->parts_K != x->K) {
+        rc = scratch_alloc(x, B, n, x->K);
+        if (rc) { x->free_scratch(); return rc; }
+    }
+    const bool trivial = kinds == 0 || max_moves == 0;
+    const int status = run.run(x->d_st, x->h_st, x->d_cost, trivial, 256, max_moves, time_limit_s,
+                               [&](bool) { launch_decision(run.t, x, kinds); });
+    if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
+    for (int b = 0; b < B && stats; ++b) {
+        const NlState &z = x->h_st[b];
+        tsp_nl_opt_stats &o = *reinterpret_cast<tsp_nl_opt_stats *>(static_cast<char *>(stats) + (size_t)b * stats_stride);
+        memset(&o, 0, sizeof o);
+        o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
+        for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
+        o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
+        o.seconds = wall_s() - run.t0; o.device_ms = run.device_ms;
+    }
+    if (states) *states = x->h_st;
+    return status;
 }
 
 extern "C" {
@@ -347,7 +398,7 @@ int tsp_dev_inst_knn_build(tsp_dev_inst *inst, int K, float *kernel_ms) {
     TSP_HIP_TRY(pd.alloc((size_t)Cc * kK * n));
     TSP_HIP_TRY(pi.alloc((size_t)Cc * kK * n));
     TSP_HIP_TRY(nbr.alloc((size_t)n * K));
-    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    if (int e = tsp_inst_events(inst)) return e;
     TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         hipLaunchKernelGGL((k_knn_scan<WTC, INTC>), dim3((n + 255) / 256, Cc), dim3(256), 0, s, inst->d_coord, n, CH, pd.p, pi.p);
@@ -397,116 +448,10 @@ int tsp_dev_inst_knn_get(tsp_dev_inst *inst, int *K, int *nbr) {
     return TSP_OK;
 }
 
-
-}  // extern "C"
-
-int tsp_nl_descend(tsp_dev_inst *inst, int kinds, tsp_nl_decision_fn decision, int B, int *succ, int succ_stride,
-                   int64_t tour_stride, double *obj, int64_t max_moves, double time_limit_s, NlData **xo, double *t0o, float *ms) {
-    const int n = inst->n;
-    const double t0 = wall_s();
-    *t0o = t0;
-    TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
-    hipStream_t s = inst->ctx->stream;
-    bool owned = false;
-    int rc = TSP_OK;
-    tsp_dev_tours *t = tsp_scratch_tours(inst, B, &owned, &rc);
-    if (rc) return rc;
-    struct Own { tsp_dev_tours *t; bool o; ~Own() { if (o) tsp_dev_tours_destroy(t); } } own{t, owned};
-    rc = tsp_dev_tours_upload(t, succ, succ_stride, tour_stride, obj);   // checks every successor list
-    if (rc) return rc;
-    NlData *x = nl_data(inst);
-    *xo = x;
-    if (x->K == 0) {
-        rc = tsp_dev_inst_knn_build(inst, std::min(TSP_NL_DEFAULT_K, n - 1), nullptr);
-        if (rc) return rc;
-    }
-    if (x->B != B || x->parts_K != x->K) {
-        rc = scratch_alloc(x, B, n, x->K);
-        if (rc) { x->free_scratch(); return rc; }
-    }
-    const bool trivial = kinds == 0 || max_moves == 0;
-    for (int b = 0; b < B; ++b) {
-        NlState z;
-        memset(&z, 0, sizeof z);
-        z.max_moves = max_moves < 0 ? -1 : max_moves;
-        z.done = trivial ? 1 : 0;
-        x->h_st[b] = z;
-    }
-    TSP_HIP_TRY(hipMemcpyAsync(x->d_st, x->h_st, sizeof(NlState) * B, hipMemcpyHostToDevice, s));
-    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
-    TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
-    int status = TSP_OK;
-    if (!trivial) {
-        double tq = wall_s();
-        decision(t, x, kinds);
-        int batch = 4, queued = 1;
-        for (;;) {
-            TSP_HIP_TRY(hipMemcpyAsync(x->h_st, x->d_st, sizeof(NlState) * B, hipMemcpyDeviceToHost, s));
-            TSP_HIP_TRY(hipStreamSynchronize(s));
-            TSP_HIP_TRY(hipGetLastError());
-            bool all = true;
-            for (int b = 0; b < B; ++b) all = all && x->h_st[b].done;
-            if (all) break;
-            const double now = wall_s();
-            if (time_limit_s > 0 && now - t0 > time_limit_s) { status = TSP_TIME_LIMIT_EXCEEDED; break; }
-            int next = batch;
-            if (time_limit_s > 0) {
-                // no more decisions than the budget left holds at the last batch's rate
-                const double per = (now - tq) / queued, left = time_limit_s - (now - t0);
-                if (per > 0.0) next = (int)std::max(1.0, std::min((double)batch, left / per));
-            }
-            // decisions queued back to back; those behind a tour's last one return at once (done)
-            tq = now;
-            for (int k = 0; k < next; ++k) decision(t, x, kinds);
-            queued = next;
-            batch = std::min(batch * 2, 256);
-        }
-    }
-    {
-        int r2 = tsp_grid_tour_cost(t, x->d_cost);
-        if (r2) return r2;
-    }
-    TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
-    TSP_HIP_TRY(hipEventSynchronize(inst->ev1));
-    TSP_HIP_TRY(hipGetLastError());
-    *ms = 0.f;
-    TSP_HIP_TRY(hipEventElapsedTime(ms, inst->ev0, inst->ev1));
-    std::vector<double> cost((size_t)B);
-    TSP_HIP_TRY(hipMemcpyAsync(cost.data(), x->d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-    TSP_HIP_TRY(hipMemcpyAsync(x->h_st, x->d_st, sizeof(NlState) * B, hipMemcpyDeviceToHost, s));
-    rc = tsp_dev_tours_download(t, succ, succ_stride, tour_stride, nullptr, nullptr);   // (synchronises the stream)
-    if (rc) return rc;
-    for (int b = 0; b < B; ++b) obj[b] = cost[b];
-    return status;
-}
-
-extern "C" {
-
 int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
                    int64_t max_moves, double time_limit_s, tsp_nl_opt_stats *stats) {
-    if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
-    if (kinds < 1 || kinds > (TSP_NL_2OPT | TSP_NL_OROPT)) return TSP_DEV_E_ARG;
-    const int n = inst->n;
-    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
-    // a kind without any move at this size is left out: 2-opt needs four nodes, Or-opt five
-    if (n < 4) kinds &= ~TSP_NL_2OPT;
-    if (n < 5) kinds &= ~TSP_NL_OROPT;
-    NlData *x = nullptr;
-    double t0 = 0.0;
-    float ms = 0.f;
-    const int status = tsp_nl_descend(inst, kinds, launch_decision, B, succ, succ_stride, tour_stride, obj, max_moves, time_limit_s,
-                                      &x, &t0, &ms);
-    if (status < 0 || (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED)) return status;
-    for (int b = 0; b < B && stats; ++b) {
-        const NlState &z = x->h_st[b];
-        tsp_nl_opt_stats &o = stats[b];
-        memset(&o, 0, sizeof o);
-        o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
-        for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
-        o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
-        o.seconds = wall_s() - t0; o.device_ms = ms;
-    }
-    return status;
+    return tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT, B, succ, succ_stride, tour_stride, obj, max_moves, time_limit_s, stats,
+                      sizeof *stats, nullptr);
 }
 
 }  // extern "C"

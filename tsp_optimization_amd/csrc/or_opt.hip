@@ -15,10 +15,8 @@
 // Per row (f, L) the cache holds the lexicographically smallest (delta, key) among its improving candidates, or none.
 // A row whose segment, p and s kept their succ / pred and whose cached insertion edge still exists keeps every old
 // candidate's delta, so its new best is min(cached, candidates on the new edges): both paths take the same decisions.
+#include "descent.hpp"
 #include "or_opt_shift.hpp"
-
-#include <time.h>
-#include <algorithm>
 
 #pragma clang fp contract(off)
 
@@ -47,20 +45,10 @@ struct alignas(16) OrState {
     int pad;
 };
 
-__device__ __forceinline__ int wrap(int x, int n) { return x >= n ? x - n : (x < 0 ? x + n : x); }
-
 template <int WT, bool INT>
 __device__ __forceinline__ double dnode(const double2 *coord, int u, int v) {
     const double2 a = coord[u], b = coord[v];
     return dist_xy<WT, INT>(a.x, a.y, b.x, b.y);
-}
-
-__device__ __forceinline__ u64 or_key(int f, int L, int a, int o, int n) {
-    return (u64)((((long long)f * 3 + (L - 1)) * n + a) * 2 + o);
-}
-
-__device__ __forceinline__ void offer(double delta, u64 key, double &bd, u64 &bk) {
-    if (delta < 0.0 && better(delta, key, bd, bk)) { bd = delta; bk = key; }
 }
 
 // wave_shr:1 of a double (lane 0 receives 0)
@@ -71,6 +59,7 @@ __device__ __forceinline__ double shr1(double v) {
 }
 
 // (delta, key) minimum over the block; every thread receives it.  Lanes without a candidate hold (inf, kNoKey).
+// Not block_argmin<true> of two_opt_common.hpp: every thread walks the waves' entries there, k_or_pick_apply then takes 38 VGPRs for 12.
 __device__ __forceinline__ void block_argmin(double &d, u64 &k, double *sd, u64 *sk) {
     wave_argmin<true>(d, k);
     const int w = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
@@ -100,14 +89,14 @@ __global__ void k_or_prep(const double2 *__restrict__ coord, const int *__restri
     if (i == n) { P[n] = coord[order[0]]; return; }
     const int v = order[i];
     P[i] = coord[v];
-    const int pm = order[wrap(i - 1, n)], v1 = order[wrap(i + 1, n)];
+    const int pm = order[or_wrap(i - 1, n)], v1 = order[or_wrap(i + 1, n)];
     const double dpf = dnode<WT, INT>(coord, pm, v);
     const double e0 = dnode<WT, INT>(coord, v, v1);
     Es[(size_t)b * n + i] = e0;
     double *rem = rems + (size_t)b * 3 * n;
     // L = 1: l = v, s = v1
     rem[i] = (dpf + e0) - dnode<WT, INT>(coord, pm, v1);
-    const int v2 = order[wrap(i + 2, n)], v3 = order[wrap(i + 3, n)];
+    const int v2 = order[or_wrap(i + 2, n)], v3 = order[or_wrap(i + 3, n)];
     rem[n + i] = (dpf + dnode<WT, INT>(coord, v1, v2)) - dnode<WT, INT>(coord, pm, v2);
     rem[2 * n + i] = (dpf + dnode<WT, INT>(coord, v2, v3)) - dnode<WT, INT>(coord, pm, v3);
 }
@@ -147,8 +136,8 @@ __global__ __launch_bounds__(256) void k_or_scan(const int *__restrict__ orders,
     const bool own1 = i1 >= base && i1 < base + kRowsPerWave && i1 < n;
     const bool own2 = i2 >= base && i2 < base + kRowsPerWave && i2 < n;
     const bool own3 = i3 >= base && i3 < base + kRowsPerWave && i3 < n;
-    const int f1 = order[pu], f2 = order[wrap(pu - 1, n)], f3 = order[wrap(pu - 2, n)];
-    const double r1 = rem[pu], r2 = rem[n + wrap(pu - 1, n)], r3 = rem[2 * n + wrap(pu - 2, n)];
+    const int f1 = order[pu], f2 = order[or_wrap(pu - 1, n)], f3 = order[or_wrap(pu - 2, n)];
+    const double r1 = rem[pu], r2 = rem[n + or_wrap(pu - 1, n)], r3 = rem[2 * n + or_wrap(pu - 2, n)];
     double bd1 = INFINITY, bd2 = INFINITY, bd3 = INFINITY;
     u64 bk1 = kNoKey, bk2 = kNoKey, bk3 = kNoKey;
     double p0, p1, p2;   // D(u, j), D(u-1, j), D(u-2, j)
@@ -236,7 +225,7 @@ __global__ __launch_bounds__(256) void k_or_mark(const double2 *__restrict__ coo
         bool rescan = false;
         int win[5];
         for (int q = 0; q < L + 2; ++q) {   // p, x1 .. xL, s
-            const int v = order[wrap(i - 1 + q, n)];
+            const int v = order[or_wrap(i - 1 + q, n)];
             win[q] = v;
             for (int c = 0; c < nchg; ++c) rescan = rescan || v == S.chg[c];
         }
@@ -257,7 +246,7 @@ __global__ __launch_bounds__(256) void k_or_mark(const double2 *__restrict__ coo
                 bool inside = false;
                 for (int q = 0; q <= L; ++q) inside = inside || a == win[q];
                 if (inside) continue;
-                cnt += row_edge<WT, INT>(coord, n, f, l, L, rem, a, order[wrap(pos[a] + 1, n)], cur.d, cur.k);
+                cnt += row_edge<WT, INT>(coord, n, f, l, L, rem, a, order[or_wrap(pos[a] + 1, n)], cur.d, cur.k);
             }
             if (cur.k != best->k) *best = cur;
             atomicAdd(&s_cnt, cnt);
@@ -284,7 +273,7 @@ __global__ __launch_bounds__(256) void k_or_rescan(const double2 *__restrict__ c
         const int r = dirty[(size_t)b * 3 * n + q];
         const int Lm = r / n, L = Lm + 1, f = r - Lm * n;
         const int i = pos[f];
-        const int p = order[wrap(i - 1, n)], l = order[wrap(i + L - 1, n)], s = order[wrap(i + L, n)];
+        const int p = order[or_wrap(i - 1, n)], l = order[or_wrap(i + L - 1, n)], s = order[or_wrap(i + L, n)];
         const double rem = (dnode<WT, INT>(coord, p, f) + dnode<WT, INT>(coord, l, s)) - dnode<WT, INT>(coord, p, s);
         double bd = INFINITY; u64 bk = kNoKey;
         for (int j = threadIdx.x; j < n; j += blockDim.x) {
@@ -328,15 +317,12 @@ __global__ __launch_bounds__(kPickThreads) void k_or_pick_apply(int *__restrict_
     if (tid == 0) { S.sweeps += 1; if (bk == kNoKey) S.done = 1; }
     if (bk == kNoKey) return;
     int *order = orders + (size_t)b * n, *pos = poss + (size_t)b * n;
-    const int o = (int)(bk & 1);
-    const u64 t = bk >> 1;
-    const int a = (int)(t % (u64)n);
-    const int fl = (int)(t / (u64)n);
-    const int L = fl % 3 + 1, f = fl / 3;
+    const OrMove mv = or_unkey(bk, n);
+    const int f = mv.f, L = mv.L, a = mv.a, o = mv.o;
     const int i = pos[f], ja = pos[a];
     int x[3];
-    for (int q = 0; q < L; ++q) x[q] = order[wrap(i + q, n)];
-    const int p = order[wrap(i - 1, n)], l = x[L - 1], s = order[wrap(i + L, n)], bb = order[wrap(ja + 1, n)];
+    for (int q = 0; q < L; ++q) x[q] = order[or_wrap(i + q, n)];
+    const int p = order[or_wrap(i - 1, n)], l = x[L - 1], s = order[or_wrap(i + L, n)], bb = order[or_wrap(ja + 1, n)];
     __syncthreads();   // every thread has read the tour before anything moves
     if (tid == 0) {
         int nt = 0, nc = 0;
@@ -349,12 +335,6 @@ __global__ __launch_bounds__(kPickThreads) void k_or_pick_apply(int *__restrict_
         if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
     }
     or_shift_apply<kPickThreads>(order, pos, n, i, ja, L, o, x);
-}
-
-double wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
 // Scratch of one (B, n): kept on the instance like the scratch tours handle.
@@ -420,9 +400,6 @@ void launch_incremental(tsp_dev_tours *t, OrScratch *x) {
 
 }  // namespace
 
-tsp_dev_tours *tsp_scratch_tours(tsp_dev_inst *inst, int B, bool *owned, int *rc);   // api.hip
-int tsp_grid_tour_cost(tsp_dev_tours *t, double *d_out);                          // two_opt_grid.hip
-
 void tsp_or_scratch_free(void *p) { delete static_cast<OrScratch *>(p); }
 
 extern "C" {
@@ -432,16 +409,10 @@ int tsp_dev_or_opt(tsp_dev_inst *inst, int B, int *succ, int succ_stride, int64_
     if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
     const int n = inst->n;
     if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
-    const double t0 = wall_s();
-    TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
-    hipStream_t s = inst->ctx->stream;
-    bool owned = false;
-    int rc = TSP_OK;
-    tsp_dev_tours *t = tsp_scratch_tours(inst, B, &owned, &rc);
+    Descent run;
+    int rc = run.open(inst, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
-    struct Own { tsp_dev_tours *t; bool o; ~Own() { if (o) tsp_dev_tours_destroy(t); } } own{t, owned};
-    rc = tsp_dev_tours_upload(t, succ, succ_stride, tour_stride, obj);   // checks every successor list
-    if (rc) return rc;
+    tsp_dev_tours *t = run.t;
     OrScratch *x = static_cast<OrScratch *>(inst->or_scratch);
     if (!x || x->B != B || x->n != n) {
         tsp_or_scratch_free(x);
@@ -452,75 +423,24 @@ int tsp_dev_or_opt(tsp_dev_inst *inst, int B, int *succ, int succ_stride, int64_
         inst->or_scratch = x;
     }
     const bool trivial = n < 5 || max_moves == 0;
-    for (int b = 0; b < B; ++b) {
-        OrState z;
-        memset(&z, 0, sizeof z);
-        z.max_moves = max_moves < 0 ? -1 : max_moves;
-        z.done = trivial ? 1 : 0;
-        x->h_st[b] = z;
-    }
-    TSP_HIP_TRY(hipMemcpyAsync(x->d_st, x->h_st, sizeof(OrState) * B, hipMemcpyHostToDevice, s));
-    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
-    TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
     const bool full = TSP_SW(inst, OROPT_FULL, 0) == 1;
-    int status = TSP_OK;
-    if (!trivial) {
-        double tq = wall_s();
-        launch_full(t, x);
-        int batch = 4, queued = 1;
-        for (;;) {
-            TSP_HIP_TRY(hipMemcpyAsync(x->h_st, x->d_st, sizeof(OrState) * B, hipMemcpyDeviceToHost, s));
-            TSP_HIP_TRY(hipStreamSynchronize(s));
-            TSP_HIP_TRY(hipGetLastError());
-            bool all = true;
-            for (int b = 0; b < B; ++b) all = all && x->h_st[b].done;
-            if (all) break;
-            const double now = wall_s();
-            if (time_limit_s > 0 && now - t0 > time_limit_s) { status = TSP_TIME_LIMIT_EXCEEDED; break; }
-            int next = batch;
-            if (time_limit_s > 0) {
-                // no more decisions than the budget left holds at the last batch's rate: the overshoot stays within about
-                // one decision however long a decision takes (a full sweep of a large instance)
-                const double per = (now - tq) / queued, left = time_limit_s - (now - t0);
-                if (per > 0.0) next = (int)std::max(1.0, std::min((double)batch, left / per));
-            }
-            // decisions queued back to back; those behind a tour's last one return at once (done)
-            tq = now;
-            for (int k = 0; k < next; ++k) {
-                if (full) launch_full(t, x);
-                else launch_incremental(t, x);
-            }
-            queued = next;
-            batch = std::min(batch * 2, 128);
-        }
-    }
-    {
-        int r2 = tsp_grid_tour_cost(t, x->d_cost);
-        if (r2) return r2;
-    }
-    TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
-    TSP_HIP_TRY(hipEventSynchronize(inst->ev1));
-    TSP_HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    TSP_HIP_TRY(hipEventElapsedTime(&ms, inst->ev0, inst->ev1));
-    std::vector<double> cost((size_t)B);
-    TSP_HIP_TRY(hipMemcpyAsync(cost.data(), x->d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-    TSP_HIP_TRY(hipMemcpyAsync(x->h_st, x->d_st, sizeof(OrState) * B, hipMemcpyDeviceToHost, s));
-    rc = tsp_dev_tours_download(t, succ, succ_stride, tour_stride, nullptr, nullptr);   // (synchronises the stream)
-    if (rc) return rc;
+    // the first decision is a full one, the later ones work from what the move before them changed
+    auto queue = [&](bool first) {
+        if (first || full) launch_full(t, x);
+        else launch_incremental(t, x);
+    };
+    const int status = run.run(x->d_st, x->h_st, x->d_cost, trivial, 128, max_moves, time_limit_s, queue);
+    if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
     const long long N = n >= 5 ? (long long)n * (5LL * n - 16) : 0;
-    for (int b = 0; b < B; ++b) {
-        obj[b] = cost[b];
-        if (stats) {
-            const OrState &z = x->h_st[b];
-            tsp_or_opt_stats &o = stats[b];
-            memset(&o, 0, sizeof o);
-            o.sweeps = z.sweeps; o.evals = z.sweeps * N; o.moves = z.moves;
-            for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
-            o.moves_reversed = z.moves_rev; o.deltas_executed = z.deltas;
-            o.rounds = 0;
-            o.seconds = wall_s() - t0; o.device_ms = ms;
-        }
+    for (int b = 0; b < B && stats; ++b) {
+        const OrState &z = x->h_st[b];
+        tsp_or_opt_stats &o = stats[b];
+        memset(&o, 0, sizeof o);
+        o.sweeps = z.sweeps; o.evals = z.sweeps * N; o.moves = z.moves;
+        for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
+        o.moves_reversed = z.moves_rev; o.deltas_executed = z.deltas;
+        o.rounds = 0;
+        o.seconds = wall_s() - run.t0; o.device_ms = run.device_ms;
     }
     return status;
 }

@@ -1,10 +1,28 @@
-// or_opt_shift.hpp -- the Or-opt move on order/pos, shared by k_or_pick_apply (or_opt.hip) and k_nl_pick_apply (nl_opt.hip).
+// or_opt_shift.hpp -- the Or-opt move, its key and its shift on order/pos, shared by or_opt.hip and the list descent (nl_opt.hip).
 #pragma once
 #include "two_opt_common.hpp"
 
 namespace tsp {
 
 __device__ __forceinline__ int or_wrap(int x, int n) { return x >= n ? x - n : (x < 0 ? x + n : x); }
+
+// an improving candidate replaces the held one when it is the smaller (delta, key)
+__device__ __forceinline__ void offer(double delta, u64 key, double &bd, u64 &bk) {
+    if (delta < 0.0 && better(delta, key, bd, bk)) { bd = delta; bk = key; }
+}
+
+// The move (f, L, a, o) -- segment of L nodes from f, between a and succ a, o = 1: reversed -- as a key, node ids not positions.
+struct OrMove {
+    int f, L, a, o;
+};
+__device__ __forceinline__ u64 or_key(int f, int L, int a, int o, int n) {
+    return (u64)((((long long)f * 3 + (L - 1)) * n + a) * 2 + o);
+}
+__device__ __forceinline__ OrMove or_unkey(u64 key, int n) {
+    const u64 t = key >> 1;
+    const int fl = (int)(t / (u64)n);
+    return OrMove{fl / 3, fl % 3 + 1, (int)(t % (u64)n), (int)(key & 1)};
+}
 
 // Segment x[0 .. L-1] at positions i .. i+L-1 goes between position ja and ja + 1 (o = 1: reversed): order/pos shift the
 // shorter arc between the segment and the insertion point by L and take the segment in its orientation.  Called by every

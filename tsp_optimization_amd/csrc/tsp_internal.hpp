@@ -1,6 +1,7 @@
 // tsp_internal.hpp -- data laid out in HBM and the opaque handle types behind include/tsp_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <time.h>
 
 #include <cstdint>
 #include <cstdio>
@@ -262,6 +263,8 @@ struct HkTree {
 }
 int tsp_hk_tree(tsp_dev_inst *inst, const double *pi, tsp::HkTree *out, tsp_lb_stats *stats);   // held_karp.hip
 int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr);                                  // nl_opt.hip: takes d_nbr over
+tsp_dev_tours *tsp_scratch_tours(tsp_dev_inst *inst, int B, bool *owned, int *rc);             // api.hip
+int tsp_grid_tour_cost(tsp_dev_tours *t, double *d_out);                                        // two_opt_grid.hip
 
 // Per-instance scratch for the host-array entry points (not for concurrent use, like every handle): >= bytes, 256-aligned.
 void *tsp_io_pool(tsp_dev_inst *inst, size_t bytes);
@@ -274,3 +277,18 @@ void *tsp_io_pool(tsp_dev_inst *inst, size_t bytes);
             return TSP_DEV_E_HIP;                                            \
         }                                                                    \
     } while (0)
+
+namespace tsp {
+// the host's monotonic clock, in seconds
+inline double wall_s() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+}  // namespace tsp
+
+// The instance's reusable pair of timing events, created on first use.
+inline int tsp_inst_events(tsp_dev_inst *inst) {
+    if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
+    return TSP_OK;
+}

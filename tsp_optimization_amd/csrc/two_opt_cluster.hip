@@ -32,7 +32,6 @@
 #include "two_opt_common.hpp"
 
 #include <algorithm>
-#include <time.h>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -1777,12 +1776,6 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
 using namespace tsp;
 
 namespace {
-double wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 // LDS one workgroup may have: what the device grants (160 KiB on gfx950)
 size_t cl_lds_limit(const tsp_dev_ctx *ctx) { return ctx->lds_bytes > 0 ? (size_t)ctx->lds_bytes : (size_t)64 * 1024; }
 

@@ -34,7 +34,6 @@
 #include "two_opt_tiled.hpp"
 
 #include <algorithm>
-#include <time.h>
 
 #pragma clang fp contract(off)
 namespace tsp {
@@ -417,12 +416,6 @@ void launch_tour_cost(tsp_dev_tours *t, double *d_out, size_t stride_bytes) {
     });
 }
 
-double wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 
 }  // namespace
 
@@ -508,7 +501,6 @@ int tsp_grid_after_external_run(tsp_dev_tours *t, int mode, int timed_out, bool 
     return TSP_OK;
 }
 
-tsp_dev_tours *tsp_scratch_tours(tsp_dev_inst *inst, int B, bool *owned, int *rc);   // api.hip
 // two_opt_cluster.hip
 int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double time_limit_s, int *all_done, int *fell_through,
                     tsp_dev_tabu *tabu, int iter, int tenure);

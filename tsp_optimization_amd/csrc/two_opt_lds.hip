@@ -14,7 +14,6 @@
 #include "two_opt_common.hpp"
 
 #include <algorithm>
-#include <time.h>
 
 #pragma clang fp contract(off)
 
@@ -632,12 +631,6 @@ __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__re
 using namespace tsp;
 
 namespace {
-double wall_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 template <int WT, bool INT, int MODE, bool CACHE, bool F32>
 hipError_t launch_lds_k(tsp_dev_tours *t, int rmin, int rmax, int max_iters) {
     hipStream_t s = t->inst->ctx->stream;
