@@ -417,6 +417,51 @@ typedef struct {
 int tsp_dev_nl_3opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride,
                     double *obj, int64_t max_moves, double time_limit_s, tsp_nl3_opt_stats *stats);
 
+/* ---- iterated local search (extension): double-bridge kicks and the list descent above, B independent chains ----------------
+ * (DESIGN.md 4.15 has the kernels.)  All integer arithmetic below is unsigned and mod 2^64.
+ * Random stream.  Counter based: no state, and libc's random() is not touched.
+ *     mix(x):  x += 0x9E3779B97F4A7C15;  z = x;  z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;  z = (z ^ z>>27) * 0x94D049BB133111EB;
+ *              return z ^ z>>31                                                              (the splitmix64 step)
+ * The draws of chain b at iteration it are  u_j = mix(mix(mix(seed ^ (b * 0x100000001B3)) + it) + j),  j = 0 .. 4.  They are
+ * reduced with plain %: the modulo bias (below n / 2^64) is accepted.
+ * Kick(it, span), n >= 8.  W = n when span <= 0, else min(span, n); a span of 1 .. 7 is TSP_DEV_E_ARG.  s = u_0 % n,
+ * seq[0] = s, seq[k+1] = succ seq[k];
+ *     o1 = 1 + u_1 % (W - 3),  o2 = o1 + 1 + u_2 % (W - 2 - o1),  o3 = o2 + 1 + u_3 % (W - 1 - o2),  o4 = o3 + 1 + u_4 % (W - o3),
+ * so 1 <= o1 < o2 < o3 < o4 <= W.  With P = seq[0:o1], Bk = seq[o1:o2], Ck = seq[o2:o3], Dk = seq[o3:o4], R = seq[o4:n] (may be
+ * empty) the new tour is P Dk Ck Bk R, every block in its old direction, closed back to seq[0]: exactly four successors change,
+ * those of the last nodes of P, Bk, Ck and Dk (the double bridge; A C B D over three cuts is a 3-opt move of type 0 and is not
+ * meant).  As undirected edges that is four out and four in, less one for every two single-node blocks that are neighbours on
+ * the cycle (R P), Bk, Ck, Dk.  All of it lies within W nodes of s.
+ * Chain b, given iterations I >= 0 and a cap M of moves per descent (M < 0: none):
+ *   1. the tsp_dev_nl_3opt descent of the caller's tour b over `kinds`, ended after M moves: the incumbent;
+ *   2. c* = the incumbent's recomputed cost (the sum over nodes in node order that every obj of this section is);
+ *   3. for it = 0 .. I-1: work = kick(incumbent); the descent of work as in 1; c = its recomputed cost; work becomes the
+ *      incumbent, and c* = c, iff c < c*;
+ *   4. the incumbent and c* are returned: never a tour in the middle of a descent.
+ * n < 8 has no kick: the call is step 1 alone and reports iterations = 0.
+ * Time limit.  TSP_TIME_LIMIT_EXCEEDED; the unfinished iteration is discarded and stats.iterations counts the completed ones, so
+ * a call without a limit and with iterations = that count returns the same tour and cost.  Until step 1 has ended the incumbent
+ * is the caller's tour, and that is what a limit so short returns (start_cost = its cost).  The counters of the discarded
+ * descent stay in the sums. */
+typedef struct {
+    int64_t decisions, moves, moves_2opt, moves_oropt, moves_by_len[3], moves_reversed, reversed, deltas_executed;
+    double seconds, device_ms;
+    int64_t moves_3opt, moves_by_type[4]; /* tsp_nl3_opt_stats, in its layout: the sums over all descents of the chain          */
+    int64_t iterations;    /* completed iterations (kick, descent, accept or reject)                                           */
+    int64_t accepted;      /* ... whose tour became the incumbent                                                              */
+    int64_t last_improved; /* the last of those, or -1                                                                         */
+    double start_cost;     /* c* after step 1                                                                                  */
+} tsp_ils_stats;
+/* B chains, chain b from tour b with stream b.  kinds, the lists and the default lists as tsp_dev_nl_3opt.  obj[B] out: c*.
+ * Bad arguments (also iterations < 0, a span of 1 .. 7): TSP_DEV_E_ARG, and the caller's tours are untouched. */
+int tsp_dev_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                uint64_t seed, int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s,
+                tsp_ils_stats *stats);
+/* The kick of iteration `it` (>= 0) of chain b applied to tour b, b = 0 .. B-1, and nothing else: the perturbation for a
+ * caller's own loop.  n < 8, it < 0 or a span of 1 .. 7: TSP_DEV_E_ARG. */
+int tsp_dev_ils_kick(tsp_dev_inst *inst, int B, int *succ, int succ_stride, int64_t tour_stride, uint64_t seed, int64_t it,
+                     int span);
+
 /* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
  * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
  * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.

@@ -150,6 +150,17 @@ int alg_3opt(instance *inst);         /* 2-opt + Or-opt + 3-opt on inst->solutio
 /* The library still exports no HEU_3opt, the name the reference declares and never defines (tests/test_cpu_or_opt.py holds
  * that): HEU_greedy followed by alg_3opt is that heuristic. */
 
+/* ---- iterated local search (extension; include/tsp_hip.h, tsp_dev_ils).  Library entry points only: no solver_type, no
+ * -method row.  iterations >= 0 (default 100), span 0 or >= 8 (default 50), chains >= 1 (default 1); else TSP_DEV_E_ARG and the
+ * settings stay. */
+int tsp_host_set_ils(int iterations, int span, int chains);
+int alg_ils(instance *inst);          /* tsp_dev_ils from inst->solution: all three kinds over the lists tsp_host_set_knn /
+                                         tsp_host_set_alpha select, seed = params.seed (as unsigned), params.time_limit when
+                                         > 0, no cap on the moves of a descent; `chains` chains start from the one tour with
+                                         streams 0 .. chains-1 and the cheapest is kept, ties -> the lower chain; obj_best
+                                         receives its recomputed cost                                                        */
+int HEU_ils_greedy(instance *inst);   /* HEU_greedy + alg_ils */
+
 /* ---- Held-Karp lower bound (extension; include/tsp_hip.h, tsp_dev_held_karp).  A library entry point only: no solver_type,
  * no -method row.  Runs the ascent on the instance's device handle from zero penalties with TSP_HK_DEFAULT_LAMBDA and the
  * default patience; ub = the cost of any tour (inst->solution.obj_best after a heuristic), max_iters <= 0 =
@@ -263,6 +274,8 @@ void tsp_host_last_or_stats(tsp_or_opt_stats *out);
 void tsp_host_last_nl_stats(tsp_nl_opt_stats *out);
 /* Counters of the last alg_3opt call of this thread. */
 void tsp_host_last_nl3_stats(tsp_nl3_opt_stats *out);
+/* Counters of the winning chain of the last alg_ils call of this thread. */
+void tsp_host_last_ils_stats(tsp_ils_stats *out);
 /* Counters of the last tsp_host_lower_bound call of this thread. */
 void tsp_host_last_lb_stats(tsp_lb_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */

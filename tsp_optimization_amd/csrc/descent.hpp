@@ -8,6 +8,18 @@
 
 namespace tsp {
 
+// What a driver adds to Descent::run when a tour is not finished at its first `done` (ils.hip).  DescentPlain: nothing.
+//   init(z, b)      the start of control block b, behind run's own
+//   fetch(s)        queues the copies of the driver's own state that a poll needs, behind run's copy of the control blocks
+//   finished(z, b)  after a poll: tour b needs no more decisions
+//   finish(status)  queued behind the last decision, ahead of the recomputed costs and the download
+struct DescentPlain {
+    template <typename State> void init(State &, int) const {}
+    int fetch(hipStream_t) const { return TSP_OK; }
+    template <typename State> bool finished(const State &z, int) const { return z.done; }
+    int finish(int) const { return TSP_OK; }
+};
+
 // open(): the scratch tours handle of the instance with the caller's tours on it.  run(): the decisions, the cost of the final
 // tours and the way back to the caller's arrays.  Between the two the caller sees to its own buffers (and lists).
 struct Descent {
@@ -37,6 +49,12 @@ struct Descent {
     template <typename State, typename Queue>
     int run(State *d_st, State *h_st, double *d_cost, bool trivial, int batch_cap, int64_t max_moves, double time_limit_s,
             Queue queue) {
+        return run(d_st, h_st, d_cost, trivial, batch_cap, max_moves, time_limit_s, queue, DescentPlain{});
+    }
+
+    template <typename State, typename Queue, typename Hooks>
+    int run(State *d_st, State *h_st, double *d_cost, bool trivial, int batch_cap, int64_t max_moves, double time_limit_s,
+            Queue queue, Hooks hooks) {
         tsp_dev_inst *inst = t->inst;
         hipStream_t s = inst->ctx->stream;
         const int B = t->B;
@@ -45,6 +63,7 @@ struct Descent {
             memset(&z, 0, sizeof z);
             z.max_moves = max_moves < 0 ? -1 : max_moves;
             z.done = trivial ? 1 : 0;
+            hooks.init(z, b);
             h_st[b] = z;
         }
         TSP_HIP_TRY(hipMemcpyAsync(d_st, h_st, sizeof(State) * B, hipMemcpyHostToDevice, s));
@@ -57,10 +76,11 @@ struct Descent {
             int batch = 4, queued = 1;
             for (;;) {
                 TSP_HIP_TRY(hipMemcpyAsync(h_st, d_st, sizeof(State) * B, hipMemcpyDeviceToHost, s));
+                if (int e = hooks.fetch(s)) return e;
                 TSP_HIP_TRY(hipStreamSynchronize(s));
                 TSP_HIP_TRY(hipGetLastError());
                 bool all = true;
-                for (int b = 0; b < B; ++b) all = all && h_st[b].done;
+                for (int b = 0; b < B; ++b) all = all && hooks.finished(h_st[b], b);
                 if (all) break;
                 const double now = wall_s();
                 if (time_limit_s > 0 && now - t0 > time_limit_s) { status = TSP_TIME_LIMIT_EXCEEDED; break; }
@@ -78,6 +98,7 @@ struct Descent {
                 batch = std::min(batch * 2, batch_cap);
             }
         }
+        if (int e = hooks.finish(status)) return e;
         if (int e = tsp_grid_tour_cost(t, d_cost)) return e;
         TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
         TSP_HIP_TRY(hipEventSynchronize(inst->ev1));

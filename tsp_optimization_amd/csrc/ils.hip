@@ -1,0 +1,224 @@
+// ils.hip -- iterated local search over the list descent (tsp_dev_ils, tsp_dev_ils_kick).  The definitions are in
+// include/tsp_hip.h.
+//
+// Decision the four launches of nl_opt.hip / nl3_opt.hip (k_nl_prep, k_nl_scan, k_nl3_scan, k_nl_pick_apply) -> k_ils_step (one
+//          workgroup per chain; it returns at once unless the chain's descent has just ended: then the cost of the work tour,
+//          work -> incumbent or back, the next kick on order/pos and the descent re-armed, or the chain marked finished).
+// The work tours are the instance's scratch tours handle, the incumbents a second order/pos per chain.  An iteration moves
+// nothing to the host, which queues decisions and polls both control blocks as it does for a single descent.
+#include "descent.hpp"
+#include "nl_common.hpp"
+
+#include <cstddef>
+
+#pragma clang fp contract(off)
+
+using namespace tsp;
+
+namespace {
+
+__host__ __device__ __forceinline__ u64 ils_mix(u64 x) {
+    x += 0x9E3779B97F4A7C15ull;
+    u64 z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// The kick of iteration `it` of chain b on order/pos (n >= 8, W >= 8), by every thread of the one workgroup (NT threads) that
+// owns the tour, behind a barrier that follows the last write of the tour.  Positions pos[s] + o1 .. pos[s] + o4 - 1 hold
+// Bk Ck Dk; reversed as one path they hold Dk' Ck' Bk', and each block reversed again leaves Dk Ck Bk.
+template <int NT>
+__device__ __forceinline__ void ils_kick(int *__restrict__ order, int *__restrict__ pos, int n, int W, u64 seed, int b,
+                                         long long it) {
+    const u64 base = ils_mix(ils_mix(seed ^ ((u64)b * 0x100000001B3ull)) + (u64)it);
+    const int s = (int)(ils_mix(base) % (u64)n);
+    const int o1 = 1 + (int)(ils_mix(base + 1) % (u64)(W - 3));
+    const int o2 = o1 + 1 + (int)(ils_mix(base + 2) % (u64)(W - 2 - o1));
+    const int o3 = o2 + 1 + (int)(ils_mix(base + 3) % (u64)(W - 1 - o2));
+    const int o4 = o3 + 1 + (int)(ils_mix(base + 4) % (u64)(W - o3));
+    const int at = or_wrap(pos[s] + o1, n);   // position pos[s] is outside the window: no reversal moves s
+    const int lB = o2 - o1, lC = o3 - o2, lD = o4 - o3;
+    nl_reverse_path<NT>(order, pos, n, at, lB + lC + lD);
+    __syncthreads();
+    nl_reverse_path<NT>(order, pos, n, at, lD);
+    nl_reverse_path<NT>(order, pos, n, or_wrap(at + lD, n), lC);
+    nl_reverse_path<NT>(order, pos, n, or_wrap(at + lD + lC, n), lB);
+}
+
+__global__ __launch_bounds__(kNlPickThreads) void k_ils_kick(int *__restrict__ orders, int *__restrict__ poss, int n, int W,
+                                                             u64 seed, long long it) {
+    const int b = blockIdx.x;
+    ils_kick<kNlPickThreads>(orders + (size_t)b * n, poss + (size_t)b * n, n, W, seed, b, it);
+}
+
+// One workgroup per chain, behind every decision.  inc: the incumbents, B x n of order, then B x n of pos.
+template <int WT, bool INT>
+__global__ __launch_bounds__(kNlPickThreads) void k_ils_step(const double2 *__restrict__ coord, int *__restrict__ orders,
+                                                             int *__restrict__ poss, int *__restrict__ inc,
+                                                             NlState *__restrict__ st, IlsState *__restrict__ ils, int n, int W,
+                                                             u64 seed, long long iterations, long long M) {
+    constexpr int NT = kNlPickThreads;
+    const int b = blockIdx.x;
+    NlState &S = st[b];
+    IlsState &I = ils[b];
+    if (I.finished || !S.done) return;
+    __shared__ double s_d[NT / 64];
+    __shared__ double s_chunk[(INT || WT == WT_CEIL_2D) ? 1 : 4096];
+    const int tid = threadIdx.x;
+    int *order = orders + (size_t)b * n, *pos = poss + (size_t)b * n;
+    int *iorder = inc + (size_t)b * n, *ipos = iorder + (size_t)gridDim.x * n;
+    const long long it = I.it;          // the iteration whose descent has ended; -1: the first descent
+    const double best = I.cost;
+    const double c = tour_cost_block<WT, INT>(coord, order, pos, n, s_d, s_chunk);
+    const bool accept = it < 0 || c < best;
+    __syncthreads();   // every thread has read the chain's state
+    if (accept)
+        for (int p = tid; p < n; p += NT) { iorder[p] = order[p]; ipos[p] = pos[p]; }
+    else
+        for (int p = tid; p < n; p += NT) { order[p] = iorder[p]; pos[p] = ipos[p]; }
+    const long long next = it + 1;      // iterations completed, and the iteration that starts now
+    if (tid == 0) {
+        if (it < 0) I.start_cost = c;
+        else if (accept) { I.accepted += 1; I.last_improved = it; }
+        if (accept) I.cost = c;
+        I.it = next;
+        if (next >= iterations) I.finished = 1;
+    }
+    if (next >= iterations) return;     // the work tour is the incumbent
+    __syncthreads();
+    ils_kick<NT>(order, pos, n, W, seed, b, next);
+    if (tid == 0) {
+        S.done = M == 0 ? 1 : 0;
+        S.max_moves = M < 0 ? -1 : S.moves + M;
+    }
+}
+
+// the stats record of a chain from its two control blocks
+void fill_stats(tsp_ils_stats &o, const NlState &z, const IlsState &q, double seconds, float device_ms) {
+    memset(&o, 0, sizeof o);
+    o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
+    for (int k = 0; k < 3; ++k) o.moves_by_len[k] = z.moves_len[k];
+    o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
+    o.seconds = seconds; o.device_ms = device_ms;
+    o.moves_3opt = z.moves_3opt;
+    for (int k = 0; k < 4; ++k) o.moves_by_type[k] = z.moves_type[k];
+    o.iterations = q.it < 0 ? 0 : q.it; o.accepted = q.accepted; o.last_improved = q.last_improved;
+    o.start_cost = q.start_cost;
+}
+
+// What Descent::run needs to know of a chain beyond its NlState.
+struct IlsHooks {
+    tsp_dev_tours *t;
+    NlData *x;
+    long long M;
+    void init(NlState &z, int) const { z.done = M == 0 ? 1 : 0; }
+    int fetch(hipStream_t s) const {
+        TSP_HIP_TRY(hipMemcpyAsync(x->h_ils, x->d_ils, sizeof(IlsState) * t->B, hipMemcpyDeviceToHost, s));
+        return TSP_OK;
+    }
+    bool finished(const NlState &, int b) const { return x->h_ils[b].finished; }
+    // at the time limit the work tours are in the middle of an iteration: the incumbents are what the call returns
+    int finish(int status) const {
+        hipStream_t s = t->inst->ctx->stream;
+        const size_t Bn = (size_t)t->B * t->n;
+        if (status == TSP_TIME_LIMIT_EXCEEDED) {
+            TSP_HIP_TRY(hipMemcpyAsync(t->d_order, x->d_inc, sizeof(int) * Bn, hipMemcpyDeviceToDevice, s));
+            TSP_HIP_TRY(hipMemcpyAsync(t->d_pos, x->d_inc + Bn, sizeof(int) * Bn, hipMemcpyDeviceToDevice, s));
+        }
+        return fetch(s);
+    }
+};
+
+bool bad_span(int span) { return span >= 1 && span <= 7; }
+
+}  // namespace
+
+static_assert(offsetof(tsp_ils_stats, iterations) == sizeof(tsp_nl3_opt_stats), "tsp_ils_stats starts as tsp_nl3_opt_stats");
+
+extern "C" {
+
+int tsp_dev_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj, uint64_t seed,
+                int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, tsp_ils_stats *stats) {
+    const int allowed = TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT;
+    const int asked = kinds;
+    int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
+    if (rc) return rc;
+    if (iterations < 0 || bad_span(span)) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    const long long M = max_moves_per_descent < 0 ? -1 : max_moves_per_descent;
+    if (n < 8) {   // no kick: the descent alone
+        const NlState *z = nullptr;
+        std::vector<tsp_nl3_opt_stats> st3((size_t)B);
+        const int status = tsp_nl_run(inst, asked, allowed, B, succ, succ_stride, tour_stride, obj, M, time_limit_s,
+                                      st3.data(), sizeof(tsp_nl3_opt_stats), &z);
+        if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
+        for (int b = 0; b < B && stats; ++b) {
+            IlsState q;
+            memset(&q, 0, sizeof q);
+            q.last_improved = -1; q.cost = q.start_cost = obj[b];
+            fill_stats(stats[b], z[b], q, st3[b].seconds, (float)st3[b].device_ms);
+        }
+        return status;
+    }
+    Descent run;
+    rc = run.open(inst, B, succ, succ_stride, tour_stride, obj);
+    if (rc) return rc;
+    NlData *x = nullptr;
+    rc = tsp_nl_prepare(inst, B, &x);
+    if (rc) return rc;
+    hipStream_t s = inst->ctx->stream;
+    const size_t Bn = (size_t)B * n;
+    if (!x->d_inc) {
+        TSP_HIP_TRY(hipMalloc(&x->d_inc, sizeof(int) * 2 * Bn));
+        TSP_HIP_TRY(hipMalloc(&x->d_ils, sizeof(IlsState) * B));
+        TSP_HIP_TRY(hipHostMalloc(&x->h_ils, sizeof(IlsState) * B, hipHostMallocDefault));
+    }
+    // the incumbents start as the caller's tours, the chains in their first descent
+    tsp_dev_tours *t = run.t;
+    for (int b = 0; b < B; ++b) {
+        IlsState q;
+        memset(&q, 0, sizeof q);
+        q.it = -1; q.last_improved = -1;
+        x->h_ils[b] = q;
+    }
+    TSP_HIP_TRY(hipMemcpyAsync(x->d_inc, t->d_order, sizeof(int) * Bn, hipMemcpyDeviceToDevice, s));
+    TSP_HIP_TRY(hipMemcpyAsync(x->d_inc + Bn, t->d_pos, sizeof(int) * Bn, hipMemcpyDeviceToDevice, s));
+    TSP_HIP_TRY(hipMemcpyAsync(x->d_ils, x->h_ils, sizeof(IlsState) * B, hipMemcpyHostToDevice, s));
+    const int W = span <= 0 ? n : std::min(span, n);
+    const IlsHooks hooks{t, x, M};
+    const int status = run.run(x->d_st, x->h_st, x->d_cost, false, 256, M, time_limit_s,
+                               [&](bool) {
+                                   tsp_nl_launch_decision(t, x, kinds);
+                                   TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
+                                       hipLaunchKernelGGL((k_ils_step<WTC, INTC>), dim3(B), dim3(kNlPickThreads), 0, s, inst->d_coord,
+                                                          t->d_order, t->d_pos, x->d_inc, x->d_st, x->d_ils, n, W, (u64)seed,
+                                                          (long long)iterations, M);
+                                   });
+                               },
+                               hooks);
+    if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
+    for (int b = 0; b < B && stats; ++b) {
+        fill_stats(stats[b], x->h_st[b], x->h_ils[b], wall_s() - run.t0, run.device_ms);
+        if (x->h_ils[b].it < 0) stats[b].start_cost = obj[b];   // the limit ended the first descent: the caller's tour
+    }
+    return status;
+}
+
+int tsp_dev_ils_kick(tsp_dev_inst *inst, int B, int *succ, int succ_stride, int64_t tour_stride, uint64_t seed, int64_t it,
+                     int span) {
+    if (!inst || !succ || B < 1 || succ_stride < 1 || it < 0 || bad_span(span) || inst->n < 8) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
+    std::vector<double> obj((size_t)B, 0.0);
+    Descent run;
+    int rc = run.open(inst, B, succ, succ_stride, tour_stride, obj.data());
+    if (rc) return rc;
+    tsp_dev_tours *t = run.t;
+    hipLaunchKernelGGL(k_ils_kick, dim3(B), dim3(kNlPickThreads), 0, inst->ctx->stream, t->d_order, t->d_pos, n,
+                       span <= 0 ? n : std::min(span, n), (u64)seed, (long long)it);
+    TSP_HIP_TRY(hipGetLastError());
+    return tsp_dev_tours_download(t, succ, succ_stride, tour_stride, nullptr, nullptr);   // (synchronises)
+}
+
+}  // extern "C"

@@ -27,6 +27,14 @@ struct alignas(16) NlState {
     int done, pad;
 };
 
+// Per-chain state of the iterated local search (ils.hip), written by thread 0 of k_ils_step.
+struct alignas(16) IlsState {
+    long long it;              // iterations completed; -1 until the first descent has ended
+    long long accepted, last_improved;
+    double cost, start_cost;   // of the incumbent; after the first descent
+    int finished, pad;
+};
+
 __device__ __forceinline__ int ahead(int px, int from, int n) {   // px - from mod n
     const int g = px - from;
     return g < 0 ? g + n : g;
@@ -61,10 +69,15 @@ struct NlData {
     NlState *h_st = nullptr;   // pinned
     double *d_E = nullptr, *d_rem = nullptr, *d_cost = nullptr;
     NlBest *d_part = nullptr;  // B x nparts of k_nl_scan, then B x nparts of k_nl3_scan
+    // ils.hip, allocated by its first call at this B: the incumbents' order and pos (B x n each) and the chains' states
+    int *d_inc = nullptr;
+    IlsState *d_ils = nullptr;
+    IlsState *h_ils = nullptr; // pinned
     void free_scratch() {
         (void)hipFree(d_st); (void)hipHostFree(h_st); (void)hipFree(d_E); (void)hipFree(d_rem); (void)hipFree(d_cost);
-        (void)hipFree(d_part);
+        (void)hipFree(d_part); (void)hipFree(d_inc); (void)hipFree(d_ils); (void)hipHostFree(h_ils);
         d_st = nullptr; h_st = nullptr; d_E = d_rem = d_cost = nullptr; d_part = nullptr; B = 0;
+        d_inc = nullptr; d_ils = nullptr; h_ils = nullptr;
     }
     ~NlData() { free_scratch(); (void)hipFree(d_nbr); }
 };
@@ -73,6 +86,13 @@ struct NlData {
 
 // nl3_opt.hip: k_nl3_scan of every tour that is not done, one candidate per workgroup in parts3 (B x nparts)
 void tsp_nl3_launch_scan(tsp_dev_tours *t, tsp::NlData *x, tsp::NlBest *parts3);
+// nl_opt.hip: the argument checks of a list descent; *kinds loses the kinds without a move at the instance's size
+int tsp_nl_check(const tsp_dev_inst *inst, int *kinds, int allowed, int B, const int *succ, int succ_stride, int64_t tour_stride,
+                 const double *obj);
+// nl_opt.hip: the instance's lists (the default lists when it has none) and the scratch of B tours -> *x
+int tsp_nl_prepare(tsp_dev_inst *inst, int B, tsp::NlData **x);
+// nl_opt.hip: one whole decision of every tour that is not done, queued on the engine's stream
+void tsp_nl_launch_decision(tsp_dev_tours *t, tsp::NlData *x, int kinds);
 // nl_opt.hip: what both entry points do.  `allowed` is the kinds mask the entry point takes.  stats (may be NULL): B records
 // `stats_stride` bytes apart that start with the layout of tsp_nl_opt_stats; that part of each is filled here.  With TSP_OK or
 // TSP_TIME_LIMIT_EXCEEDED *states (unless NULL) are the B final states, for what the caller's records hold beyond it.

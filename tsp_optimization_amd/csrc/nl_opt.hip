@@ -308,9 +308,25 @@ int scratch_alloc(NlData *x, int B, int n, int K) {
     return TSP_OK;
 }
 
+bool bad_k(const tsp_dev_inst *inst, int K) { return K < 1 || K > TSP_NL_MAX_K || K > inst->n - 1; }
+
+}  // namespace
+
+void tsp_nl_data_free(void *p) { delete static_cast<NlData *>(p); }
+
+// Lists built elsewhere on the device (alpha.hip) become the handle's lists; nothing queued may still read the old ones.
+int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr) {
+    TSP_HIP_TRY(hipStreamSynchronize(inst->ctx->stream));
+    NlData *x = nl_data(inst);
+    (void)hipFree(x->d_nbr);
+    x->d_nbr = d_nbr;
+    x->K = K;
+    return TSP_OK;
+}
+
 // One whole decision of every tour that is not done, queued on the engine's stream: k_nl_prep, k_nl_scan when kinds has one of
 // its two (candidates in the first B x nparts entries of d_part), k_nl3_scan when it has the third (in the second), the pick.
-void launch_decision(tsp_dev_tours *t, NlData *x, int kinds) {
+void tsp_nl_launch_decision(tsp_dev_tours *t, NlData *x, int kinds) {
     tsp_dev_inst *inst = t->inst;
     hipStream_t s = inst->ctx->stream;
     const int n = t->n, B = t->B;
@@ -328,47 +344,47 @@ void launch_decision(tsp_dev_tours *t, NlData *x, int kinds) {
                        low ? x->d_part : nullptr, three ? parts3 : nullptr);
 }
 
-bool bad_k(const tsp_dev_inst *inst, int K) { return K < 1 || K > TSP_NL_MAX_K || K > inst->n - 1; }
+int tsp_nl_check(const tsp_dev_inst *inst, int *kinds, int allowed, int B, const int *succ, int succ_stride, int64_t tour_stride,
+                 const double *obj) {
+    if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
+    if (*kinds < 1 || (*kinds & ~allowed)) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    if ((*kinds & TSP_NL_3OPT) && n > kNlMaxN3) return TSP_DEV_E_ARG;
+    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
+    // a kind without any move at this size is left out: 2-opt needs four nodes, Or-opt and 3-opt five
+    if (n < 4) *kinds &= ~TSP_NL_2OPT;
+    if (n < 5) *kinds &= ~(TSP_NL_OROPT | TSP_NL_3OPT);
+    return TSP_OK;
+}
 
-}  // namespace
-
-void tsp_nl_data_free(void *p) { delete static_cast<NlData *>(p); }
-
-// Lists built elsewhere on the device (alpha.hip) become the handle's lists; nothing queued may still read the old ones.
-int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr) {
-    TSP_HIP_TRY(hipStreamSynchronize(inst->ctx->stream));
+int tsp_nl_prepare(tsp_dev_inst *inst, int B, NlData **out) {
+    const int n = inst->n;
     NlData *x = nl_data(inst);
-    (void)hipFree(x->d_nbr);
-    x->d_nbr = d_nbr;
-    x->K = K;
+    if (x->K == 0) {
+        const int rc = tsp_dev_inst_knn_build(inst, std::min(TSP_NL_DEFAULT_K, n - 1), nullptr);
+        if (rc) return rc;
+    }
+    if (x->B != B || x->parts_K != x->K) {
+        const int rc = scratch_alloc(x, B, n, x->K);
+        if (rc) { x->free_scratch(); return rc; }
+    }
+    *out = x;
     return TSP_OK;
 }
 
 int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
                int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const NlState **states) {
-    if (!inst || !succ || !obj || B < 1 || succ_stride < 1) return TSP_DEV_E_ARG;
-    if (kinds < 1 || (kinds & ~allowed)) return TSP_DEV_E_ARG;
-    const int n = inst->n;
-    if ((kinds & TSP_NL_3OPT) && n > kNlMaxN3) return TSP_DEV_E_ARG;
-    if (B > 1 && tour_stride < (int64_t)n * succ_stride) return TSP_DEV_E_ARG;
-    // a kind without any move at this size is left out: 2-opt needs four nodes, Or-opt and 3-opt five
-    if (n < 4) kinds &= ~TSP_NL_2OPT;
-    if (n < 5) kinds &= ~(TSP_NL_OROPT | TSP_NL_3OPT);
-    Descent run;
-    int rc = run.open(inst, B, succ, succ_stride, tour_stride, obj);
+    int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
-    NlData *x = nl_data(inst);
-    if (x->K == 0) {
-        rc = tsp_dev_inst_knn_build(inst, std::min(TSP_NL_DEFAULT_K, n - 1), nullptr);
-        if (rc) return rc;
-    }
-    if (x->B != B || x->parts_K != x->K) {
-        rc = scratch_alloc(x, B, n, x->K);
-        if (rc) { x->free_scratch(); return rc; }
-    }
+    Descent run;
+    rc = run.open(inst, B, succ, succ_stride, tour_stride, obj);
+    if (rc) return rc;
+    NlData *x = nullptr;
+    rc = tsp_nl_prepare(inst, B, &x);
+    if (rc) return rc;
     const bool trivial = kinds == 0 || max_moves == 0;
     const int status = run.run(x->d_st, x->h_st, x->d_cost, trivial, 256, max_moves, time_limit_s,
-                               [&](bool) { launch_decision(run.t, x, kinds); });
+                               [&](bool) { tsp_nl_launch_decision(run.t, x, kinds); });
     if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
     for (int b = 0; b < B && stats; ++b) {
         const NlState &z = x->h_st[b];

@@ -199,4 +199,34 @@ __device__ __forceinline__ double pair_delta_approx(const NodeRec &a, const Node
     return approx_root_dist<WT>(a.x, a.y, b.x, b.y) + approx_root_dist<WT>(a.xs, a.ys, b.xs, b.ys) - a.ds - b.ds;
 }
 
+
+// ---- tour cost ----------------------------------------------------------------------------
+// Sum over nodes of d(v, succ v) in node order (tabusearch.c:168-172), by one whole block.
+template <int WT, bool INT>
+__device__ __forceinline__ double tour_cost_block(const double2 *coord, const int *order, const int *pos, int n,
+                                                  double *s_d /*>=16*/, double *s_chunk /*4096 unless INT*/) {
+    const int tid = threadIdx.x;
+    if constexpr (INT || WT == WT_CEIL_2D) {  // integer-valued terms: any order is exact
+        double c = 0.0;
+        for (int v = tid; v < n; v += (int)blockDim.x) c += load_node<WT, INT>(coord, order, pos, n, v).ds;
+        return block_sum<double>(c, s_d);
+    } else {  // same sequential order as the reference, staged through LDS
+        double acc = 0.0;
+        for (int base = 0; base < n; base += 4096) {
+            __syncthreads();
+            for (int t = tid; t < 4096 && base + t < n; t += (int)blockDim.x)
+                s_chunk[t] = load_node<WT, INT>(coord, order, pos, n, base + t).ds;
+            __syncthreads();
+            if (tid == 0) {
+                const int m = min(4096, n - base);
+                for (int t = 0; t < m; ++t) acc += s_chunk[t];
+            }
+        }
+        __syncthreads();
+        if (tid == 0) s_d[0] = acc;
+        __syncthreads();
+        return s_d[0];
+    }
+}
+
 }  // namespace tsp

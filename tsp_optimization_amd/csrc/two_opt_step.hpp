@@ -60,35 +60,7 @@ __device__ __forceinline__ void read_partial(const Partial *slot, double &delta,
 __device__ __forceinline__ int skipped_in_tile_row(int r0, int gx, int TJ) { return min(gx, (r0 + 1) / TJ); }
 
 
-// ---- tour cost ----------------------------------------------------------------------------
-// Sum over nodes of d(v, succ v) in node order (tabusearch.c:168-172), by one whole block.
-template <int WT, bool INT>
-__device__ __forceinline__ double tour_cost_block(const double2 *coord, const int *order, const int *pos, int n,
-                                                  double *s_d /*>=16*/, double *s_chunk /*4096 unless INT*/) {
-    const int tid = threadIdx.x;
-    if constexpr (INT || WT == WT_CEIL_2D) {  // integer-valued terms: any order is exact
-        double c = 0.0;
-        for (int v = tid; v < n; v += (int)blockDim.x) c += load_node<WT, INT>(coord, order, pos, n, v).ds;
-        return block_sum<double>(c, s_d);
-    } else {  // same sequential order as the reference, staged through LDS
-        double acc = 0.0;
-        for (int base = 0; base < n; base += 4096) {
-            __syncthreads();
-            for (int t = tid; t < 4096 && base + t < n; t += (int)blockDim.x)
-                s_chunk[t] = load_node<WT, INT>(coord, order, pos, n, base + t).ds;
-            __syncthreads();
-            if (tid == 0) {
-                const int m = min(4096, n - base);
-                for (int t = 0; t < m; ++t) acc += s_chunk[t];
-            }
-        }
-        __syncthreads();
-        if (tid == 0) s_d[0] = acc;
-        __syncthreads();
-        return s_d[0];
-    }
-}
-
+// ---- tour cost: tour_cost_block of two_opt_common.hpp -------------------------------------
 // out[b] = recomputed cost of tour b (BEST runs that stop early; multi-start "true cost")
 template <int WT, bool INT>
 __global__ __launch_bounds__(kApplyThreads) void k_tour_cost(const double2 *__restrict__ coord,

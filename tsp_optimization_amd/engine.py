@@ -67,6 +67,17 @@ class Nl3OptStats(C.Structure):
         return d
 
 
+class IlsStats(C.Structure):
+    _fields_ = Nl3OptStats._fields_ + [("iterations", C.c_int64), ("accepted", C.c_int64), ("last_improved", C.c_int64),
+                                       ("start_cost", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["moves_by_len"] = list(self.moves_by_len)
+        d["moves_by_type"] = list(self.moves_by_type)
+        return d
+
+
 class LbStats(C.Structure):
     _fields_ = [("iterations", C.c_int64), ("trees", C.c_int64), ("rounds", C.c_int64), ("dists_executed", C.c_int64),
                 ("tour_found", C.c_int), ("lambda_final", C.c_double), ("seconds", C.c_double), ("device_ms", C.c_double)]
@@ -168,6 +179,9 @@ def lib():
         L.tsp_dev_inst_knn_get.argtypes = [vp, ip, ip]
         L.tsp_dev_nl_opt.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double, C.POINTER(NlOptStats)]
         L.tsp_dev_nl_3opt.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double, C.POINTER(Nl3OptStats)]
+        L.tsp_dev_ils.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_uint64, C.c_int64, C.c_int, C.c_int64,
+                                  C.c_double, C.POINTER(IlsStats)]
+        L.tsp_dev_ils_kick.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int64, C.c_uint64, C.c_int64, C.c_int]
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
@@ -193,6 +207,7 @@ EXPORTED = [
     "tsp_dev_multistart_allreduce_f64", "tsp_dev_multistart_allreduce_f64_group",
     "tsp_dev_or_opt", "tsp_dev_two_opt_or_opt",
     "tsp_dev_inst_knn_build", "tsp_dev_inst_knn_set", "tsp_dev_inst_knn_get", "tsp_dev_nl_opt", "tsp_dev_nl_3opt",
+    "tsp_dev_ils", "tsp_dev_ils_kick",
     "tsp_dev_one_tree", "tsp_dev_held_karp",
     "tsp_dev_inst_alpha_build", "tsp_dev_alpha_rows",
 ]
@@ -424,6 +439,33 @@ class Instance:
         if single:
             return rc, succ2[0], float(o[0]), stats[0]
         return rc, succ2, o, stats
+
+    # -- iterated local search (extension) ---------------------------------------------------
+    def ils(self, succ, iterations, seed=0, span=0, kinds=NL_2OPT | NL_OROPT | NL_3OPT, max_moves_per_descent=-1, time_limit=-1.0,
+            obj=None):
+        """Iterated local search (tsp_dev_ils): the list descent of nl_3opt, then `iterations` times a double-bridge kick within
+        `span` nodes (0: the whole tour), the descent again and the better tour kept.  succ [n] or [B,n]: B chains, chain b with
+        random stream b of `seed`.  -> (status, succ', obj' (recomputed cost of the incumbent), stats dict(s)): the nl_3opt
+        counters summed over the chain's descents, iterations, accepted, last_improved, start_cost"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
+        st = (IlsStats * B)()
+        rc = lib().tsp_dev_ils(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations), int(span),
+                               int(max_moves_per_descent), time_limit, st)
+        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
+        stats = [s.as_dict() for s in st]
+        if single:
+            return rc, succ2[0], float(o[0]), stats[0]
+        return rc, succ2, o, stats
+
+    def ils_kick(self, succ, seed, it, span=0):
+        """The kick of iteration `it` of chain b applied to tour b and nothing else (tsp_dev_ils_kick).  succ [n] or [B,n]
+        -> succ'"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        _check(lib().tsp_dev_ils_kick(self._h, B, _i(succ2), 1, n, int(seed) & (2 ** 64 - 1), int(it), int(span)))
+        return succ2[0] if single else succ2
 
     # -- Held-Karp lower bound (extension) ---------------------------------------------------
     def _pi(self, pi):

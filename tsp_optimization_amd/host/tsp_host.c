@@ -140,6 +140,8 @@ static __thread double t_device_ms;
 static __thread tsp_or_opt_stats t_or_stats;   /* the Or-opt phases of the last alg_oropt / alg_2opt_oropt */
 static __thread tsp_nl_opt_stats t_nl_stats;   /* the last alg_nl_opt */
 static __thread tsp_nl3_opt_stats t_nl3_stats; /* the last alg_3opt */
+static __thread tsp_ils_stats t_ils_stats;     /* the winning chain of the last alg_ils */
+static int g_ils_iters = 100, g_ils_span = 50, g_ils_chains = 1;   /* tsp_host_set_ils */
 static int g_knn_k = TSP_NL_DEFAULT_K;         /* list length of alg_nl_opt (tsp_host_set_knn) */
 static int g_alpha_k = 0, g_alpha_iters = 0;   /* alpha lists instead (tsp_host_set_alpha); 0 = nearest-neighbour lists */
 
@@ -601,6 +603,55 @@ int alg_3opt(instance *inst) {
     if (rc == TIME_LIMIT_EXCEEDED) LOG_I("3-opt heuristics time exceeded");
     return rc;
 }
+
+/* ---- iterated local search (extension) ------------------------------------------------------------------- */
+
+int tsp_host_set_ils(int iterations, int span, int chains) {
+    if (iterations < 0 || (span >= 1 && span <= 7) || chains < 1) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_ils_iters = iterations;
+    g_ils_span = span;
+    g_ils_chains = chains;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+void tsp_host_last_ils_stats(tsp_ils_stats *out) {
+    if (out) *out = t_ils_stats;
+}
+
+/* tsp_dev_ils over the lists alg_3opt would use: `chains` chains from inst->solution, the cheapest kept (ties -> lower chain) */
+int alg_ils(instance *inst) {
+    const int n = inst->num_nodes;
+    double obj = inst->solution.obj_best;
+    pthread_mutex_lock(&g_lock);
+    const int B = g_ils_chains;
+    int *succ = (int *)malloc(sizeof(int) * (size_t)B * n);
+    double *objs = (double *)calloc((size_t)B, sizeof *objs);
+    tsp_ils_stats *st = (tsp_ils_stats *)calloc((size_t)B, sizeof *st);
+    if (!succ || !objs || !st) LOG_E("out of memory");
+    for (int b = 0; b < B; b++)
+        for (int v = 0; v < n; v++) succ[(size_t)b * n + v] = inst->solution.edges[v].j;
+    tsp_dev_inst *dev = dev_inst_locked(inst);
+    int rc = lists_locked(inst, dev, obj);
+    if (rc == 0)
+        rc = tsp_dev_ils(dev, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, 1, n, objs, (uint64_t)(unsigned)inst->params.seed,
+                         g_ils_iters, g_ils_span, -1, limit_of(inst), st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_ils", rc);
+    int win = 0;
+    for (int b = 1; b < B; b++)
+        if (objs[b] < objs[win]) win = b;
+    for (int v = 0; v < n; v++) { inst->solution.edges[v].i = v; inst->solution.edges[v].j = succ[(size_t)win * n + v]; }
+    inst->solution.obj_best = objs[win];
+    t_ils_stats = st[win];
+    free(succ); free(objs); free(st);
+    if (rc == TIME_LIMIT_EXCEEDED) LOG_I("iterated local search time exceeded");
+    return rc;
+}
+
+/* construction + alg_ils: the constructive status is overwritten */
+int HEU_ils_greedy(instance *inst) { (void)HEU_greedy(inst); return alg_ils(inst); }
 
 /* 2-opt + Or-opt over the lists of lists_locked */
 int alg_nl_opt(instance *inst) {
