@@ -462,6 +462,60 @@ int tsp_dev_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride
 int tsp_dev_ils_kick(tsp_dev_inst *inst, int B, int *succ, int succ_stride, int64_t tour_stride, uint64_t seed, int64_t it,
                      int span);
 
+/* ---- don't-look bits (extension; Bentley, Johnson & McGeoch, LKH): the list descent and the chains over an active set -------
+ * (DESIGN.md 4.16 has the kernels.)  A new descent rule behind new entry points: it takes other decisions than the full scan
+ * of tsp_dev_nl_3opt, which keeps its trajectory, as does tsp_dev_ils.
+ * Candidates of a node v, cand(v): the moves of the list neighbourhood that v's own list entries (v, u), u = nbr[v][k], generate.
+ *     2-opt:  the moves with a new edge {v, u}: {i, j} = {v, u} or {i1, j1} = {v, u};
+ *     Or-opt: the moves one of whose two attaching edges is {v, u};
+ *     3-opt:  the moves with a removed edge (v, q = succ v) and new edges {v, u} and {q, w}, w in q's stored list.
+ * The union of cand(v) over all v is the neighbourhood of tsp_dev_nl_3opt.  Deltas, keys, the order (delta, kind, key) and the way
+ * a move is applied are those of tsp_dev_nl_3opt.
+ * Decision with active set A (one set per tour).  For v in A, m_v = the best of cand(v), or none; m = the best of all m_v.  Every
+ * decision counts in `decisions`.
+ *   - m.delta < 0: m is applied and A becomes {v in A : m_v.delta < 0} + ends(m), where ends(m) are the tails and heads of the
+ *     edges m removes, in the tour before the move: i, i1, j, j1 (2-opt); pred f, f, l, succ l, a, b (Or-opt); a, a1, b, b1, c, c1
+ *     (3-opt).
+ *   - otherwise, mode TSP_DLB_ON: the descent ends.
+ *   - otherwise, mode TSP_DLB_CLOSE: if A was all of V at this decision's start the descent ends; else A becomes V,
+ *     closing_scans += 1 and the descent goes on.  So a TSP_DLB_CLOSE result is a local optimum of the whole list neighbourhood.
+ * max_moves and the time limit work as in tsp_dev_nl_3opt.
+ * Start.  A = V, or the caller's set: `active`, B x n bytes, non-zero = active, NULL = all.  An empty set is allowed: mode
+ * TSP_DLB_ON then takes one decision and ends, mode TSP_DLB_CLOSE goes to A = V.
+ * Chains.  Step 1 of a chain starts with A = V.  Every kick sets A to exactly the tails and heads of its four removed edges and
+ * clears everything else, also what a descent ended by the cap M left active: with seq the sequence of the kick's definition
+ * before the kick, seq[o1-1], seq[o1], seq[o2-1], seq[o2], seq[o3-1], seq[o3], seq[o4-1], seq[o4 mod n]: at most eight nodes,
+ * fewer when blocks are single nodes.  Accept and reject, the random stream and the time-limit rules are those of tsp_dev_ils.
+ * Mode TSP_DLB_OFF is the full scan: the entry points below then follow tsp_dev_nl_3opt / tsp_dev_ils move for move, ignore
+ * `active` and report active_nodes = closing_scans = 0.  The result does not depend on the order in which a set is stored: two
+ * runs return the same bits. */
+enum { TSP_DLB_OFF = 0, TSP_DLB_ON = 1, TSP_DLB_CLOSE = 2 };
+typedef struct {
+    int64_t decisions, moves, moves_2opt, moves_oropt, moves_by_len[3], moves_reversed, reversed, deltas_executed;
+    double seconds, device_ms;
+    int64_t moves_3opt, moves_by_type[4]; /* tsp_nl3_opt_stats, in its layout                                                   */
+    int64_t active_nodes;   /* sum of |A| at the start of every decision                                                        */
+    int64_t closing_scans;  /* times A was reset to V (mode TSP_DLB_CLOSE)                                                      */
+} tsp_nl_dlb_stats;
+typedef struct {
+    int64_t decisions, moves, moves_2opt, moves_oropt, moves_by_len[3], moves_reversed, reversed, deltas_executed;
+    double seconds, device_ms;
+    int64_t moves_3opt, moves_by_type[4];
+    int64_t iterations, accepted, last_improved;
+    double start_cost;      /* tsp_ils_stats, in its layout                                                                     */
+    int64_t active_nodes;   /* as above, summed over all descents of the chain                                                  */
+    int64_t closing_scans;
+} tsp_ils_dlb_stats;
+/* tsp_dev_nl_3opt under dlb_mode from the set `active`.  A mode that is none of the three: TSP_DEV_E_ARG, and the caller's tours
+ * are untouched. */
+int tsp_dev_nl_3opt_dlb(tsp_dev_inst *inst, int kinds, int dlb_mode, int B, int *succ, int succ_stride, int64_t tour_stride,
+                        double *obj, const unsigned char *active, int64_t max_moves, double time_limit_s,
+                        tsp_nl_dlb_stats *stats);
+/* tsp_dev_ils with every descent under dlb_mode.  A bad mode as above. */
+int tsp_dev_ils_dlb(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                    uint64_t seed, int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s,
+                    int dlb_mode, tsp_ils_dlb_stats *stats);
+
 /* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
  * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
  * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.

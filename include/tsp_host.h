@@ -160,6 +160,10 @@ int alg_ils(instance *inst);          /* tsp_dev_ils from inst->solution: all th
                                          streams 0 .. chains-1 and the cheapest is kept, ties -> the lower chain; obj_best
                                          receives its recomputed cost                                                        */
 int HEU_ils_greedy(instance *inst);   /* HEU_greedy + alg_ils */
+/* Don't-look bits (include/tsp_hip.h, tsp_dev_nl_3opt_dlb / tsp_dev_ils_dlb) for alg_3opt (from every node active), alg_ils and
+ * HEU_ils_greedy: TSP_DLB_OFF (the default: the full scan, as before), TSP_DLB_ON or TSP_DLB_CLOSE; else TSP_DEV_E_ARG and the
+ * setting stays.  No -method row, as for the other extensions. */
+int tsp_host_set_dlb(int mode);
 
 /* ---- Held-Karp lower bound (extension; include/tsp_hip.h, tsp_dev_held_karp).  A library entry point only: no solver_type,
  * no -method row.  Runs the ascent on the instance's device handle from zero penalties with TSP_HK_DEFAULT_LAMBDA and the
@@ -276,6 +280,8 @@ void tsp_host_last_nl_stats(tsp_nl_opt_stats *out);
 void tsp_host_last_nl3_stats(tsp_nl3_opt_stats *out);
 /* Counters of the winning chain of the last alg_ils call of this thread. */
 void tsp_host_last_ils_stats(tsp_ils_stats *out);
+/* active_nodes and closing_scans of the last alg_3opt or alg_ils call of this thread (0 under TSP_DLB_OFF); either may be NULL. */
+void tsp_host_last_dlb_stats(int64_t *active_nodes, int64_t *closing_scans);
 /* Counters of the last tsp_host_lower_bound call of this thread. */
 void tsp_host_last_lb_stats(tsp_lb_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */

@@ -1,0 +1,390 @@
+"""Don't-look bits on the device (tsp_dev_nl_3opt_dlb, tsp_dev_ils_dlb) against the CPU reference of the definition in
+include/tsp_hip.h (tests/dlb_ref.py on top of nl3_opt_ref.py and ils_ref.py): whole descents and chains over metrics, lists,
+kinds, modes and starts, the smallest sizes, active sets whose lanes end inside and beyond a workgroup, several tours with
+different sets in one call, non-integer costs, mode 0, a caller's own set, the time limit, bad arguments, the host library and
+the recorded runs of tests/golden/dlb_runs.json.  Tour, cost and every counter (active_nodes and closing_scans among them;
+deltas_executed left out) must equal the reference's.  Every device call passes a finite time limit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import alpha_ref as AR
+import dlb_ref as DR
+import ils_ref as IR
+import nl_opt_ref as NL
+from helpers import HostInstance, Instance, golden, load_instance, rand_instance, random_tour
+from oracle import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+LIMIT = 300.0      # a descent that does not end is a failure, not a hang
+ILS_STATS = DR.COUNTERS + ("iterations", "accepted", "last_improved", "start_cost")
+# the seeds for which the reference accepts some and rejects some of the 40 iterations (7 unless noted), found with
+# dlb_ref.chain on the CPU; they serve both modes
+SEEDS = {("att48", 0): 8, ("kroA100", 30): 9}
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from tsp_optimization_amd import engine as E
+    assert E.device_count() >= 1, "no HIP device visible: the product path has no CPU fallback"
+    return E
+
+
+@pytest.fixture(scope="module")
+def ctx(eng):
+    c = eng.Context(0)
+    yield c
+    c.close()
+
+
+def _same(dev_succ, dev_obj, dev_st, ref_succ, ref_cost, ref_st, keys=DR.COUNTERS):
+    assert O.is_tour(dev_succ)
+    assert (dev_succ == np.asarray(ref_succ)).all(), "tour differs from the reference"
+    assert dev_obj == ref_cost, (dev_obj, ref_cost)
+    for k in keys:
+        assert dev_st[k] == ref_st[k], (k, dev_st[k], ref_st[k])
+
+
+def _setup(eng, ctx, name, lists="knn", K=5, integer_cost=1):
+    xy, wt = load_instance(name)
+    D = O.dist_matrix(xy, wt, integer_cost)
+    inst = eng.Instance(ctx, xy, wt, integer_cost)
+    if lists == "alpha":
+        nbr = inst.alpha_build(K)
+        nbr = nbr[0] if isinstance(nbr, tuple) else nbr
+    else:
+        inst.knn_build(K)
+        nbr = inst.knn()
+    return xy, wt, D, inst, nbr
+
+
+def _rand(eng, ctx, n, K, hi=10000):
+    xy = rand_instance(n, seed=n, hi=hi)
+    D = O.dist_matrix(xy, O.EUC_2D, 1)
+    inst = eng.Instance(ctx, xy, O.EUC_2D, 1)
+    inst.knn_build(K)
+    return xy, D, inst, inst.knn()
+
+
+# ---- 1. whole descents ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("lists", ["knn", "alpha"])
+@pytest.mark.parametrize("name", ["att48", "kroA100"])
+def test_descents_equal_the_reference(eng, ctx, name, lists):
+    xy, wt, D, inst, nbr = _setup(eng, ctx, name, lists)
+    n = len(xy)
+    if lists == "alpha":                                  # the device's lists are the reference's
+        A, Wt, _ = AR.alpha_rows(D)
+        assert (nbr == AR.lists(A, Wt, np.arange(n), 5)[0]).all()
+    shrunk = 0
+    for start in (random_tour(n, np.random.default_rng(7)), O.greedy(xy, wt)[1]):
+        for kinds in (7, 3, 4):
+            for mode in (DR.ON, DR.CLOSE):
+                ref, c, _ = DR.descent(D, start, nbr, kinds, mode)
+                rc, s, o, st = inst.nl_3opt(start, kinds=kinds, time_limit=LIMIT, dlb=mode)
+                assert rc == 0, (kinds, mode)
+                _same(s, o, st, ref, IR.cost(D, ref), c)
+                assert o == O.succ_cost(xy, wt, s) and st["deltas_executed"] > 0
+                assert (st["closing_scans"] > 0) == (mode == DR.CLOSE) or st["moves"] == 0
+                shrunk += int(st["active_nodes"] < n * st["decisions"])
+                if mode == DR.CLOSE:                      # a local optimum of the whole list neighbourhood
+                    rc, s2, o2, st2 = inst.nl_3opt(s, kinds=kinds, time_limit=LIMIT)
+                    assert rc == 0 and (s2 == s).all() and st2["moves"] == 0 and st2["decisions"] == 1
+    inst.close()
+    assert shrunk >= 10
+
+
+def test_the_smallest_instances(eng, ctx):
+    xy48, wt = load_instance("att48")
+    for n in (5, 6, 7, 8, 9):
+        xy = xy48[:n]
+        D = O.dist_matrix(xy, wt, 1)
+        inst = eng.Instance(ctx, xy, wt, 1)
+        for K in (n - 1, 2):
+            inst.knn_build(K)
+            nbr = inst.knn()
+            for q in range(3):
+                start = random_tour(n, np.random.default_rng(10 * n + q))
+                for mode in (DR.ON, DR.CLOSE):
+                    ref, c, _ = DR.descent(D, start, nbr, 7, mode)
+                    rc, s, o, st = inst.nl_3opt(start, time_limit=LIMIT, dlb=mode)
+                    assert rc == 0
+                    _same(s, o, st, ref, IR.cost(D, ref), c)
+                    # chains: the descent alone below eight nodes, kicks from eight on
+                    rs, rcost, rst = DR.chain(D, start, nbr, 7, q, 0, 12, 0, mode=mode)
+                    rc, s, o, st = inst.ils(start, 12, seed=q, time_limit=LIMIT, dlb=mode)
+                    assert rc == 0 and st["iterations"] == (12 if n >= 8 else 0)
+                    _same(s, o, st, rs, rcost, rst, ILS_STATS)
+        inst.close()
+
+
+def test_active_lanes_that_end_inside_and_beyond_the_first_workgroup(eng, ctx):
+    # n = 64, K = 5: 320 lanes with every node active, two workgroups; |A| K falls through 256 as A shrinks
+    xy, D, inst, nbr = _rand(eng, ctx, 64, 5)
+    start = random_tour(64, np.random.default_rng(64))
+    for mode in (DR.ON, DR.CLOSE):
+        trace = []
+        ref, c, _ = DR.descent(D, start, nbr, 7, mode, trace=trace)
+        sizes = [na for _, na in trace]
+        assert max(sizes) * 5 > 256 and any(0 < na * 5 <= 256 for na in sizes) and any(na * 5 in range(257, 320) for na in sizes)
+        rc, s, o, st = inst.nl_3opt(start, time_limit=LIMIT, dlb=mode)
+        assert rc == 0
+        _same(s, o, st, ref, IR.cost(D, ref), c)
+    inst.close()
+
+
+def test_a_thousand_nodes_with_the_longest_lists(eng, ctx):
+    # n = 1025, K = 16: 16400 lanes, 65 workgroups, the last one with 16 lanes; a set of about a hundred nodes from a random
+    # tour (a few workgroups, the moves cut short), and the eight nodes of a kick closed to the whole neighbourhood
+    n = 1025
+    xy, D, inst, nbr = _rand(eng, ctx, n, 16)
+    rng = np.random.default_rng(n)
+    start = random_tour(n, rng)
+    A = rng.random(n) < 0.1
+    ref, c, _ = DR.descent(D, start, nbr, 7, DR.ON, active=A, max_moves=12)
+    rc, s, o, st = inst.nl_3opt(start, max_moves=12, time_limit=LIMIT, dlb=DR.ON, active=A)
+    assert rc == 0 and st["moves"] == 12
+    _same(s, o, st, ref, IR.cost(D, ref), c)
+    rc, opt, _, _ = inst.nl_3opt(O.greedy(xy, O.EUC_2D)[1], time_limit=LIMIT)
+    kicked = inst.ils_kick(opt, 3, 0, 50)
+    A = DR.kick_nodes(opt, 3, 0, 0, 50)
+    ref, c, _ = DR.descent(D, kicked, nbr, 7, DR.CLOSE, active=A)
+    rc, s, o, st = inst.nl_3opt(kicked, time_limit=LIMIT, dlb=DR.CLOSE, active=A)
+    assert rc == 0 and st["closing_scans"] >= 1
+    _same(s, o, st, ref, IR.cost(D, ref), c)
+    inst.close()
+
+
+def test_tours_with_different_sets_in_one_call(eng, ctx):
+    xy, wt, D, inst, nbr = _setup(eng, ctx, "kroA100")
+    n = len(xy)
+    rng = np.random.default_rng(5)
+    starts = np.stack([random_tour(n, rng), O.greedy(xy, wt)[1], random_tour(n, rng)])
+    active = np.stack([np.zeros(n, dtype=np.uint8), np.ones(n, dtype=np.uint8), (rng.random(n) < 0.15).astype(np.uint8) * 7])
+    for mode in (DR.ON, DR.CLOSE):
+        rc, S, Ob, St = inst.nl_3opt(starts, time_limit=LIMIT, dlb=mode, active=active)
+        assert rc == 0
+        for b in range(3):
+            ref, c, _ = DR.descent(D, starts[b], nbr, 7, mode, active=active[b])
+            _same(S[b], Ob[b], St[b], ref, IR.cost(D, ref), c)
+        if mode == DR.ON:                                  # the empty set: one decision, nothing looked at, the tour as it came
+            assert (S[0] == starts[0]).all() and (St[0]["decisions"], St[0]["moves"], St[0]["active_nodes"]) == (1, 0, 0)
+        else:
+            assert St[0]["closing_scans"] >= 1 and St[0]["moves"] > 0
+    inst.close()
+
+
+def test_non_integer_costs(eng, ctx):
+    xy, wt, D, inst, nbr = _setup(eng, ctx, "kroA100", integer_cost=0)
+    start = random_tour(len(xy), np.random.default_rng(7))
+    for mode in (DR.ON, DR.CLOSE):
+        ref, c, _ = DR.descent(D, start, nbr, 7, mode)
+        rc, s, o, st = inst.nl_3opt(start, time_limit=LIMIT, dlb=mode)
+        assert rc == 0
+        _same(s, o, st, ref, IR.cost(D, ref), c)
+        rs, rcost, rst = DR.chain(D, start, nbr, 7, 7, 0, 20, 30, mode=mode, max_moves=50)
+        rc, s, o, st = inst.ils(start, 20, seed=7, span=30, max_moves_per_descent=50, time_limit=LIMIT, dlb=mode)
+        assert rc == 0
+        _same(s, o, st, rs, rcost, rst, ILS_STATS)
+        assert np.float64(o).tobytes() == np.float64(IR.cost(D, s)).tobytes()
+        assert np.float64(st["start_cost"]).tobytes() == np.float64(rst["start_cost"]).tobytes()
+    inst.close()
+
+
+# ---- 2. mode 0, a caller's set --------------------------------------------------------------------------------------------------------
+
+def test_mode_zero_is_the_full_scan(eng, ctx):
+    xy, wt, D, inst, nbr = _setup(eng, ctx, "kroA100")
+    n = len(xy)
+    L = eng.lib()
+    start = random_tour(n, np.random.default_rng(3))
+    timing = ("seconds", "device_ms")
+    rc0, s0, o0, st0 = inst.nl_3opt(start, time_limit=LIMIT)
+    succ, obj, st = start.copy(), np.zeros(1), eng.NlDlbStats()
+    junk = np.zeros(n, dtype=np.uint8)                    # ignored
+    rc = L.tsp_dev_nl_3opt_dlb(inst._h, 7, 0, 1, succ.ctypes.data_as(C.POINTER(C.c_int)), 1, n, obj.ctypes.data_as(C.POINTER(C.c_double)),
+                               junk.ctypes.data_as(C.POINTER(C.c_ubyte)), -1, LIMIT, C.byref(st))
+    d = st.as_dict()
+    assert rc == rc0 == 0 and (succ == s0).all() and obj[0] == o0 and d["active_nodes"] == d["closing_scans"] == 0
+    assert all(d[k] == st0[k] for k in st0 if k not in timing)
+    rc0, s0, o0, st0 = inst.ils(start, 15, seed=4, span=30, time_limit=LIMIT)
+    succ, obj, st = start.copy(), np.zeros(1), eng.IlsDlbStats()
+    rc = L.tsp_dev_ils_dlb(inst._h, 7, 1, succ.ctypes.data_as(C.POINTER(C.c_int)), 1, n, obj.ctypes.data_as(C.POINTER(C.c_double)),
+                           4, 15, 30, -1, LIMIT, 0, C.byref(st))
+    d = st.as_dict()
+    assert rc == rc0 == 0 and (succ == s0).all() and obj[0] == o0 and d["active_nodes"] == d["closing_scans"] == 0
+    assert all(d[k] == st0[k] for k in st0 if k not in timing)
+    # the Python defaults are today's calls and today's keys
+    assert "active_nodes" not in st0 and "active_nodes" not in inst.nl_3opt(start, time_limit=LIMIT)[3]
+    inst.close()
+
+
+def test_a_kicked_optimum_from_the_eight_nodes_of_the_kick(eng, ctx):
+    xy, wt, D, inst, nbr = _setup(eng, ctx, "kroA100")
+    n = len(xy)
+    rc, opt, _, _ = inst.nl_3opt(random_tour(n, np.random.default_rng(1)), time_limit=LIMIT)
+    moved = 0
+    for it in range(8):
+        for span in (0, 30):
+            kicked = inst.ils_kick(opt, 21, it, span)
+            s_, o1, o2, o3, o4 = IR.cuts(n, span, IR.draws(21, 0, it))
+            seq = [s_]
+            for _ in range(n - 1):
+                seq.append(int(opt[seq[-1]]))
+            A = np.zeros(n, dtype=np.uint8)
+            A[[seq[o - 1] for o in (o1, o2, o3, o4)] + [seq[o % n] for o in (o1, o2, o3, o4)]] = 1
+            assert (A != 0).tolist() == DR.kick_nodes(opt, 21, 0, it, span).tolist()
+            for mode in (DR.ON, DR.CLOSE):
+                ref, c, _ = DR.descent(D, kicked, nbr, 7, mode, active=A)
+                rc, s, o, st = inst.nl_3opt(kicked, time_limit=LIMIT, dlb=mode, active=A)
+                assert rc == 0
+                _same(s, o, st, ref, IR.cost(D, ref), c)
+                moved += st["moves"]
+                if mode == DR.ON:
+                    assert st["active_nodes"] < n * st["decisions"] and st["active_nodes"] <= 20 * st["decisions"]
+    inst.close()
+    assert moved > 0
+
+
+# ---- 3. chains ----------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("mode", [DR.ON, DR.CLOSE])
+@pytest.mark.parametrize("name", ["att48", "kroA100"])
+def test_chains_equal_the_reference(eng, ctx, name, mode):
+    xy, wt, D, inst, nbr = _setup(eng, ctx, name)
+    n = len(xy)
+    start = random_tour(n, np.random.default_rng(7))
+    for span in (0, 30):
+        seed = SEEDS.get((name, span), 7)
+        ref, cost, st = DR.chain(D, start, nbr, 7, seed, 0, 40, span, mode=mode)
+        assert 0 < st["accepted"] < st["iterations"] == 40, (name, mode, span, st["accepted"])
+        rc, s, o, dst = inst.ils(start, 40, seed=seed, span=span, time_limit=LIMIT, dlb=mode)
+        assert rc == 0
+        _same(s, o, dst, ref, cost, st, ILS_STATS)
+        assert o == O.succ_cost(xy, wt, s) and o < dst["start_cost"]
+        # descents in which the nodes of the kick alone were looked at
+        assert dst["active_nodes"] < n * dst["decisions"]
+        assert (dst["closing_scans"] >= 41) == (mode == DR.CLOSE)
+    inst.close()
+
+
+def test_prefixes_of_a_chain_and_chains_of_a_batch(eng, ctx):
+    xy, wt, D, inst, nbr = _setup(eng, ctx, "kroA100")
+    n = len(xy)
+    start = random_tour(n, np.random.default_rng(7))
+    for mode in (DR.ON, DR.CLOSE):
+        for iters in range(5):
+            ref, cost, st = DR.chain(D, start, nbr, 7, 9, 0, iters, 30, mode=mode)
+            rc, s, o, dst = inst.ils(start, iters, seed=9, span=30, time_limit=LIMIT, dlb=mode)
+            assert rc == 0
+            _same(s, o, dst, ref, cost, st, ILS_STATS)
+            if iters == 0:
+                rc3, s3, o3, st3 = inst.nl_3opt(start, time_limit=LIMIT, dlb=mode)
+                assert (s == s3).all() and o == o3 == dst["start_cost"] and all(dst[k] == st3[k] for k in DR.COUNTERS)
+        starts = np.stack([start, start, O.greedy(xy, wt)[1]])
+        rc, S, Ob, St = inst.ils(starts, 8, seed=11, span=30, time_limit=LIMIT, dlb=mode)
+        assert rc == 0
+        for b in range(3):
+            _same(S[b], Ob[b], St[b], *DR.chain(D, starts[b], nbr, 7, 11, b, 8, 30, mode=mode), ILS_STATS)
+        rc, s, o, dst = inst.ils(start, 8, seed=11, span=30, time_limit=LIMIT, dlb=mode)     # alone, it is stream 0
+        assert (s == S[0]).all() and o == Ob[0] and all(dst[k] == St[0][k] for k in ILS_STATS)
+        assert not (S[0] == S[1]).all()                                                     # the streams differ
+    inst.close()
+
+
+# ---- 4. the time limit, bad arguments ----------------------------------------------------------------------------------------------
+
+def test_a_limit_too_short_for_the_first_descent_returns_the_callers_tour(eng, ctx):
+    n = 5000
+    xy = rand_instance(n)
+    inst = eng.Instance(ctx, xy, O.EUC_2D, 1)
+    inst.knn_build(8)
+    start = random_tour(n, np.random.default_rng(1))
+    for mode in (DR.ON, DR.CLOSE):
+        rc, s, o, st = inst.ils(start, 10, seed=3, span=50, time_limit=1e-4, dlb=mode)
+        assert rc == eng.TIME_LIMIT_EXCEEDED
+        assert (s == start).all() and o == st["start_cost"] == O.succ_cost(xy, O.EUC_2D, start) and st["iterations"] == 0
+        rc, s, o, st = inst.nl_3opt(start, time_limit=1e-4, dlb=mode)
+        assert rc == eng.TIME_LIMIT_EXCEEDED and O.is_tour(s) and o == O.succ_cost(xy, O.EUC_2D, s)
+    inst.close()
+
+
+def test_bad_modes_leave_the_tours_alone(eng, ctx):
+    xy, wt, D, inst, nbr = _setup(eng, ctx, "att48")
+    n = len(xy)
+    start = random_tour(n, np.random.default_rng(4))
+    L = eng.lib()
+    ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    for mode in (-1, 3, 4, 1 << 20):
+        succ, obj = start.copy(), np.zeros(1)
+        st = eng.NlDlbStats()
+        rc = L.tsp_dev_nl_3opt_dlb(inst._h, 7, mode, 1, succ.ctypes.data_as(ip), 1, n, obj.ctypes.data_as(dp), None, -1, LIMIT, C.byref(st))
+        assert rc == eng.E_ARG and (succ == start).all(), mode
+        sti = eng.IlsDlbStats()
+        rc = L.tsp_dev_ils_dlb(inst._h, 7, 1, succ.ctypes.data_as(ip), 1, n, obj.ctypes.data_as(dp), 1, 5, 0, -1, LIMIT, mode, C.byref(sti))
+        assert rc == eng.E_ARG and (succ == start).all(), mode
+        with pytest.raises(eng.TspDeviceError, match="-3"):
+            inst.nl_3opt(start, time_limit=LIMIT, dlb=mode)
+        with pytest.raises(eng.TspDeviceError, match="-3"):
+            inst.ils(start, 5, time_limit=LIMIT, dlb=mode)
+    # the other checks of the two calls hold under a mode
+    for kinds, iters, span in ((0, 5, 0), (8, 5, 0), (7, -1, 0), (7, 5, 3)):
+        succ, obj = start.copy(), np.zeros(1)
+        sti = eng.IlsDlbStats()
+        rc = L.tsp_dev_ils_dlb(inst._h, kinds, 1, succ.ctypes.data_as(ip), 1, n, obj.ctypes.data_as(dp), 1, iters, span, -1, LIMIT, 1,
+                               C.byref(sti))
+        assert rc == eng.E_ARG and (succ == start).all(), (kinds, iters, span)
+    # and the handle still follows the reference
+    ref, c, _ = DR.descent(D, start, nbr, 7, DR.ON)
+    rc, s, o, st = inst.nl_3opt(start, time_limit=LIMIT, dlb=DR.ON)
+    _same(s, o, st, ref, IR.cost(D, ref), c)
+    inst.close()
+
+
+# ---- 5. the recorded runs and the host library --------------------------------------------------------------------------------------
+
+def test_recorded_runs_and_the_host_library(eng, ctx):
+    from tsp_optimization_amd.build import lib_path
+    runs = golden("dlb_runs.json")["runs"]
+    assert [r["mode"] for r in runs] == [1, 2] and all(r["name"] == "pr299" for r in runs)
+    xy, wt = load_instance("pr299")
+    inst = eng.Instance(ctx, xy, wt, 1)
+    succ, obj, status = inst.construct(eng.GREEDY, np.array([0], dtype=np.int32))
+    inst.knn_build(runs[0]["K"])
+    got = {}
+    for r in runs:
+        rc, s, o, st = inst.ils(succ[0], r["iterations"], seed=r["seed"], span=r["span"], time_limit=LIMIT, dlb=r["mode"])
+        assert rc == 0
+        _same(s, o, st, r["succ"], r["cost"], r["stats"], ILS_STATS)
+        assert o == O.succ_cost(xy, wt, s)
+        got[r["mode"]] = (s, o, st)
+    inst.close()
+    L = C.CDLL(lib_path("libtsp_host.so"))
+    L.alg_ils.argtypes = [C.POINTER(Instance)]
+    L.tsp_host_last_ils_stats.argtypes = [C.POINTER(eng.IlsStats)]
+    L.tsp_host_last_dlb_stats.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    r0 = runs[0]
+    try:
+        h = HostInstance("pr299")
+        h.c.params.seed = r0["seed"]
+        h.c.params.time_limit = int(LIMIT)
+        assert L.tsp_host_set_alpha(0, 0) == 0 and L.tsp_host_set_knn(r0["K"]) == 0
+        assert L.tsp_host_set_ils(r0["iterations"], r0["span"], 1) == 0
+        for mode in (1, 2):
+            h.set_tour(succ[0], obj[0])
+            assert L.tsp_host_set_dlb(mode) == 0 and L.alg_ils(C.byref(h.c)) == 0
+            hs = eng.IlsStats()
+            L.tsp_host_last_ils_stats(C.byref(hs))
+            an, cs = C.c_int64(-1), C.c_int64(-1)
+            L.tsp_host_last_dlb_stats(C.byref(an), C.byref(cs))
+            d = hs.as_dict()
+            d["active_nodes"], d["closing_scans"] = an.value, cs.value
+            s, o, st = got[mode]
+            _same(h.succ, h.obj, d, s, o, st, ILS_STATS)
+    finally:
+        L.tsp_host_set_dlb(0)
+        L.tsp_host_set_ils(100, 50, 1)
+        L.tsp_host_set_knn(eng.NL_DEFAULT_K)
+        L.tsp_host_shutdown()

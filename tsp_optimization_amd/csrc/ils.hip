@@ -28,15 +28,25 @@ __host__ __device__ __forceinline__ u64 ils_mix(u64 x) {
 // The kick of iteration `it` of chain b on order/pos (n >= 8, W >= 8), by every thread of the one workgroup (NT threads) that
 // owns the tour, behind a barrier that follows the last write of the tour.  Positions pos[s] + o1 .. pos[s] + o4 - 1 hold
 // Bk Ck Dk; reversed as one path they hold Dk' Ck' Bk', and each block reversed again leaves Dk Ck Bk.
+struct IlsCuts {
+    int s, o1, o2, o3, o4;
+};
+__device__ __forceinline__ IlsCuts ils_cuts(int n, int W, u64 seed, int b, long long it) {
+    const u64 base = ils_mix(ils_mix(seed ^ ((u64)b * 0x100000001B3ull)) + (u64)it);
+    IlsCuts c;
+    c.s = (int)(ils_mix(base) % (u64)n);
+    c.o1 = 1 + (int)(ils_mix(base + 1) % (u64)(W - 3));
+    c.o2 = c.o1 + 1 + (int)(ils_mix(base + 2) % (u64)(W - 2 - c.o1));
+    c.o3 = c.o2 + 1 + (int)(ils_mix(base + 3) % (u64)(W - 1 - c.o2));
+    c.o4 = c.o3 + 1 + (int)(ils_mix(base + 4) % (u64)(W - c.o3));
+    return c;
+}
+
 template <int NT>
 __device__ __forceinline__ void ils_kick(int *__restrict__ order, int *__restrict__ pos, int n, int W, u64 seed, int b,
                                          long long it) {
-    const u64 base = ils_mix(ils_mix(seed ^ ((u64)b * 0x100000001B3ull)) + (u64)it);
-    const int s = (int)(ils_mix(base) % (u64)n);
-    const int o1 = 1 + (int)(ils_mix(base + 1) % (u64)(W - 3));
-    const int o2 = o1 + 1 + (int)(ils_mix(base + 2) % (u64)(W - 2 - o1));
-    const int o3 = o2 + 1 + (int)(ils_mix(base + 3) % (u64)(W - 1 - o2));
-    const int o4 = o3 + 1 + (int)(ils_mix(base + 4) % (u64)(W - o3));
+    const IlsCuts c = ils_cuts(n, W, seed, b, it);
+    const int s = c.s, o1 = c.o1, o2 = c.o2, o3 = c.o3, o4 = c.o4;
     const int at = or_wrap(pos[s] + o1, n);   // position pos[s] is outside the window: no reversal moves s
     const int lB = o2 - o1, lC = o3 - o2, lD = o4 - o3;
     nl_reverse_path<NT>(order, pos, n, at, lB + lC + lD);
@@ -53,11 +63,13 @@ __global__ __launch_bounds__(kNlPickThreads) void k_ils_kick(int *__restrict__ o
 }
 
 // One workgroup per chain, behind every decision.  inc: the incumbents, B x n of order, then B x n of pos.
-template <int WT, bool INT>
+// DLB: the kick also sets the active set of the descent it re-arms: the tails and heads of its four removed edges, read from
+// the tour before the kick, and nothing else.
+template <int WT, bool INT, bool DLB>
 __global__ __launch_bounds__(kNlPickThreads) void k_ils_step(const double2 *__restrict__ coord, int *__restrict__ orders,
                                                              int *__restrict__ poss, int *__restrict__ inc,
                                                              NlState *__restrict__ st, IlsState *__restrict__ ils, int n, int W,
-                                                             u64 seed, long long iterations, long long M) {
+                                                             u64 seed, long long iterations, long long M, NlDlb dlb) {
     constexpr int NT = kNlPickThreads;
     const int b = blockIdx.x;
     NlState &S = st[b];
@@ -70,6 +82,7 @@ __global__ __launch_bounds__(kNlPickThreads) void k_ils_step(const double2 *__re
     int *iorder = inc + (size_t)b * n, *ipos = iorder + (size_t)gridDim.x * n;
     const long long it = I.it;          // the iteration whose descent has ended; -1: the first descent
     const double best = I.cost;
+    const int na = S.nact;              // what that descent left active
     const double c = tour_cost_block<WT, INT>(coord, order, pos, n, s_d, s_chunk);
     const bool accept = it < 0 || c < best;
     __syncthreads();   // every thread has read the chain's state
@@ -87,7 +100,30 @@ __global__ __launch_bounds__(kNlPickThreads) void k_ils_step(const double2 *__re
     }
     if (next >= iterations) return;     // the work tour is the incumbent
     __syncthreads();
+    int cut[8];
+    if constexpr (DLB) {
+        const IlsCuts c = ils_cuts(n, W, seed, b, next);
+        const int p0 = pos[c.s], o[4] = {c.o1, c.o2, c.o3, c.o4};   // o4 <= n: position p0 + o4 wraps to s itself at the most
+        for (int q = 0; q < 4; ++q) {
+            cut[2 * q] = order[or_wrap(p0 + o[q] - 1, n)];
+            cut[2 * q + 1] = order[or_wrap(p0 + o[q], n)];
+        }
+        __syncthreads();   // every thread has read the tour before the kick moves it
+    }
     ils_kick<NT>(order, pos, n, W, seed, b, next);
+    if constexpr (DLB) {
+        // hit is all zero behind a decision.  Whatever the descent left in A goes, also what a descent ended by M left there.
+        unsigned char *act = dlb.act + (size_t)b * n;
+        int *list = dlb.list + (size_t)b * n;
+        for (int slot = tid; slot < na; slot += NT) act[list[slot]] = 0;
+        __syncthreads();
+        if (tid == 0) {
+            int c = 0;
+            for (int q = 0; q < 8; ++q)
+                if (!act[cut[q]]) { act[cut[q]] = 1; list[c++] = cut[q]; }   // single-node blocks name a node twice
+            S.nact = c;
+        }
+    }
     if (tid == 0) {
         S.done = M == 0 ? 1 : 0;
         S.max_moves = M < 0 ? -1 : S.moves + M;
@@ -96,7 +132,7 @@ __global__ __launch_bounds__(kNlPickThreads) void k_ils_step(const double2 *__re
 
 // the stats record of a chain from its two control blocks
 void fill_stats(tsp_ils_stats &o, const NlState &z, const IlsState &q, double seconds, float device_ms) {
-    memset(&o, 0, sizeof o);
+    memset(&o, 0, sizeof(tsp_ils_stats));
     o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
     for (int k = 0; k < 3; ++k) o.moves_by_len[k] = z.moves_len[k];
     o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
@@ -112,7 +148,8 @@ struct IlsHooks {
     tsp_dev_tours *t;
     NlData *x;
     long long M;
-    void init(NlState &z, int) const { z.done = M == 0 ? 1 : 0; }
+    const int *nact;   // don't-look bits: |A| of the first descent; else NULL
+    void init(NlState &z, int b) const { z.done = M == 0 ? 1 : 0; if (nact) z.nact = nact[b]; }
     int fetch(hipStream_t s) const {
         TSP_HIP_TRY(hipMemcpyAsync(x->h_ils, x->d_ils, sizeof(IlsState) * t->B, hipMemcpyDeviceToHost, s));
         return TSP_OK;
@@ -135,11 +172,23 @@ bool bad_span(int span) { return span >= 1 && span <= 7; }
 }  // namespace
 
 static_assert(offsetof(tsp_ils_stats, iterations) == sizeof(tsp_nl3_opt_stats), "tsp_ils_stats starts as tsp_nl3_opt_stats");
+static_assert(offsetof(tsp_ils_dlb_stats, active_nodes) == sizeof(tsp_ils_stats), "tsp_ils_dlb_stats starts as tsp_ils_stats");
 
-extern "C" {
-
-int tsp_dev_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj, uint64_t seed,
-                int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, tsp_ils_stats *stats) {
+// What both entry points do.  stats (may be NULL): B records `stride` bytes apart that start with the layout of tsp_ils_stats; with
+// dlb_mode != 0 they are tsp_ils_dlb_stats.
+static int ils_run(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj, uint64_t seed,
+                   int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, int dlb_mode, void *stats_,
+                   size_t stride) {
+    char *stats = static_cast<char *>(stats_);
+    auto record = [&](int b, const NlState &z, const IlsState &q, double seconds, float device_ms) -> tsp_ils_stats & {
+        tsp_ils_stats &o = *reinterpret_cast<tsp_ils_stats *>(stats + (size_t)b * stride);
+        fill_stats(o, z, q, seconds, device_ms);
+        if (dlb_mode) {
+            tsp_ils_dlb_stats &d = *reinterpret_cast<tsp_ils_dlb_stats *>(&o);
+            d.active_nodes = z.active_nodes; d.closing_scans = z.closing_scans;
+        }
+        return o;
+    };
     const int allowed = TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT;
     const int asked = kinds;
     int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
@@ -151,13 +200,13 @@ int tsp_dev_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride
         const NlState *z = nullptr;
         std::vector<tsp_nl3_opt_stats> st3((size_t)B);
         const int status = tsp_nl_run(inst, asked, allowed, B, succ, succ_stride, tour_stride, obj, M, time_limit_s,
-                                      st3.data(), sizeof(tsp_nl3_opt_stats), &z);
+                                      st3.data(), sizeof(tsp_nl3_opt_stats), &z, dlb_mode, nullptr);
         if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
         for (int b = 0; b < B && stats; ++b) {
             IlsState q;
             memset(&q, 0, sizeof q);
             q.last_improved = -1; q.cost = q.start_cost = obj[b];
-            fill_stats(stats[b], z[b], q, st3[b].seconds, (float)st3[b].device_ms);
+            record(b, z[b], q, st3[b].seconds, (float)st3[b].device_ms);
         }
         return status;
     }
@@ -186,23 +235,50 @@ int tsp_dev_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride
     TSP_HIP_TRY(hipMemcpyAsync(x->d_inc + Bn, t->d_pos, sizeof(int) * Bn, hipMemcpyDeviceToDevice, s));
     TSP_HIP_TRY(hipMemcpyAsync(x->d_ils, x->h_ils, sizeof(IlsState) * B, hipMemcpyHostToDevice, s));
     const int W = span <= 0 ? n : std::min(span, n);
-    const IlsHooks hooks{t, x, M};
+    std::vector<int> nact;   // step 1 of a chain starts with A = V
+    if (dlb_mode) {
+        rc = tsp_nl_dlb_start(inst, x, B, nullptr, &nact);
+        if (rc) return rc;
+    }
+    const IlsHooks hooks{t, x, M, dlb_mode ? nact.data() : nullptr};
     const int status = run.run(x->d_st, x->h_st, x->d_cost, false, 256, M, time_limit_s,
                                [&](bool) {
-                                   tsp_nl_launch_decision(t, x, kinds);
+                                   tsp_nl_launch_decision(t, x, kinds, dlb_mode);
                                    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-                                       hipLaunchKernelGGL((k_ils_step<WTC, INTC>), dim3(B), dim3(kNlPickThreads), 0, s, inst->d_coord,
-                                                          t->d_order, t->d_pos, x->d_inc, x->d_st, x->d_ils, n, W, (u64)seed,
-                                                          (long long)iterations, M);
+                                       if (!dlb_mode)
+                                           hipLaunchKernelGGL((k_ils_step<WTC, INTC, false>), dim3(B), dim3(kNlPickThreads), 0, s,
+                                                              inst->d_coord, t->d_order, t->d_pos, x->d_inc, x->d_st, x->d_ils, n, W,
+                                                              (u64)seed, (long long)iterations, M, NlDlb{});
+                                       else
+                                           hipLaunchKernelGGL((k_ils_step<WTC, INTC, true>), dim3(B), dim3(kNlPickThreads), 0, s,
+                                                              inst->d_coord, t->d_order, t->d_pos, x->d_inc, x->d_st, x->d_ils, n, W,
+                                                              (u64)seed, (long long)iterations, M, x->dlb(dlb_mode));
                                    });
                                },
                                hooks);
     if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
     for (int b = 0; b < B && stats; ++b) {
-        fill_stats(stats[b], x->h_st[b], x->h_ils[b], wall_s() - run.t0, run.device_ms);
-        if (x->h_ils[b].it < 0) stats[b].start_cost = obj[b];   // the limit ended the first descent: the caller's tour
+        tsp_ils_stats &o = record(b, x->h_st[b], x->h_ils[b], wall_s() - run.t0, run.device_ms);
+        if (x->h_ils[b].it < 0) o.start_cost = obj[b];   // the limit ended the first descent: the caller's tour
     }
     return status;
+}
+
+extern "C" {
+
+int tsp_dev_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj, uint64_t seed,
+                int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, tsp_ils_stats *stats) {
+    return ils_run(inst, kinds, B, succ, succ_stride, tour_stride, obj, seed, iterations, span, max_moves_per_descent, time_limit_s,
+                   TSP_DLB_OFF, stats, sizeof *stats);
+}
+
+int tsp_dev_ils_dlb(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                    uint64_t seed, int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, int dlb_mode,
+                    tsp_ils_dlb_stats *stats) {
+    if (dlb_mode != TSP_DLB_OFF && dlb_mode != TSP_DLB_ON && dlb_mode != TSP_DLB_CLOSE) return TSP_DEV_E_ARG;
+    for (int b = 0; b < B && stats; ++b) stats[b].active_nodes = stats[b].closing_scans = 0;
+    return ils_run(inst, kinds, B, succ, succ_stride, tour_stride, obj, seed, iterations, span, max_moves_per_descent, time_limit_s,
+                   dlb_mode, stats, sizeof *stats);
 }
 
 int tsp_dev_ils_kick(tsp_dev_inst *inst, int B, int *succ, int succ_stride, int64_t tour_stride, uint64_t seed, int64_t it,

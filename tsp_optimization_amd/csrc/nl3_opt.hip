@@ -29,13 +29,19 @@ __device__ __forceinline__ unsigned pair_slots(int s, int t) { return ((unsigned
 __device__ __forceinline__ bool same_edge(int x, int y, int p, int u) { return (x == p && y == u) || (x == u && y == p); }
 
 // One lane per list entry (p, k1), u = nbr[p][k1], q = succ p: the moves that remove (p, q) and add {p, u} and {q, w}, w in N(q).
-template <int WT, bool INT>
+// DLB: the lanes of the active nodes alone, as k_nl_scan<.., true> of nl_opt.hip maps and reports them.
+template <int WT, bool INT, bool DLB>
 __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ coord, const int *__restrict__ orders,
                                                   const int *__restrict__ poss, NlState *__restrict__ st, int n, int K,
                                                   const int *__restrict__ nbr, const double *__restrict__ Es,
-                                                  NlBest *__restrict__ parts) {
+                                                  NlBest *__restrict__ parts, NlDlb dlb) {
     const int bt = blockIdx.y;
     if (st[bt].done) return;
+    long long lanes = (long long)n * K;
+    if constexpr (DLB) {
+        lanes = (long long)st[bt].nact * K;
+        if ((long long)blockIdx.x * blockDim.x >= lanes) return;
+    }
     __shared__ double sd[4];
     __shared__ u64 sk[4];
     const int *order = orders + (size_t)bt * n, *pos = poss + (size_t)bt * n;
@@ -44,9 +50,15 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
     u64 bk = kNoKey;
     unsigned cnt = 0;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < (long long)n * K) {
-        const int p = (int)(t / K);
-        const int u = nbr[t];
+    if (t < lanes) {
+        int p = (int)(t / K);
+        long long e = t;
+        if constexpr (DLB) {
+            e = t - (long long)p * K;
+            p = dlb.list[(size_t)bt * n + p];
+            e += (long long)p * K;
+        }
+        const int u = nbr[e];
         const int pp = pos[p], pu = pos[u];
         if (apart(pp, pu, n)) {
             const int pq = or_wrap(pp + 1, n), q = order[pq];
@@ -112,6 +124,8 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
                 }
             }
         }
+        if constexpr (DLB)
+            if (bk != kNoKey) dlb.hit[(size_t)bt * n + p] = 1;
     }
     block_argmin<true>(bd, bk, sd, sk);
     if (threadIdx.x == 0) parts[(size_t)bt * gridDim.x + blockIdx.x] = NlBest{bd, bk};
@@ -122,15 +136,20 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
 
 }  // namespace
 
-void tsp_nl3_launch_scan(tsp_dev_tours *t, NlData *x, NlBest *parts3) {
+void tsp_nl3_launch_scan(tsp_dev_tours *t, NlData *x, NlBest *parts3, int dlb_mode) {
     tsp_dev_inst *inst = t->inst;
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-        hipLaunchKernelGGL((k_nl3_scan<WTC, INTC>), dim3(x->nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord, t->d_order,
-                           t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3);
+        if (!dlb_mode)
+            hipLaunchKernelGGL((k_nl3_scan<WTC, INTC, false>), dim3(x->nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord,
+                               t->d_order, t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3, NlDlb{});
+        else
+            hipLaunchKernelGGL((k_nl3_scan<WTC, INTC, true>), dim3(x->nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord,
+                               t->d_order, t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3, x->dlb(dlb_mode));
     });
 }
 
 static_assert(offsetof(tsp_nl3_opt_stats, moves_3opt) == sizeof(tsp_nl_opt_stats), "tsp_nl3_opt_stats starts as tsp_nl_opt_stats");
+static_assert(offsetof(tsp_nl_dlb_stats, active_nodes) == sizeof(tsp_nl3_opt_stats), "tsp_nl_dlb_stats starts as tsp_nl3_opt_stats");
 
 extern "C" {
 
@@ -143,6 +162,22 @@ int tsp_dev_nl_3opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_st
     for (int b = 0; b < B && stats; ++b) {
         stats[b].moves_3opt = st[b].moves_3opt;
         for (int q = 0; q < 4; ++q) stats[b].moves_by_type[q] = st[b].moves_type[q];
+    }
+    return status;
+}
+
+int tsp_dev_nl_3opt_dlb(tsp_dev_inst *inst, int kinds, int dlb_mode, int B, int *succ, int succ_stride, int64_t tour_stride,
+                        double *obj, const unsigned char *active, int64_t max_moves, double time_limit_s, tsp_nl_dlb_stats *stats) {
+    if (dlb_mode != TSP_DLB_OFF && dlb_mode != TSP_DLB_ON && dlb_mode != TSP_DLB_CLOSE) return TSP_DEV_E_ARG;
+    const NlState *st = nullptr;
+    const int status = tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj,
+                                  max_moves, time_limit_s, stats, sizeof *stats, &st, dlb_mode, active);
+    if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
+    for (int b = 0; b < B && stats; ++b) {
+        stats[b].moves_3opt = st[b].moves_3opt;
+        for (int q = 0; q < 4; ++q) stats[b].moves_by_type[q] = st[b].moves_type[q];
+        stats[b].active_nodes = st[b].active_nodes;
+        stats[b].closing_scans = st[b].closing_scans;
     }
     return status;
 }

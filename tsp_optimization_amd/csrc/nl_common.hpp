@@ -24,7 +24,18 @@ struct alignas(16) NlState {
     long long max_moves;   // < 0: unlimited
     long long decisions, moves, moves_2opt, moves_oropt, moves_len[3], moves_rev, reversed, deltas;
     long long moves_3opt, moves_type[4];
-    int done, pad;
+    long long active_nodes, closing_scans;   // don't-look bits: sum of |A| over the decisions, times A was reset to V
+    int done;
+    int nact;                                // don't-look bits: |A|, the entries of the tour's row of NlDlb::list
+};
+
+// Don't-look bits: the active set A of every tour, as a bitmap and as a list without duplicates in no
+// particular order, and what the lanes of a decision's scans report per node.  Between two decisions hit is all zero.
+struct NlDlb {
+    unsigned char *act;   // B x n: 1 = the node is in A
+    unsigned char *hit;   // B x n: a lane of the node held an improving move in this decision (same-value plain stores)
+    int *list;            // B x n: the nodes of A, NlState::nact of them
+    int mode;             // TSP_DLB_ON or TSP_DLB_CLOSE
 };
 
 // Per-chain state of the iterated local search (ils.hip), written by thread 0 of k_ils_step.
@@ -73,28 +84,41 @@ struct NlData {
     int *d_inc = nullptr;
     IlsState *d_ils = nullptr;
     IlsState *h_ils = nullptr; // pinned
+    // don't-look bits, allocated by the first call at this B that asks for them: NlDlb::act, hit (B x n bytes each) and list
+    unsigned char *d_act = nullptr, *d_hit = nullptr;
+    int *d_alist = nullptr;
+    NlDlb dlb(int mode) const { return NlDlb{d_act, d_hit, d_alist, mode}; }
     void free_scratch() {
         (void)hipFree(d_st); (void)hipHostFree(h_st); (void)hipFree(d_E); (void)hipFree(d_rem); (void)hipFree(d_cost);
         (void)hipFree(d_part); (void)hipFree(d_inc); (void)hipFree(d_ils); (void)hipHostFree(h_ils);
         d_st = nullptr; h_st = nullptr; d_E = d_rem = d_cost = nullptr; d_part = nullptr; B = 0;
         d_inc = nullptr; d_ils = nullptr; h_ils = nullptr;
+        (void)hipFree(d_act); (void)hipFree(d_hit); (void)hipFree(d_alist);
+        d_act = d_hit = nullptr; d_alist = nullptr;
     }
     ~NlData() { free_scratch(); (void)hipFree(d_nbr); }
 };
 
 }  // namespace tsp
 
-// nl3_opt.hip: k_nl3_scan of every tour that is not done, one candidate per workgroup in parts3 (B x nparts)
-void tsp_nl3_launch_scan(tsp_dev_tours *t, tsp::NlData *x, tsp::NlBest *parts3);
+// nl3_opt.hip: k_nl3_scan of every tour that is not done, one candidate per workgroup in parts3 (B x nparts); dlb_mode != 0: over
+// the lanes of the active nodes alone
+void tsp_nl3_launch_scan(tsp_dev_tours *t, tsp::NlData *x, tsp::NlBest *parts3, int dlb_mode = 0);
 // nl_opt.hip: the argument checks of a list descent; *kinds loses the kinds without a move at the instance's size
 int tsp_nl_check(const tsp_dev_inst *inst, int *kinds, int allowed, int B, const int *succ, int succ_stride, int64_t tour_stride,
                  const double *obj);
 // nl_opt.hip: the instance's lists (the default lists when it has none) and the scratch of B tours -> *x
 int tsp_nl_prepare(tsp_dev_inst *inst, int B, tsp::NlData **x);
-// nl_opt.hip: one whole decision of every tour that is not done, queued on the engine's stream
-void tsp_nl_launch_decision(tsp_dev_tours *t, tsp::NlData *x, int kinds);
+// nl_opt.hip: one whole decision of every tour that is not done, queued on the engine's stream; dlb_mode != 0: a decision with
+// active sets (tsp_nl_dlb_start has set them)
+void tsp_nl_launch_decision(tsp_dev_tours *t, tsp::NlData *x, int kinds, int dlb_mode = 0);
+// nl_opt.hip: the active sets of the B tours of *x at the start of a call, queued on the engine's stream: `active` (B x n bytes,
+// non-zero = active) or, when NULL, every node.  nact[b] = |A| of tour b, for NlState::nact.
+int tsp_nl_dlb_start(tsp_dev_inst *inst, tsp::NlData *x, int B, const unsigned char *active, std::vector<int> *nact);
 // nl_opt.hip: what both entry points do.  `allowed` is the kinds mask the entry point takes.  stats (may be NULL): B records
 // `stats_stride` bytes apart that start with the layout of tsp_nl_opt_stats; that part of each is filled here.  With TSP_OK or
 // TSP_TIME_LIMIT_EXCEEDED *states (unless NULL) are the B final states, for what the caller's records hold beyond it.
+// dlb_mode != 0: the descent with don't-look bits from the set `active` (as tsp_nl_dlb_start takes it).
 int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
-               int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const tsp::NlState **states);
+               int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const tsp::NlState **states,
+               int dlb_mode = 0, const unsigned char *active = nullptr);

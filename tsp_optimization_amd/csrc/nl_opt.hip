@@ -162,13 +162,21 @@ struct NlView {
 };
 
 // One lane per list entry (v, k), u = nbr[v][k]: the moves whose new (2-opt) or attaching (Or-opt) edge is {v, u}.
-template <int WT, bool INT>
+// DLB: the same lanes of the active nodes alone, lane t = (slot t / K of the tour's list, k = t % K), on the same grid: a
+// workgroup whose first lane lies beyond |A| K returns (and writes no candidate), and a lane that holds an improving move
+// says so in hit[v].
+template <int WT, bool INT, bool DLB>
 __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coord, const int *__restrict__ orders,
                                                  const int *__restrict__ poss, NlState *__restrict__ st, int n, int K, int kinds,
                                                  const int *__restrict__ nbr, const double *__restrict__ Es,
-                                                 const double *__restrict__ rems, NlBest *__restrict__ parts) {
+                                                 const double *__restrict__ rems, NlBest *__restrict__ parts, NlDlb dlb) {
     const int b = blockIdx.y;
     if (st[b].done) return;
+    long long lanes = (long long)n * K;
+    if constexpr (DLB) {
+        lanes = (long long)st[b].nact * K;
+        if ((long long)blockIdx.x * blockDim.x >= lanes) return;
+    }
     __shared__ double sd[4];
     __shared__ u64 sk[4];
     NlView<WT, INT> w;
@@ -176,9 +184,15 @@ __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coo
     w.E = Es + (size_t)b * n; w.rem = rems + (size_t)b * 3 * n; w.n = n;
     w.bd = INFINITY; w.bk = kNoKey; w.cnt = 0;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < (long long)n * K) {
-        const int v = (int)(t / K);
-        const int u = nbr[t];
+    if (t < lanes) {
+        int v = (int)(t / K);
+        long long e = t;
+        if constexpr (DLB) {
+            e = t - (long long)v * K;
+            v = dlb.list[(size_t)b * n + v];
+            e += (long long)v * K;
+        }
+        const int u = nbr[e];
         if (u != v) {
             const int pv = w.pos[v], pu = w.pos[u];
             const double dk = w.d(v, u);
@@ -192,6 +206,8 @@ __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coo
                 w.roles(u, pu, v, pv, dk);
             }
         }
+        if constexpr (DLB)
+            if (w.bk != kNoKey) dlb.hit[(size_t)b * n + v] = 1;
     }
     double bd = w.bd;
     u64 bk = w.bk;
@@ -202,38 +218,11 @@ __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coo
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd((unsigned long long *)&st[b].deltas, cnt);
 }
 
-// Decision over the candidates of k_nl_scan (parts2) and k_nl3_scan (parts3; either may be NULL: no kind of it is enabled), then
-// the move.  One workgroup per tour.
-__global__ __launch_bounds__(kNlPickThreads) void k_nl_pick_apply(int *__restrict__ orders, int *__restrict__ poss,
-                                                                  NlState *__restrict__ st, int n, int nparts,
-                                                                  const NlBest *__restrict__ parts2,
-                                                                  const NlBest *__restrict__ parts3) {
-    constexpr int NT = kNlPickThreads;
-    const int bt = blockIdx.x;
-    NlState &S = st[bt];
-    if (S.done) return;
-    __shared__ double sd[NT / 64];
-    __shared__ u64 sk[NT / 64];
+// The move `bk` of whichever kind on order/pos and in the counters.  Called by every thread of the one workgroup (NT threads) that
+// owns the tour, with nothing of the tour written since the last barrier.
+template <int NT>
+__device__ __forceinline__ void nl_apply_move(int *__restrict__ order, int *__restrict__ pos, NlState &S, int n, u64 bk) {
     const int tid = threadIdx.x;
-    if (S.max_moves >= 0 && S.moves >= S.max_moves) {
-        if (tid == 0) S.done = 1;
-        return;
-    }
-    double bd = INFINITY; u64 bk = kNoKey;
-    for (int h = 0; h < 2; ++h) {
-        const NlBest *part = h ? parts3 : parts2;
-        if (!part) continue;
-        part += (size_t)bt * nparts;
-        for (int r = tid; r < nparts; r += NT) {
-            const NlBest q = part[r];
-            if (q.k != kNoKey && better(q.d, q.k, bd, bk)) { bd = q.d; bk = q.k; }
-        }
-    }
-    block_argmin<true>(bd, bk, sd, sk);
-    __syncthreads();
-    if (tid == 0) { S.decisions += 1; if (bk == kNoKey) S.done = 1; }
-    if (bk == kNoKey) return;
-    int *order = orders + (size_t)bt * n, *pos = poss + (size_t)bt * n;
     if (bk & kNl3Bit) {
         const u64 key = bk & (kNl3Bit - 1);
         const int T = (int)(key & 3);
@@ -288,6 +277,137 @@ __global__ __launch_bounds__(kNlPickThreads) void k_nl_pick_apply(int *__restric
     or_shift_apply<NT>(order, pos, n, i, ja, L, o, x);
 }
 
+// ends(m): the tails and heads of the edges that move `bk` removes, read from the tour before the move (scalars, not an array:
+// they stay in registers)
+struct NlEnds {
+    int ne = 0;   // 0: no move
+    int e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0, e5 = 0;
+};
+__device__ __forceinline__ NlEnds nl_move_ends(const int *__restrict__ order, const int *__restrict__ pos, int n, u64 bk) {
+    NlEnds r;
+    if (bk & kNl3Bit) {
+        const u64 abc = (bk & (kNl3Bit - 1)) >> 2;
+        r.e0 = (int)(abc / ((u64)n * (u64)n)); r.e2 = (int)((abc / (u64)n) % (u64)n); r.e4 = (int)(abc % (u64)n);
+        r.e1 = order[or_wrap(pos[r.e0] + 1, n)]; r.e3 = order[or_wrap(pos[r.e2] + 1, n)]; r.e5 = order[or_wrap(pos[r.e4] + 1, n)];
+        r.ne = 6;
+    } else if (!(bk & kNlOrBit)) {
+        r.e0 = (int)(bk / (u64)n); r.e2 = (int)(bk % (u64)n);
+        r.e1 = order[or_wrap(pos[r.e0] + 1, n)]; r.e3 = order[or_wrap(pos[r.e2] + 1, n)];
+        r.ne = 4;
+    } else {
+        const OrMove mv = or_unkey(bk & (kNlOrBit - 1), n);
+        const int pf = pos[mv.f];
+        r.e0 = order[or_wrap(pf - 1, n)]; r.e1 = mv.f;
+        r.e2 = order[or_wrap(pf + mv.L - 1, n)]; r.e3 = order[or_wrap(pf + mv.L, n)];
+        r.e4 = mv.a; r.e5 = order[or_wrap(pos[mv.a] + 1, n)];
+        r.ne = 6;
+    }
+    return r;
+}
+
+// The active set of one tour behind a decision that looked at its `na` nodes, by every thread of the workgroup (NT threads) that
+// owns the tour.  With a move (its ends in e): the listed nodes without a hit leave A, the others keep their order at the
+// front of the list (compacted in place: a chunk's writes lie at or below its own reads), then the ends that are not yet in A
+// join.  Without one, in mode TSP_DLB_CLOSE and with A smaller than V: A = V.  hit is left all zero.
+template <int NT>
+__device__ __forceinline__ void nl_dlb_update(unsigned char *__restrict__ act, unsigned char *__restrict__ hit,
+                                              int *__restrict__ list, NlState &S, int n, int na, int mode, const NlEnds &e,
+                                              int *s_w) {
+    const int tid = threadIdx.x;
+    if (e.ne == 0) {   // no lane held an improving move: hit is all zero
+        if (mode != TSP_DLB_CLOSE || na == n) return;
+        for (int v = tid; v < n; v += NT) { act[v] = 1; list[v] = v; }
+        if (tid == 0) { S.nact = n; S.closing_scans += 1; }
+        return;
+    }
+    const int lane = tid & 63, wv = tid >> 6;
+    int base = 0;
+    for (int c0 = 0; c0 < na; c0 += NT) {
+        const int slot = c0 + tid;
+        int v = -1;
+        bool keep = false;
+        if (slot < na) {
+            v = list[slot];
+            keep = hit[v] != 0;
+            hit[v] = 0;
+            if (!keep) act[v] = 0;
+        }
+        const u64 m = __ballot(keep);
+        if (lane == 0) s_w[wv] = __popcll(m);
+        __syncthreads();
+        int off = base;
+        for (int q = 0; q < NT / 64; ++q) {
+            const int c = s_w[q];
+            if (q < wv) off += c;
+            base += c;
+        }
+        if (keep) list[off + __popcll(m & ((1ull << lane) - 1ull))] = v;
+        __syncthreads();   // the next chunk rewrites s_w; the bitmap is complete behind the last one
+    }
+    if (tid == 0) {
+        // the bitmap keeps an end that is listed, or named twice, out
+        auto join = [&](int v) { if (!act[v]) { act[v] = 1; list[base++] = v; } };
+        join(e.e0); join(e.e1); join(e.e2); join(e.e3);
+        if (e.ne == 6) { join(e.e4); join(e.e5); }
+        S.nact = base;
+    }
+}
+
+// Decision over the candidates of k_nl_scan (parts2) and k_nl3_scan (parts3; either may be NULL: no kind of it is enabled), then
+// the move.  One workgroup per tour.  DLB: only the candidates of the workgroups that had lanes (|A| K of them, K lanes a
+// node), and behind the move the new active set; a decision without a move ends the descent only in mode TSP_DLB_ON or when
+// it looked at every node.
+template <bool DLB>
+__global__ __launch_bounds__(kNlPickThreads) void k_nl_pick_apply(int *__restrict__ orders, int *__restrict__ poss,
+                                                                  NlState *__restrict__ st, int n, int nparts,
+                                                                  const NlBest *__restrict__ parts2,
+                                                                  const NlBest *__restrict__ parts3, int K, NlDlb dlb) {
+    constexpr int NT = kNlPickThreads;
+    const int bt = blockIdx.x;
+    NlState &S = st[bt];
+    if (S.done) return;
+    __shared__ double sd[NT / 64];
+    __shared__ u64 sk[NT / 64];
+    const int tid = threadIdx.x;
+    if (S.max_moves >= 0 && S.moves >= S.max_moves) {
+        if (tid == 0) S.done = 1;
+        return;
+    }
+    const int na = DLB ? S.nact : n;
+    const int used = DLB ? (int)(((long long)na * K + 255) / 256) : nparts;
+    double bd = INFINITY; u64 bk = kNoKey;
+    for (int h = 0; h < 2; ++h) {
+        const NlBest *part = h ? parts3 : parts2;
+        if (!part) continue;
+        part += (size_t)bt * nparts;
+        for (int r = tid; r < used; r += NT) {
+            const NlBest q = part[r];
+            if (q.k != kNoKey && better(q.d, q.k, bd, bk)) { bd = q.d; bk = q.k; }
+        }
+    }
+    block_argmin<true>(bd, bk, sd, sk);
+    __syncthreads();
+    int *order = orders + (size_t)bt * n, *pos = poss + (size_t)bt * n;
+    if constexpr (!DLB) {
+        if (tid == 0) { S.decisions += 1; if (bk == kNoKey) S.done = 1; }
+        if (bk == kNoKey) return;
+        nl_apply_move<NT>(order, pos, S, n, bk);
+    } else {
+        __shared__ int s_w[NT / 64];
+        if (tid == 0) {
+            S.decisions += 1; S.active_nodes += na;
+            if (bk == kNoKey && (dlb.mode != TSP_DLB_CLOSE || na == n)) S.done = 1;
+        }
+        NlEnds e;
+        if (bk != kNoKey) {
+            e = nl_move_ends(order, pos, n, bk);
+            nl_apply_move<NT>(order, pos, S, n, bk);
+        }
+        const size_t at = (size_t)bt * n;
+        nl_dlb_update<NT>(dlb.act + at, dlb.hit + at, dlb.list + at, S, n, na, dlb.mode, e, s_w);
+    }
+}
+
 NlData *nl_data(tsp_dev_inst *inst) {
     if (!inst->nl_data) inst->nl_data = new NlData();
     return static_cast<NlData *>(inst->nl_data);
@@ -326,7 +446,7 @@ int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr) {
 
 // One whole decision of every tour that is not done, queued on the engine's stream: k_nl_prep, k_nl_scan when kinds has one of
 // its two (candidates in the first B x nparts entries of d_part), k_nl3_scan when it has the third (in the second), the pick.
-void tsp_nl_launch_decision(tsp_dev_tours *t, NlData *x, int kinds) {
+void tsp_nl_launch_decision(tsp_dev_tours *t, NlData *x, int kinds, int dlb_mode) {
     tsp_dev_inst *inst = t->inst;
     hipStream_t s = inst->ctx->stream;
     const int n = t->n, B = t->B;
@@ -335,13 +455,56 @@ void tsp_nl_launch_decision(tsp_dev_tours *t, NlData *x, int kinds) {
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         hipLaunchKernelGGL((k_nl_prep<WTC, INTC>), dim3((n + 255) / 256, B), dim3(256), 0, s, inst->d_coord, t->d_order, x->d_st, n,
                            x->d_E, x->d_rem);
-        if (low)
-            hipLaunchKernelGGL((k_nl_scan<WTC, INTC>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
-                               x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part);
+        if (low && !dlb_mode)
+            hipLaunchKernelGGL((k_nl_scan<WTC, INTC, false>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
+                               x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part, NlDlb{});
+        else if (low)
+            hipLaunchKernelGGL((k_nl_scan<WTC, INTC, true>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
+                               x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part, x->dlb(dlb_mode));
     });
-    if (three) tsp_nl3_launch_scan(t, x, parts3);
-    hipLaunchKernelGGL(k_nl_pick_apply, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
-                       low ? x->d_part : nullptr, three ? parts3 : nullptr);
+    if (three) tsp_nl3_launch_scan(t, x, parts3, dlb_mode);
+    if (!dlb_mode)
+        hipLaunchKernelGGL(k_nl_pick_apply<false>, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
+                           low ? x->d_part : nullptr, three ? parts3 : nullptr, x->K, NlDlb{});
+    else
+        hipLaunchKernelGGL(k_nl_pick_apply<true>, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
+                           low ? x->d_part : nullptr, three ? parts3 : nullptr, x->K, x->dlb(dlb_mode));
+}
+
+// What Descent::run needs to know of a descent with don't-look bits beyond its NlState: |A| at the start.
+namespace {
+struct DlbHooks : DescentPlain {
+    const int *nact;
+    void init(NlState &z, int b) const { z.nact = nact[b]; }
+};
+}  // namespace
+
+int tsp_nl_dlb_start(tsp_dev_inst *inst, NlData *x, int B, const unsigned char *active, std::vector<int> *nact) {
+    const int n = inst->n;
+    const size_t Bn = (size_t)B * n;
+    hipStream_t s = inst->ctx->stream;
+    if (!x->d_act) {
+        TSP_HIP_TRY(hipMalloc(&x->d_act, Bn));
+        TSP_HIP_TRY(hipMalloc(&x->d_hit, Bn));
+        TSP_HIP_TRY(hipMalloc(&x->d_alist, sizeof(int) * Bn));
+    }
+    std::vector<unsigned char> act(Bn);
+    std::vector<int> list(Bn, 0);
+    nact->assign((size_t)B, 0);
+    for (int b = 0; b < B; ++b) {
+        int c = 0;
+        for (int v = 0; v < n; ++v) {
+            const bool on = !active || active[(size_t)b * n + v] != 0;
+            act[(size_t)b * n + v] = on ? 1 : 0;
+            if (on) list[(size_t)b * n + c++] = v;
+        }
+        (*nact)[b] = c;
+    }
+    TSP_HIP_TRY(hipMemsetAsync(x->d_hit, 0, Bn, s));
+    TSP_HIP_TRY(hipMemcpyAsync(x->d_act, act.data(), Bn, hipMemcpyHostToDevice, s));
+    TSP_HIP_TRY(hipMemcpyAsync(x->d_alist, list.data(), sizeof(int) * Bn, hipMemcpyHostToDevice, s));
+    TSP_HIP_TRY(hipStreamSynchronize(s));   // the two host arrays end here
+    return TSP_OK;
 }
 
 int tsp_nl_check(const tsp_dev_inst *inst, int *kinds, int allowed, int B, const int *succ, int succ_stride, int64_t tour_stride,
@@ -373,7 +536,8 @@ int tsp_nl_prepare(tsp_dev_inst *inst, int B, NlData **out) {
 }
 
 int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
-               int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const NlState **states) {
+               int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const NlState **states, int dlb_mode,
+               const unsigned char *active) {
     int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
     Descent run;
@@ -383,8 +547,19 @@ int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int
     rc = tsp_nl_prepare(inst, B, &x);
     if (rc) return rc;
     const bool trivial = kinds == 0 || max_moves == 0;
-    const int status = run.run(x->d_st, x->h_st, x->d_cost, trivial, 256, max_moves, time_limit_s,
-                               [&](bool) { tsp_nl_launch_decision(run.t, x, kinds); });
+    int status;
+    if (!dlb_mode) {
+        status = run.run(x->d_st, x->h_st, x->d_cost, trivial, 256, max_moves, time_limit_s,
+                         [&](bool) { tsp_nl_launch_decision(run.t, x, kinds); });
+    } else {
+        std::vector<int> nact;
+        rc = tsp_nl_dlb_start(inst, x, B, active, &nact);
+        if (rc) return rc;
+        DlbHooks hooks;
+        hooks.nact = nact.data();
+        status = run.run(x->d_st, x->h_st, x->d_cost, trivial, 256, max_moves, time_limit_s,
+                         [&](bool) { tsp_nl_launch_decision(run.t, x, kinds, dlb_mode); }, hooks);
+    }
     if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
     for (int b = 0; b < B && stats; ++b) {
         const NlState &z = x->h_st[b];

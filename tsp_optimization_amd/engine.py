@@ -15,6 +15,7 @@ OK, WRONG_STARTING_NODE, TIME_LIMIT_EXCEEDED = 0, 1, 2
 E_ARG = -3
 NL_2OPT, NL_OROPT = 1, 2
 NL_3OPT = 4   # tsp_dev_nl_3opt only
+DLB_OFF, DLB_ON, DLB_CLOSE = 0, 1, 2   # don't-look bits of nl_3opt and ils
 NL_MAX_K, NL_DEFAULT_K = 16, 10
 HK_DEFAULT_ITERS, HK_DEFAULT_LAMBDA = 300, 2.0
 ALPHA_DEFAULT_K = 5
@@ -76,6 +77,16 @@ class IlsStats(C.Structure):
         d["moves_by_len"] = list(self.moves_by_len)
         d["moves_by_type"] = list(self.moves_by_type)
         return d
+
+
+class NlDlbStats(C.Structure):
+    _fields_ = Nl3OptStats._fields_ + [("active_nodes", C.c_int64), ("closing_scans", C.c_int64)]
+    as_dict = IlsStats.as_dict
+
+
+class IlsDlbStats(C.Structure):
+    _fields_ = IlsStats._fields_ + [("active_nodes", C.c_int64), ("closing_scans", C.c_int64)]
+    as_dict = IlsStats.as_dict
 
 
 class LbStats(C.Structure):
@@ -182,6 +193,10 @@ def lib():
         L.tsp_dev_ils.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_uint64, C.c_int64, C.c_int, C.c_int64,
                                   C.c_double, C.POINTER(IlsStats)]
         L.tsp_dev_ils_kick.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int64, C.c_uint64, C.c_int64, C.c_int]
+        L.tsp_dev_nl_3opt_dlb.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.POINTER(C.c_ubyte), C.c_int64,
+                                          C.c_double, C.POINTER(NlDlbStats)]
+        L.tsp_dev_ils_dlb.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_uint64, C.c_int64, C.c_int, C.c_int64,
+                                      C.c_double, C.c_int, C.POINTER(IlsDlbStats)]
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
@@ -207,7 +222,7 @@ EXPORTED = [
     "tsp_dev_multistart_allreduce_f64", "tsp_dev_multistart_allreduce_f64_group",
     "tsp_dev_or_opt", "tsp_dev_two_opt_or_opt",
     "tsp_dev_inst_knn_build", "tsp_dev_inst_knn_set", "tsp_dev_inst_knn_get", "tsp_dev_nl_opt", "tsp_dev_nl_3opt",
-    "tsp_dev_ils", "tsp_dev_ils_kick",
+    "tsp_dev_ils", "tsp_dev_ils_kick", "tsp_dev_nl_3opt_dlb", "tsp_dev_ils_dlb",
     "tsp_dev_one_tree", "tsp_dev_held_karp",
     "tsp_dev_inst_alpha_build", "tsp_dev_alpha_rows",
 ]
@@ -425,15 +440,25 @@ class Instance:
             return rc, succ2[0], float(o[0]), stats[0]
         return rc, succ2, o, stats
 
-    def nl_3opt(self, succ, obj=None, kinds=NL_2OPT | NL_OROPT | NL_3OPT, max_moves=-1, time_limit=-1.0):
+    def nl_3opt(self, succ, obj=None, kinds=NL_2OPT | NL_OROPT | NL_3OPT, max_moves=-1, time_limit=-1.0, dlb=DLB_OFF, active=None):
         """The list descent with the 3-opt kind (tsp_dev_nl_3opt): kinds is any non-empty subset of NL_2OPT | NL_OROPT | NL_3OPT.
         succ [n] or [B,n].  -> (status, succ', obj' (recomputed cost), stats dict(s)) as nl_opt, the stats with moves_3opt and
-        moves_by_type"""
+        moves_by_type.  dlb = DLB_ON or DLB_CLOSE: the descent with don't-look bits (tsp_dev_nl_3opt_dlb) from the active set
+        `active` ([n] or [B,n], non-zero = active; None: every node); the stats then carry active_nodes and closing_scans"""
         single, succ2 = self._tours(succ)
         B, n = succ2.shape
         o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
-        st = (Nl3OptStats * B)()
-        rc = lib().tsp_dev_nl_3opt(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
+        if dlb != DLB_OFF:
+            act = None
+            if active is not None:
+                act = np.ascontiguousarray(np.asarray(active).reshape(B, n) != 0, dtype=np.uint8)
+            st = (NlDlbStats * B)()
+            rc = lib().tsp_dev_nl_3opt_dlb(self._h, int(kinds), int(dlb), B, _i(succ2), 1, n, _d(o),
+                                           None if act is None else act.ctypes.data_as(C.POINTER(C.c_ubyte)), int(max_moves),
+                                           time_limit, st)
+        else:
+            st = (Nl3OptStats * B)()
+            rc = lib().tsp_dev_nl_3opt(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
         _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
         stats = [s.as_dict() for s in st]
         if single:
@@ -442,17 +467,23 @@ class Instance:
 
     # -- iterated local search (extension) ---------------------------------------------------
     def ils(self, succ, iterations, seed=0, span=0, kinds=NL_2OPT | NL_OROPT | NL_3OPT, max_moves_per_descent=-1, time_limit=-1.0,
-            obj=None):
+            obj=None, dlb=DLB_OFF):
         """Iterated local search (tsp_dev_ils): the list descent of nl_3opt, then `iterations` times a double-bridge kick within
         `span` nodes (0: the whole tour), the descent again and the better tour kept.  succ [n] or [B,n]: B chains, chain b with
         random stream b of `seed`.  -> (status, succ', obj' (recomputed cost of the incumbent), stats dict(s)): the nl_3opt
-        counters summed over the chain's descents, iterations, accepted, last_improved, start_cost"""
+        counters summed over the chain's descents, iterations, accepted, last_improved, start_cost.  dlb = DLB_ON or DLB_CLOSE: every
+        descent with don't-look bits (tsp_dev_ils_dlb), the stats with active_nodes and closing_scans"""
         single, succ2 = self._tours(succ)
         B, n = succ2.shape
         o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
-        st = (IlsStats * B)()
-        rc = lib().tsp_dev_ils(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations), int(span),
-                               int(max_moves_per_descent), time_limit, st)
+        if dlb != DLB_OFF:
+            st = (IlsDlbStats * B)()
+            rc = lib().tsp_dev_ils_dlb(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations),
+                                       int(span), int(max_moves_per_descent), time_limit, int(dlb), st)
+        else:
+            st = (IlsStats * B)()
+            rc = lib().tsp_dev_ils(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations),
+                                   int(span), int(max_moves_per_descent), time_limit, st)
         _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
         stats = [s.as_dict() for s in st]
         if single:

@@ -141,7 +141,9 @@ static __thread tsp_or_opt_stats t_or_stats;   /* the Or-opt phases of the last 
 static __thread tsp_nl_opt_stats t_nl_stats;   /* the last alg_nl_opt */
 static __thread tsp_nl3_opt_stats t_nl3_stats; /* the last alg_3opt */
 static __thread tsp_ils_stats t_ils_stats;     /* the winning chain of the last alg_ils */
+static __thread int64_t t_dlb_active, t_dlb_closing;   /* active_nodes, closing_scans of the last alg_3opt or alg_ils */
 static int g_ils_iters = 100, g_ils_span = 50, g_ils_chains = 1;   /* tsp_host_set_ils */
+static int g_dlb = TSP_DLB_OFF;                /* don't-look bits of alg_3opt and alg_ils (tsp_host_set_dlb) */
 static int g_knn_k = TSP_NL_DEFAULT_K;         /* list length of alg_nl_opt (tsp_host_set_knn) */
 static int g_alpha_k = 0, g_alpha_iters = 0;   /* alpha lists instead (tsp_host_set_alpha); 0 = nearest-neighbour lists */
 
@@ -585,21 +587,36 @@ static int lists_locked(instance *inst, tsp_dev_inst *dev, double obj) {
     return rc;
 }
 
-/* 2-opt + Or-opt + 3-opt over the lists alg_nl_opt would use */
+int tsp_host_set_dlb(int mode) {
+    if (mode != TSP_DLB_OFF && mode != TSP_DLB_ON && mode != TSP_DLB_CLOSE) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_dlb = mode;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+void tsp_host_last_dlb_stats(int64_t *active_nodes, int64_t *closing_scans) {
+    if (active_nodes) *active_nodes = t_dlb_active;
+    if (closing_scans) *closing_scans = t_dlb_closing;
+}
+
+/* 2-opt + Or-opt + 3-opt over the lists alg_nl_opt would use, from every node active under tsp_host_set_dlb */
 int alg_3opt(instance *inst) {
-    tsp_nl3_opt_stats st;
+    tsp_nl_dlb_stats st;
     memset(&st, 0, sizeof st);
     double obj = inst->solution.obj_best;
     pthread_mutex_lock(&g_lock);
     tsp_dev_inst *dev = dev_inst_locked(inst);
     int rc = lists_locked(inst, dev, obj);
     if (rc == 0)
-        rc = tsp_dev_nl_3opt(dev, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, 1, &inst->solution.edges[0].j, 2,
-                             2 * (int64_t)inst->num_nodes, &obj, -1, limit_of(inst), &st);
+        rc = tsp_dev_nl_3opt_dlb(dev, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, g_dlb, 1, &inst->solution.edges[0].j, 2,
+                                 2 * (int64_t)inst->num_nodes, &obj, NULL, -1, limit_of(inst), &st);
     pthread_mutex_unlock(&g_lock);
     if (rc < 0) dev_fail("tsp_dev_nl_3opt", rc);
     inst->solution.obj_best = obj;
-    t_nl3_stats = st;
+    memcpy(&t_nl3_stats, &st, sizeof t_nl3_stats);   /* tsp_nl_dlb_stats starts as tsp_nl3_opt_stats */
+    t_dlb_active = st.active_nodes;
+    t_dlb_closing = st.closing_scans;
     if (rc == TIME_LIMIT_EXCEEDED) LOG_I("3-opt heuristics time exceeded");
     return rc;
 }
@@ -628,15 +645,15 @@ int alg_ils(instance *inst) {
     const int B = g_ils_chains;
     int *succ = (int *)malloc(sizeof(int) * (size_t)B * n);
     double *objs = (double *)calloc((size_t)B, sizeof *objs);
-    tsp_ils_stats *st = (tsp_ils_stats *)calloc((size_t)B, sizeof *st);
+    tsp_ils_dlb_stats *st = (tsp_ils_dlb_stats *)calloc((size_t)B, sizeof *st);
     if (!succ || !objs || !st) LOG_E("out of memory");
     for (int b = 0; b < B; b++)
         for (int v = 0; v < n; v++) succ[(size_t)b * n + v] = inst->solution.edges[v].j;
     tsp_dev_inst *dev = dev_inst_locked(inst);
     int rc = lists_locked(inst, dev, obj);
     if (rc == 0)
-        rc = tsp_dev_ils(dev, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, 1, n, objs, (uint64_t)(unsigned)inst->params.seed,
-                         g_ils_iters, g_ils_span, -1, limit_of(inst), st);
+        rc = tsp_dev_ils_dlb(dev, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, 1, n, objs, (uint64_t)(unsigned)inst->params.seed,
+                             g_ils_iters, g_ils_span, -1, limit_of(inst), g_dlb, st);
     pthread_mutex_unlock(&g_lock);
     if (rc < 0) dev_fail("tsp_dev_ils", rc);
     int win = 0;
@@ -644,7 +661,9 @@ int alg_ils(instance *inst) {
         if (objs[b] < objs[win]) win = b;
     for (int v = 0; v < n; v++) { inst->solution.edges[v].i = v; inst->solution.edges[v].j = succ[(size_t)win * n + v]; }
     inst->solution.obj_best = objs[win];
-    t_ils_stats = st[win];
+    memcpy(&t_ils_stats, &st[win], sizeof t_ils_stats);   /* tsp_ils_dlb_stats starts as tsp_ils_stats */
+    t_dlb_active = st[win].active_nodes;
+    t_dlb_closing = st[win].closing_scans;
     free(succ); free(objs); free(st);
     if (rc == TIME_LIMIT_EXCEEDED) LOG_I("iterated local search time exceeded");
     return rc;
