@@ -31,93 +31,6 @@ def _tour(succ):
     return succ, order, pos, pred
 
 
-def _two_opt(D, succ, pred, v, u):
-    """the two 2-opt moves of the entries (v, u): {i, j} = {v, u} and {i1, j1} = {v, u} -> (owner, delta, key)"""
-    n = len(succ)
-    out = []
-    for x, y in ((v, u), (pred[v], pred[u])):
-        i, j = np.minimum(x, y), np.maximum(x, y)
-        i1, j1 = succ[i], succ[j]
-        ok = (i != j) & (j != i1) & (j1 != i)
-        delta = ((_d(D, i, j) + _d(D, i1, j1)) - _d(D, i, i1)) - _d(D, j, j1)
-        out.append((v[ok], delta[ok], (i * n + j)[ok]))
-    return out
-
-
-def _or_opt(D, succ, order, pos, pred, v, u):
-    """the Or-opt moves one of whose attaching edges is {v, u}: for (x, y) = (v, u) and (u, v), with the edge x -> y in the new
-    tour, (a, f) = (x, y) and (l, b) = (x, y) forward, (a, l) = (x, y) and (f, b) = (x, y) reversed -> (owner, delta, key)"""
-    n = len(succ)
-    out = []
-    for x, y in ((v, u), (u, v)):
-        for L in (1, 2, 3):
-            back = lambda z: order[(pos[z] - (L - 1)) % n]   # noqa: E731  the first node of the segment that ends at z
-            for o, f, a in ((0, y, x), (0, back(x), pred[y]), (1, back(y), x), (1, x, pred[y])):
-                if o == 1 and L == 1:
-                    continue
-                pf = pos[f]
-                ok = ((pos[a] - pf + 1) % n) > L          # a not in {p, f .. l}
-                p, l, s, b = order[(pf - 1) % n], order[(pf + L - 1) % n], order[(pf + L) % n], succ[a]
-                rem = (_d(D, p, f) + _d(D, l, s)) - _d(D, p, s)
-                ins = (_d(D, a, f) + _d(D, l, b)) if o == 0 else (_d(D, a, l) + _d(D, f, b))
-                delta = (ins - _d(D, a, b)) - rem
-                out.append((v[ok], delta[ok], R.key(f, L, a, o, n)[ok]))
-    return out
-
-
-def _three_opt(D, succ, order, pos, pred, nbr, act):
-    """nl3_opt_ref.sparse_moves for the entries of the nodes `act` alone, with the owner p of every move -> (owner, delta, key)"""
-    n = len(succ)
-    K = nbr.shape[1]
-    if len(act) == 0:
-        return []
-    p, k1, k2, su, sw = [g.reshape(-1) for g in np.meshgrid(act, np.arange(K), np.arange(K), [0, 1], [0, 1], indexing="ij")]
-    q = succ[p]
-    u, w = nbr[p, k1], nbr[q, k2]
-
-    def apart(x, y):
-        gap = (pos[x] - pos[y]) % n
-        return (gap != 0) & (gap != 1) & (gap != n - 1)
-
-    tY, hY = np.where(su == 0, u, pred[u]), np.where(su == 0, succ[u], u)
-    tZ, hZ = np.where(sw == 0, w, pred[w]), np.where(sw == 0, succ[w], w)
-    yo, zo = np.where(su == 0, hY, tY), np.where(sw == 0, hZ, tZ)
-    keep = apart(p, u) & apart(q, w) & apart(yo, zo) & (tY != p) & (tZ != p) & (tY != tZ)
-    p, su, sw, tY, tZ = (z[keep] for z in (p, su, sw, tY, tZ))
-    if len(p) == 0:
-        return []
-    tails = np.stack([p, tY, tZ], axis=1)
-    rows = np.arange(len(p))
-    pa = pos[tails[rows, np.argmin(tails, axis=1)]]
-    off = (pos[tails] - pa[:, None]) % n
-    role = (off[:, :, None] > off[:, None, :]).sum(axis=2)
-    rX, rY, rZ = role[:, 0], role[:, 1], role[:, 2]
-    partner = np.zeros((len(p), 6), dtype=np.int64)
-    for s, t in ((rX * 2, rY * 2 + su), (rX * 2 + 1, rZ * 2 + sw), (rY * 2 + 1 - su, rZ * 2 + 1 - sw)):
-        partner[rows, s] = t
-        partner[rows, t] = s
-    T = np.full(len(p), -1, dtype=np.int64)
-    T[(partner[:, 0] == 3) & (partner[:, 4] == 1)] = 0
-    T[(partner[:, 0] == 3) & (partner[:, 4] == 2)] = 3
-    T[(partner[:, 0] == 2) & (partner[:, 1] == 4)] = 1
-    T[(partner[:, 0] == 4) & (partner[:, 3] == 1)] = 2
-    by_role = np.empty((len(p), 3), dtype=np.int64)
-    by_role[rows[:, None], role] = tails
-    a, b, c = by_role[:, 0], by_role[:, 1], by_role[:, 2]
-    s1, s2, s3 = (pos[b] - pos[a]) % n, (pos[c] - pos[b]) % n, (pos[a] - pos[c]) % n
-    out = []
-    for Tq in range(4):
-        twin = (s1 == 1, s3 == 1, s2 == 1, s1 == 1)
-        if Tq == 0:
-            sel = (T == 0) | ((T == 3) & (s1 == 1)) | ((T == 2) & (s2 == 1)) | ((T == 1) & (s3 == 1))
-        else:
-            sel = (T == Tq) | ((T == 0) & twin[Tq])
-        move, delta, k, _ = N3._evaluate(D, succ, pos, a[sel], b[sel], c[sel], Tq)
-        assert move.all()
-        out.append((p[sel], delta, k))
-    return out
-
-
 def candidates(D, succ, nbr, kinds, active):
     """The improving candidates of the active nodes -> (owner, delta, kind, key) arrays."""
     succ, order, pos, pred = _tour(succ)
@@ -130,13 +43,13 @@ def candidates(D, succ, nbr, kinds, active):
     u = nbr[act].reshape(-1)
     ok = u != v
     v, u = v[ok], u[ok]
+    d = lambda x, y: _d(D, x, y)   # noqa: E731
     found = []
-    if kinds & N3.NL_2OPT:
-        found += [(0,) + c for c in _two_opt(D, succ, pred, v, u)]
-    if kinds & N3.NL_OROPT:
-        found += [(1,) + c for c in _or_opt(D, succ, order, pos, pred, v, u)]
+    for kind in (0, 1):
+        if kinds & (N3.NL_2OPT, N3.NL_OROPT)[kind]:
+            found += [(kind,) + c for c in NL.entry_moves(v, u, succ, order, pos, pred, d, kind)]
     if kinds & N3.NL_3OPT:
-        found += [(2,) + c for c in _three_opt(D, succ, order, pos, pred, nbr, act)]
+        found.append((2,) + N3.sparse_moves(D, succ, nbr, owners=act, with_owner=True))
     own = np.concatenate([c[1] for c in found] + [np.zeros(0, dtype=np.int64)]).astype(np.int64)
     delta = np.concatenate([c[2] for c in found] + [np.zeros(0)])
     kind = np.concatenate([np.full(len(c[1]), c[0], dtype=np.int64) for c in found] + [np.zeros(0, dtype=np.int64)])

@@ -128,20 +128,23 @@ def decide3(D, succ, nbr):
     return _best(*moves(D, succ, nbr))
 
 
-def sparse_moves(D, succ, nbr):
+def sparse_moves(D, succ, nbr, owners=None, with_owner=False):
     """The moves of the list neighbourhood as the kernel finds them: (p, k1, k2) and the <= 4 choices of the removed edges at
     u = nbr[p][k1] and w = nbr[succ p][k2] ((u, succ u) or (pred u, u); the same at w), the third new edge forced.  A move with a
     segment of one node has the same new edges as a second type (0 and 3 for S1, 0 and 2 for S2, 0 and 1 for S3): both are
-    moves of the neighbourhood, so both are offered.  -> (delta, key) arrays, a move as often as it is reached"""
+    moves of the neighbourhood, so both are offered.  owners: the nodes p whose entries are walked (default: all).
+    -> (delta, key) arrays, a move as often as it is reached; with_owner: (owner p, delta, key)"""
     succ, order, pos = _tour(succ)
     n = len(succ)
-    if n < 5:
-        return np.zeros(0), np.zeros(0, dtype=np.int64)
+    own = np.arange(n) if owners is None else np.asarray(owners, dtype=np.int64)
+    if n < 5 or len(own) == 0:
+        none = np.zeros(0, dtype=np.int64)
+        return ((none,) if with_owner else ()) + (np.zeros(0), none)
     nbr = np.asarray(nbr, dtype=np.int64)
     K = nbr.shape[1]
     pred = np.empty(n, dtype=np.int64)
     pred[succ] = np.arange(n)
-    p, k1, k2, su, sw = [g.reshape(-1) for g in np.meshgrid(np.arange(n), np.arange(K), np.arange(K), [0, 1], [0, 1], indexing="ij")]
+    p, k1, k2, su, sw = [g.reshape(-1) for g in np.meshgrid(own, np.arange(K), np.arange(K), [0, 1], [0, 1], indexing="ij")]
     q = succ[p]
     u, w = nbr[p, k1], nbr[q, k2]
 
@@ -175,7 +178,7 @@ def sparse_moves(D, succ, nbr):
     by_role[rows[:, None], role] = tails
     a, b, c = by_role[:, 0], by_role[:, 1], by_role[:, 2]
     s1, s2, s3 = (pos[b] - pos[a]) % n, (pos[c] - pos[b]) % n, (pos[a] - pos[c]) % n
-    ds, ks = [], []
+    ps, ds, ks = [], [], []
     for Tq in range(4):
         twin = (s1 == 1, s3 == 1, s2 == 1, s1 == 1)   # type Tq <-> its twin when that segment has one node
         if Tq == 0:
@@ -184,9 +187,10 @@ def sparse_moves(D, succ, nbr):
             sel = (T == Tq) | ((T == 0) & twin[Tq])
         move, delta, k, _ = _evaluate(D, succ, pos, a[sel], b[sel], c[sel], Tq)
         assert move.all()
+        ps.append(p[sel])
         ds.append(delta)
         ks.append(k)
-    return np.concatenate(ds), np.concatenate(ks)
+    return ((np.concatenate(ps),) if with_owner else ()) + (np.concatenate(ds), np.concatenate(ks))
 
 
 def decide3_sparse(D, succ, nbr):

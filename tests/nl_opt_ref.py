@@ -154,6 +154,35 @@ def _take(best, delta, key, kind):
     return c if _better(c, best) else best
 
 
+def entry_moves(v, u, succ, order, pos, pred, d, kind):
+    """The delta expressions of the list entries (v, u), arrays with u != v, of one kind: 0, the two 2-opt moves {i, j} = {v, u}
+    and {i1, j1} = {v, u}; 1, the Or-opt moves one of whose attaching edges is {v, u}: for (x, y) = (v, u) and (u, v), with the
+    edge x -> y in the new tour, (a, f) = (x, y) and (l, b) = (x, y) forward, (a, l) = (x, y) and (f, b) = (x, y) reversed.
+    d(x, y): the distance of two arrays of nodes.  Yields (owner v, delta, key) per expression."""
+    n = len(succ)
+    if kind == 0:
+        for x, y in ((v, u), (pred[v], pred[u])):
+            i, j = np.minimum(x, y), np.maximum(x, y)
+            i1, j1 = succ[i], succ[j]
+            ok = (i != j) & (j != i1) & (j1 != i)
+            own, i, j, i1, j1 = v[ok], i[ok], j[ok], i1[ok], j1[ok]
+            yield own, ((d(i, j) + d(i1, j1)) - d(i, i1)) - d(j, j1), i * n + j
+        return
+    for x, y in ((v, u), (u, v)):
+        for L in (1, 2, 3):
+            back = lambda z: order[(pos[z] - (L - 1)) % n]   # noqa: E731  the first node of the segment that ends at z
+            for o, f, a in ((0, y, x), (0, back(x), pred[y]), (1, back(y), x), (1, x, pred[y])):
+                if o == 1 and L == 1:
+                    continue
+                ok = ((pos[a] - pos[f] + 1) % n) > L      # a not in {p, f .. l}
+                own, f, a = v[ok], f[ok], a[ok]
+                pf = pos[f]
+                p, l, s, b = order[(pf - 1) % n], order[(pf + L - 1) % n], order[(pf + L) % n], succ[a]
+                rem = (d(p, f) + d(l, s)) - d(p, s)
+                ins = (d(a, f) + d(l, b)) if o == 0 else (d(a, l) + d(f, b))
+                yield own, (ins - d(a, b)) - rem, R.key(f, L, a, o, n)
+
+
 def decide_sparse(xy, succ, nbr, kinds, integer_cost=1):
     """decide() for EUC_2D from the related pairs alone: every move is generated from the list edge that puts it into the
     neighbourhood and then evaluated from its own definition -> (delta, kind, key) or None."""
@@ -162,44 +191,20 @@ def decide_sparse(xy, succ, nbr, kinds, integer_cost=1):
     n = len(succ)
     kinds = effective_kinds(kinds, n)
     nbr = np.asarray(nbr, dtype=np.int64)
-    K = nbr.shape[1]
     order = R.tour_order(succ)
     pos = np.empty(n, dtype=np.int64)
     pos[order] = np.arange(n)
     pred = np.empty(n, dtype=np.int64)
     pred[succ] = np.arange(n)
-    # directed related pairs, both directions of every list entry, once each
-    v = np.repeat(np.arange(n, dtype=np.int64), K)
+    # the related pairs, once each: the enumeration takes both directions of an entry
+    v = np.repeat(np.arange(n, dtype=np.int64), nbr.shape[1])
     u = nbr.reshape(-1)
-    code = np.unique(np.concatenate([v * n + u, u * n + v]))
-    x, y = code // n, code % n
-    d = lambda a, b: _euc(xy, a, b, integer_cost)   # noqa: E731
+    code = np.unique(np.minimum(v, u) * n + np.maximum(v, u))
+    v, u = code // n, code % n
+    v, u = v[v != u], u[v != u]
     best = None
-    if kinds & NL_2OPT:
-        for i, j in ((x, y), (pred[x], pred[y])):
-            keep = i < j               # every unordered pair appears in both directions
-            i, j = i[keep], j[keep]
-            i1, j1 = succ[i], succ[j]
-            keep = (j != i1) & (j1 != i)
-            i, j, i1, j1 = i[keep], j[keep], i1[keep], j1[keep]
-            delta = ((d(i, j) + d(i1, j1)) - d(i, i1)) - d(j, j1)
-            best = _take(best, delta, i * n + j, 0)
-    if kinds & NL_OROPT:
-        for L in (1, 2, 3):
-            for o in ((0,) if L == 1 else (0, 1)):
-                # the attaching edge x -> y is (a, first node of the inserted segment) or (last node of it, b)
-                for at_a in (True, False):
-                    if at_a:
-                        a = x
-                        f = y if o == 0 else order[(pos[y] - (L - 1)) % n]
-                    else:
-                        a = pred[y]
-                        f = order[(pos[x] - (L - 1)) % n] if o == 0 else x
-                    pf = pos[f]
-                    keep = ((pos[a] - pf + 1) % n) > L
-                    a, f, pf = a[keep], f[keep], pf[keep]
-                    p, l, s, b = order[(pf - 1) % n], order[(pf + L - 1) % n], order[(pf + L) % n], succ[a]
-                    rem = (d(p, f) + d(l, s)) - d(p, s)
-                    ins = ((d(a, f) + d(l, b)) - d(a, b)) if o == 0 else ((d(a, l) + d(f, b)) - d(a, b))
-                    best = _take(best, ins - rem, ((f * 3 + (L - 1)) * n + a) * 2 + o, 1)
+    for kind in (0, 1):
+        if kinds & (NL_2OPT, NL_OROPT)[kind]:
+            for _, delta, key in entry_moves(v, u, succ, order, pos, pred, lambda a, b: _euc(xy, a, b, integer_cost), kind):
+                best = _take(best, delta, key, kind)
     return best

@@ -388,3 +388,62 @@ def test_recorded_runs_and_the_host_library(eng, ctx):
         L.tsp_host_set_ils(100, 50, 1)
         L.tsp_host_set_knn(eng.NL_DEFAULT_K)
         L.tsp_host_shutdown()
+
+
+# ---- 6. the stats records of the five entry points -----------------------------------------------------------------------------------
+
+def test_a_record_ends_where_its_type_ends(eng, ctx):
+    """Each entry point through the library itself with B + 1 records of its own type, all bytes 0xA5, and B passed: the record
+    behind the last stays as it was, the B records equal what the same call returns through Instance, and the fields a record
+    shares with the next smaller type equal that type's entry point where the header promises "move for move".  n = 7 is the
+    chains' path without a kick, n = 12 has kicks.  The two clocks (seconds, device_ms) differ between any two calls and are
+    left out of every comparison."""
+    L = eng.lib()
+    ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    K, B, IT, SEED = 3, 2, 3, 5
+    clocks = ("seconds", "device_ms")
+    for n in (7, 12):
+        xy, D, inst, nbr = _rand(eng, ctx, n, K, hi=1000)
+        rng = np.random.default_rng(n)
+        starts = np.stack([random_tour(n, rng) for _ in range(B)])
+
+        def raw(fn, typ, kinds, pre, post):
+            succ, obj = starts.copy(), np.zeros(B)
+            st = (typ * (B + 1))()
+            C.memset(st, 0xA5, C.sizeof(st))
+            assert fn(inst._h, kinds, *pre, B, succ.ctypes.data_as(ip), 1, n, obj.ctypes.data_as(dp), *post, st) == 0
+            assert bytes(st[B]) == b"\xa5" * C.sizeof(typ), (fn.__name__, n, "a write behind the last record")
+            return [st[b].as_dict() for b in range(B)], succ, obj
+
+        def same(got, want, keys=None):
+            gst, gs, go = got
+            wst, ws, wo = want if len(want) == 3 else (want[3], want[1], want[2])   # raw(), or Instance's (rc, succ, obj, stats)
+            assert (gs == ws).all() and (go == wo).all()
+            for b in range(B):
+                for k in (keys or gst[b].keys()):
+                    assert k in clocks or gst[b][k] == wst[b][k], (n, b, k, gst[b][k], wst[b][k])
+                assert keys or gst[b].keys() == wst[b].keys()
+
+        nl = raw(L.tsp_dev_nl_opt, eng.NlOptStats, 3, (), (-1, LIMIT))
+        same(nl, inst.nl_opt(starts, kinds=3, time_limit=LIMIT))
+        nl3 = raw(L.tsp_dev_nl_3opt, eng.Nl3OptStats, 7, (), (-1, LIMIT))
+        same(nl3, inst.nl_3opt(starts, time_limit=LIMIT))
+        dlb = raw(L.tsp_dev_nl_3opt_dlb, eng.NlDlbStats, 7, (DR.ON,), (None, -1, LIMIT))
+        same(dlb, inst.nl_3opt(starts, time_limit=LIMIT, dlb=DR.ON))
+        ils = raw(L.tsp_dev_ils, eng.IlsStats, 7, (), (SEED, IT, 0, -1, LIMIT))
+        same(ils, inst.ils(starts, IT, seed=SEED, time_limit=LIMIT))
+        ilsd = raw(L.tsp_dev_ils_dlb, eng.IlsDlbStats, 7, (), (SEED, IT, 0, -1, LIMIT, DR.CLOSE))
+        same(ilsd, inst.ils(starts, IT, seed=SEED, time_limit=LIMIT, dlb=DR.CLOSE))
+        for st, _, obj in (ils, ilsd):
+            for b in range(B):
+                assert st[b]["iterations"] == (IT if n >= 8 else 0) and st[b]["accepted"] <= st[b]["iterations"]
+                if n < 8:
+                    assert st[b]["last_improved"] == -1 and st[b]["start_cost"] == obj[b]
+        # the shared fields: tsp_dev_nl_3opt within kinds 3 is tsp_dev_nl_opt, mode 0 of the two newest is the call without a mode
+        same(raw(L.tsp_dev_nl_3opt, eng.Nl3OptStats, 3, (), (-1, LIMIT)), nl, keys=[k for k, _ in eng.NlOptStats._fields_])
+        off = raw(L.tsp_dev_nl_3opt_dlb, eng.NlDlbStats, 7, (DR.OFF,), (None, -1, LIMIT))
+        same(off, nl3, keys=[k for k, _ in eng.Nl3OptStats._fields_])
+        offi = raw(L.tsp_dev_ils_dlb, eng.IlsDlbStats, 7, (), (SEED, IT, 0, -1, LIMIT, DR.OFF))
+        same(offi, ils, keys=[k for k, _ in eng.IlsStats._fields_])
+        assert all(q["active_nodes"] == q["closing_scans"] == 0 for q in off[0] + offi[0])
+        inst.close()

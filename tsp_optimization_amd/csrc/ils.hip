@@ -5,11 +5,10 @@
 //          workgroup per chain; it returns at once unless the chain's descent has just ended: then the cost of the work tour,
 //          work -> incumbent or back, the next kick on order/pos and the descent re-armed, or the chain marked finished).
 // The work tours are the instance's scratch tours handle, the incumbents a second order/pos per chain.  An iteration moves
-// nothing to the host, which queues decisions and polls both control blocks as it does for a single descent.
+// nothing to the host, which queues decisions and polls both control blocks as it does for a single descent.  The records are
+// written by tsp_nl_write_stats (nl_opt.hip) from both control blocks; below eight nodes the call is tsp_nl_run.
 #include "descent.hpp"
 #include "nl_common.hpp"
-
-#include <cstddef>
 
 #pragma clang fp contract(off)
 
@@ -130,26 +129,12 @@ __global__ __launch_bounds__(kNlPickThreads) void k_ils_step(const double2 *__re
     }
 }
 
-// the stats record of a chain from its two control blocks
-void fill_stats(tsp_ils_stats &o, const NlState &z, const IlsState &q, double seconds, float device_ms) {
-    memset(&o, 0, sizeof(tsp_ils_stats));
-    o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
-    for (int k = 0; k < 3; ++k) o.moves_by_len[k] = z.moves_len[k];
-    o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
-    o.seconds = seconds; o.device_ms = device_ms;
-    o.moves_3opt = z.moves_3opt;
-    for (int k = 0; k < 4; ++k) o.moves_by_type[k] = z.moves_type[k];
-    o.iterations = q.it < 0 ? 0 : q.it; o.accepted = q.accepted; o.last_improved = q.last_improved;
-    o.start_cost = q.start_cost;
-}
-
 // What Descent::run needs to know of a chain beyond its NlState.
-struct IlsHooks {
+struct IlsHooks : NlHooks {   // nact: |A| of the first descent
     tsp_dev_tours *t;
     NlData *x;
     long long M;
-    const int *nact;   // don't-look bits: |A| of the first descent; else NULL
-    void init(NlState &z, int b) const { z.done = M == 0 ? 1 : 0; if (nact) z.nact = nact[b]; }
+    void init(NlState &z, int b) const { z.done = M == 0 ? 1 : 0; NlHooks::init(z, b); }
     int fetch(hipStream_t s) const {
         TSP_HIP_TRY(hipMemcpyAsync(x->h_ils, x->d_ils, sizeof(IlsState) * t->B, hipMemcpyDeviceToHost, s));
         return TSP_OK;
@@ -171,24 +156,10 @@ bool bad_span(int span) { return span >= 1 && span <= 7; }
 
 }  // namespace
 
-static_assert(offsetof(tsp_ils_stats, iterations) == sizeof(tsp_nl3_opt_stats), "tsp_ils_stats starts as tsp_nl3_opt_stats");
-static_assert(offsetof(tsp_ils_dlb_stats, active_nodes) == sizeof(tsp_ils_stats), "tsp_ils_dlb_stats starts as tsp_ils_stats");
-
-// What both entry points do.  stats (may be NULL): B records `stride` bytes apart that start with the layout of tsp_ils_stats; with
-// dlb_mode != 0 they are tsp_ils_dlb_stats.
+// What both entry points do; `out` names their record type.
 static int ils_run(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj, uint64_t seed,
-                   int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, int dlb_mode, void *stats_,
-                   size_t stride) {
-    char *stats = static_cast<char *>(stats_);
-    auto record = [&](int b, const NlState &z, const IlsState &q, double seconds, float device_ms) -> tsp_ils_stats & {
-        tsp_ils_stats &o = *reinterpret_cast<tsp_ils_stats *>(stats + (size_t)b * stride);
-        fill_stats(o, z, q, seconds, device_ms);
-        if (dlb_mode) {
-            tsp_ils_dlb_stats &d = *reinterpret_cast<tsp_ils_dlb_stats *>(&o);
-            d.active_nodes = z.active_nodes; d.closing_scans = z.closing_scans;
-        }
-        return o;
-    };
+                   int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, int dlb_mode,
+                   const NlStatsOut &out) {
     const int allowed = TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT;
     const int asked = kinds;
     int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
@@ -196,20 +167,8 @@ static int ils_run(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_str
     if (iterations < 0 || bad_span(span)) return TSP_DEV_E_ARG;
     const int n = inst->n;
     const long long M = max_moves_per_descent < 0 ? -1 : max_moves_per_descent;
-    if (n < 8) {   // no kick: the descent alone
-        const NlState *z = nullptr;
-        std::vector<tsp_nl3_opt_stats> st3((size_t)B);
-        const int status = tsp_nl_run(inst, asked, allowed, B, succ, succ_stride, tour_stride, obj, M, time_limit_s,
-                                      st3.data(), sizeof(tsp_nl3_opt_stats), &z, dlb_mode, nullptr);
-        if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
-        for (int b = 0; b < B && stats; ++b) {
-            IlsState q;
-            memset(&q, 0, sizeof q);
-            q.last_improved = -1; q.cost = q.start_cost = obj[b];
-            record(b, z[b], q, st3[b].seconds, (float)st3[b].device_ms);
-        }
-        return status;
-    }
+    if (n < 8)   // no kick: the descent alone
+        return tsp_nl_run(inst, asked, allowed, B, succ, succ_stride, tour_stride, obj, M, time_limit_s, out, dlb_mode, nullptr);
     Descent run;
     rc = run.open(inst, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
@@ -240,27 +199,24 @@ static int ils_run(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_str
         rc = tsp_nl_dlb_start(inst, x, B, nullptr, &nact);
         if (rc) return rc;
     }
-    const IlsHooks hooks{t, x, M, dlb_mode ? nact.data() : nullptr};
+    IlsHooks hooks;
+    hooks.nact = dlb_mode ? nact.data() : nullptr; hooks.t = t; hooks.x = x; hooks.M = M;
     const int status = run.run(x->d_st, x->h_st, x->d_cost, false, 256, M, time_limit_s,
                                [&](bool) {
                                    tsp_nl_launch_decision(t, x, kinds, dlb_mode);
                                    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-                                       if (!dlb_mode)
-                                           hipLaunchKernelGGL((k_ils_step<WTC, INTC, false>), dim3(B), dim3(kNlPickThreads), 0, s,
-                                                              inst->d_coord, t->d_order, t->d_pos, x->d_inc, x->d_st, x->d_ils, n, W,
-                                                              (u64)seed, (long long)iterations, M, NlDlb{});
-                                       else
-                                           hipLaunchKernelGGL((k_ils_step<WTC, INTC, true>), dim3(B), dim3(kNlPickThreads), 0, s,
+                                       TSP_DISPATCH_DLB(dlb_mode, {
+                                           hipLaunchKernelGGL((k_ils_step<WTC, INTC, DLBC>), dim3(B), dim3(kNlPickThreads), 0, s,
                                                               inst->d_coord, t->d_order, t->d_pos, x->d_inc, x->d_st, x->d_ils, n, W,
                                                               (u64)seed, (long long)iterations, M, x->dlb(dlb_mode));
+                                       });
                                    });
                                },
                                hooks);
     if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
-    for (int b = 0; b < B && stats; ++b) {
-        tsp_ils_stats &o = record(b, x->h_st[b], x->h_ils[b], wall_s() - run.t0, run.device_ms);
-        if (x->h_ils[b].it < 0) o.start_cost = obj[b];   // the limit ended the first descent: the caller's tour
-    }
+    const double seconds = wall_s() - run.t0;
+    // a chain whose first descent the limit ended starts from the caller's tour, whose cost obj[b] then is
+    for (int b = 0; b < B; ++b) tsp_nl_write_stats(out, b, x->h_st[b], &x->h_ils[b], obj[b], seconds, run.device_ms);
     return status;
 }
 
@@ -269,16 +225,16 @@ extern "C" {
 int tsp_dev_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj, uint64_t seed,
                 int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, tsp_ils_stats *stats) {
     return ils_run(inst, kinds, B, succ, succ_stride, tour_stride, obj, seed, iterations, span, max_moves_per_descent, time_limit_s,
-                   TSP_DLB_OFF, stats, sizeof *stats);
+                   TSP_DLB_OFF, NlStatsOut{stats, sizeof *stats, kNlStats3 | kNlStatsChain});
 }
 
 int tsp_dev_ils_dlb(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
                     uint64_t seed, int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s, int dlb_mode,
                     tsp_ils_dlb_stats *stats) {
     if (dlb_mode != TSP_DLB_OFF && dlb_mode != TSP_DLB_ON && dlb_mode != TSP_DLB_CLOSE) return TSP_DEV_E_ARG;
-    for (int b = 0; b < B && stats; ++b) stats[b].active_nodes = stats[b].closing_scans = 0;
+    for (int b = 0; b < B && stats; ++b) stats[b].active_nodes = stats[b].closing_scans = 0;   // also when a check below fails
     return ils_run(inst, kinds, B, succ, succ_stride, tour_stride, obj, seed, iterations, span, max_moves_per_descent, time_limit_s,
-                   dlb_mode, stats, sizeof *stats);
+                   dlb_mode, NlStatsOut{stats, sizeof *stats, kNlStats3 | kNlStatsChain | kNlStatsDlb});
 }
 
 int tsp_dev_ils_kick(tsp_dev_inst *inst, int B, int *succ, int succ_stride, int64_t tour_stride, uint64_t seed, int64_t it,

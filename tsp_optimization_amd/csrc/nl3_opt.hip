@@ -7,9 +7,8 @@
 // A lane works on the six ends of the three removed edges ("slots": tail and head of a, b, c) and not on node ids, because a
 // segment of one node puts two slots on one node.  Such a move has the same new edges as a second type with the segment
 // reversed, and both are moves of the neighbourhood, so the lane offers both, each summed in its own order.
+// The two entry points are a mode check, the NlStatsOut of their record type and tsp_nl_run (nl_opt.hip).
 #include "nl_common.hpp"
-
-#include <cstddef>
 
 #pragma clang fp contract(off)
 
@@ -139,47 +138,26 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
 void tsp_nl3_launch_scan(tsp_dev_tours *t, NlData *x, NlBest *parts3, int dlb_mode) {
     tsp_dev_inst *inst = t->inst;
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-        if (!dlb_mode)
-            hipLaunchKernelGGL((k_nl3_scan<WTC, INTC, false>), dim3(x->nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord,
-                               t->d_order, t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3, NlDlb{});
-        else
-            hipLaunchKernelGGL((k_nl3_scan<WTC, INTC, true>), dim3(x->nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord,
+        TSP_DISPATCH_DLB(dlb_mode, {
+            hipLaunchKernelGGL((k_nl3_scan<WTC, INTC, DLBC>), dim3(x->nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord,
                                t->d_order, t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3, x->dlb(dlb_mode));
+        });
     });
 }
-
-static_assert(offsetof(tsp_nl3_opt_stats, moves_3opt) == sizeof(tsp_nl_opt_stats), "tsp_nl3_opt_stats starts as tsp_nl_opt_stats");
-static_assert(offsetof(tsp_nl_dlb_stats, active_nodes) == sizeof(tsp_nl3_opt_stats), "tsp_nl_dlb_stats starts as tsp_nl3_opt_stats");
 
 extern "C" {
 
 int tsp_dev_nl_3opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
                     int64_t max_moves, double time_limit_s, tsp_nl3_opt_stats *stats) {
-    const NlState *st = nullptr;
-    const int status = tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj,
-                                  max_moves, time_limit_s, stats, sizeof *stats, &st);
-    if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
-    for (int b = 0; b < B && stats; ++b) {
-        stats[b].moves_3opt = st[b].moves_3opt;
-        for (int q = 0; q < 4; ++q) stats[b].moves_by_type[q] = st[b].moves_type[q];
-    }
-    return status;
+    return tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj, max_moves,
+                      time_limit_s, NlStatsOut{stats, sizeof *stats, kNlStats3}, TSP_DLB_OFF, nullptr);
 }
 
 int tsp_dev_nl_3opt_dlb(tsp_dev_inst *inst, int kinds, int dlb_mode, int B, int *succ, int succ_stride, int64_t tour_stride,
                         double *obj, const unsigned char *active, int64_t max_moves, double time_limit_s, tsp_nl_dlb_stats *stats) {
     if (dlb_mode != TSP_DLB_OFF && dlb_mode != TSP_DLB_ON && dlb_mode != TSP_DLB_CLOSE) return TSP_DEV_E_ARG;
-    const NlState *st = nullptr;
-    const int status = tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj,
-                                  max_moves, time_limit_s, stats, sizeof *stats, &st, dlb_mode, active);
-    if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
-    for (int b = 0; b < B && stats; ++b) {
-        stats[b].moves_3opt = st[b].moves_3opt;
-        for (int q = 0; q < 4; ++q) stats[b].moves_by_type[q] = st[b].moves_type[q];
-        stats[b].active_nodes = st[b].active_nodes;
-        stats[b].closing_scans = st[b].closing_scans;
-    }
-    return status;
+    return tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj, max_moves,
+                      time_limit_s, NlStatsOut{stats, sizeof *stats, kNlStats3 | kNlStatsDlb}, dlb_mode, active);
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // nl_common.hpp -- what the list descents share: nl_opt.hip (2-opt + Or-opt, tsp_dev_nl_opt) and nl3_opt.hip (those two and the
 // 3-opt kind, tsp_dev_nl_3opt).  The decision word, the per-tour state, the symmetric distance, the reversal of a forward path on
-// order/pos, the lists and scratch of an instance, and the host functions the two files call in each other.
+// order/pos, the lists and scratch of an instance, where a call's stats records go (NlStatsOut), the hooks and the DLB dispatch of
+// the launches, and the host functions the files call in each other (ils.hip too).
 #pragma once
+#include "descent.hpp"
 #include "or_opt_shift.hpp"
 
 #pragma clang fp contract(off)
@@ -99,11 +101,42 @@ struct NlData {
     ~NlData() { free_scratch(); (void)hipFree(d_nbr); }
 };
 
+// What Descent::run needs to know of a list descent beyond its NlState: with don't-look bits |A| at the start (else nact is NULL).
+struct NlHooks : DescentPlain {
+    const int *nact = nullptr;
+    void init(NlState &z, int b) const { if (nact) z.nact = nact[b]; }
+};
+
+// Where the stats records of a call go: B records `stride` bytes apart, of the public type that `parts` names.  Every record type
+// starts as tsp_nl_opt_stats; kNlStats3 adds the 3-opt counters (tsp_nl3_opt_stats), kNlStatsChain the fields of a chain behind
+// them (tsp_ils_stats), kNlStatsDlb the two don't-look counters behind whatever else it has (tsp_nl_dlb_stats, tsp_ils_dlb_stats).
+enum { kNlStats3 = 1, kNlStatsChain = 2, kNlStatsDlb = 4 };
+struct NlStatsOut {
+    void *p;   // may be NULL: no records
+    size_t stride;
+    int parts;
+};
+
 }  // namespace tsp
 
+// Runs the statements with the compile-time constant DLBC = (dlb_mode != 0): one launch site for both forms of a kernel.
+#define TSP_DISPATCH_DLB(DLB_RT, ...)                           \
+    do {                                                        \
+        auto dlb_call__ = [&](auto dlb_c) {                     \
+            constexpr bool DLBC = decltype(dlb_c)::value;       \
+            __VA_ARGS__                                         \
+        };                                                      \
+        if (!(DLB_RT)) dlb_call__(std::false_type{}); else dlb_call__(std::true_type{}); \
+    } while (0)
+
+// nl_opt.hip: record b of `out` from the final state of its tour: the groups the record type has and nothing behind them.  q: the
+// chain's state, or NULL (no chain ran: no iterations, last_improved -1).  start_cost: of a chain whose first descent has not
+// ended (q NULL, or q->it < 0).
+void tsp_nl_write_stats(const tsp::NlStatsOut &out, int b, const tsp::NlState &z, const tsp::IlsState *q, double start_cost,
+                        double seconds, float device_ms);
 // nl3_opt.hip: k_nl3_scan of every tour that is not done, one candidate per workgroup in parts3 (B x nparts); dlb_mode != 0: over
 // the lanes of the active nodes alone
-void tsp_nl3_launch_scan(tsp_dev_tours *t, tsp::NlData *x, tsp::NlBest *parts3, int dlb_mode = 0);
+void tsp_nl3_launch_scan(tsp_dev_tours *t, tsp::NlData *x, tsp::NlBest *parts3, int dlb_mode);
 // nl_opt.hip: the argument checks of a list descent; *kinds loses the kinds without a move at the instance's size
 int tsp_nl_check(const tsp_dev_inst *inst, int *kinds, int allowed, int B, const int *succ, int succ_stride, int64_t tour_stride,
                  const double *obj);
@@ -111,14 +144,12 @@ int tsp_nl_check(const tsp_dev_inst *inst, int *kinds, int allowed, int B, const
 int tsp_nl_prepare(tsp_dev_inst *inst, int B, tsp::NlData **x);
 // nl_opt.hip: one whole decision of every tour that is not done, queued on the engine's stream; dlb_mode != 0: a decision with
 // active sets (tsp_nl_dlb_start has set them)
-void tsp_nl_launch_decision(tsp_dev_tours *t, tsp::NlData *x, int kinds, int dlb_mode = 0);
+void tsp_nl_launch_decision(tsp_dev_tours *t, tsp::NlData *x, int kinds, int dlb_mode);
 // nl_opt.hip: the active sets of the B tours of *x at the start of a call, queued on the engine's stream: `active` (B x n bytes,
 // non-zero = active) or, when NULL, every node.  nact[b] = |A| of tour b, for NlState::nact.
 int tsp_nl_dlb_start(tsp_dev_inst *inst, tsp::NlData *x, int B, const unsigned char *active, std::vector<int> *nact);
-// nl_opt.hip: what both entry points do.  `allowed` is the kinds mask the entry point takes.  stats (may be NULL): B records
-// `stats_stride` bytes apart that start with the layout of tsp_nl_opt_stats; that part of each is filled here.  With TSP_OK or
-// TSP_TIME_LIMIT_EXCEEDED *states (unless NULL) are the B final states, for what the caller's records hold beyond it.
-// dlb_mode != 0: the descent with don't-look bits from the set `active` (as tsp_nl_dlb_start takes it).
+// nl_opt.hip: what the descents' entry points do.  `allowed` is the kinds mask the entry point takes; `out` takes the B records
+// (chain fields as tsp_nl_write_stats fills them without a chain, start_cost = the final cost).  dlb_mode != 0: the descent with
+// don't-look bits from the set `active` (as tsp_nl_dlb_start takes it).
 int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
-               int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const tsp::NlState **states,
-               int dlb_mode = 0, const unsigned char *active = nullptr);
+               int64_t max_moves, double time_limit_s, const tsp::NlStatsOut &out, int dlb_mode, const unsigned char *active);

@@ -9,8 +9,12 @@
 // Every distance goes through dsym(): the lower node id first, so that a move reached through several (v, u, role)
 // combinations has the same delta bits each time.  A 2-opt move always reverses the forward path i1 .. j in place, so that
 // order/pos keep the orientation of succ and the Or-opt shift works unchanged.
+// Host: tsp_nl_run is the body of every descent entry point of this file and of nl3_opt.hip (and of ils.hip below eight nodes);
+// tsp_nl_write_stats fills the records of all five stats types, told by an NlStatsOut which groups a record has.
 #include "descent.hpp"
 #include "nl_common.hpp"
+
+#include <cstddef>
 
 #pragma clang fp contract(off)
 
@@ -455,29 +459,18 @@ void tsp_nl_launch_decision(tsp_dev_tours *t, NlData *x, int kinds, int dlb_mode
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         hipLaunchKernelGGL((k_nl_prep<WTC, INTC>), dim3((n + 255) / 256, B), dim3(256), 0, s, inst->d_coord, t->d_order, x->d_st, n,
                            x->d_E, x->d_rem);
-        if (low && !dlb_mode)
-            hipLaunchKernelGGL((k_nl_scan<WTC, INTC, false>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
-                               x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part, NlDlb{});
-        else if (low)
-            hipLaunchKernelGGL((k_nl_scan<WTC, INTC, true>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order, t->d_pos,
-                               x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part, x->dlb(dlb_mode));
+        if (low)
+            TSP_DISPATCH_DLB(dlb_mode, {
+                hipLaunchKernelGGL((k_nl_scan<WTC, INTC, DLBC>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order,
+                                   t->d_pos, x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part, x->dlb(dlb_mode));
+            });
     });
     if (three) tsp_nl3_launch_scan(t, x, parts3, dlb_mode);
-    if (!dlb_mode)
-        hipLaunchKernelGGL(k_nl_pick_apply<false>, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
-                           low ? x->d_part : nullptr, three ? parts3 : nullptr, x->K, NlDlb{});
-    else
-        hipLaunchKernelGGL(k_nl_pick_apply<true>, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
+    TSP_DISPATCH_DLB(dlb_mode, {
+        hipLaunchKernelGGL(k_nl_pick_apply<DLBC>, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
                            low ? x->d_part : nullptr, three ? parts3 : nullptr, x->K, x->dlb(dlb_mode));
+    });
 }
-
-// What Descent::run needs to know of a descent with don't-look bits beyond its NlState: |A| at the start.
-namespace {
-struct DlbHooks : DescentPlain {
-    const int *nact;
-    void init(NlState &z, int b) const { z.nact = nact[b]; }
-};
-}  // namespace
 
 int tsp_nl_dlb_start(tsp_dev_inst *inst, NlData *x, int B, const unsigned char *active, std::vector<int> *nact) {
     const int n = inst->n;
@@ -535,9 +528,45 @@ int tsp_nl_prepare(tsp_dev_inst *inst, int B, NlData **out) {
     return TSP_OK;
 }
 
+// The layouts that let one writer serve the five record types: each starts as the one before it.
+static_assert(offsetof(tsp_nl3_opt_stats, moves_3opt) == sizeof(tsp_nl_opt_stats), "tsp_nl3_opt_stats starts as tsp_nl_opt_stats");
+static_assert(offsetof(tsp_nl_dlb_stats, active_nodes) == sizeof(tsp_nl3_opt_stats), "tsp_nl_dlb_stats starts as tsp_nl3_opt_stats");
+static_assert(offsetof(tsp_ils_stats, iterations) == sizeof(tsp_nl3_opt_stats), "tsp_ils_stats starts as tsp_nl3_opt_stats");
+static_assert(offsetof(tsp_ils_dlb_stats, active_nodes) == sizeof(tsp_ils_stats), "tsp_ils_dlb_stats starts as tsp_ils_stats");
+
+void tsp_nl_write_stats(const NlStatsOut &out, int b, const NlState &z, const IlsState *q, double start_cost, double seconds,
+                        float device_ms) {
+    if (!out.p) return;
+    char *rec = static_cast<char *>(out.p) + (size_t)b * out.stride;
+    tsp_nl_opt_stats &o = *reinterpret_cast<tsp_nl_opt_stats *>(rec);
+    o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
+    for (int k = 0; k < 3; ++k) o.moves_by_len[k] = z.moves_len[k];
+    o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
+    o.seconds = seconds; o.device_ms = device_ms;
+    if (out.parts & kNlStats3) {
+        tsp_nl3_opt_stats &o3 = *reinterpret_cast<tsp_nl3_opt_stats *>(rec);
+        o3.moves_3opt = z.moves_3opt;
+        for (int k = 0; k < 4; ++k) o3.moves_by_type[k] = z.moves_type[k];
+    }
+    const bool chain = out.parts & kNlStatsChain;
+    if (chain) {
+        tsp_ils_stats &c = *reinterpret_cast<tsp_ils_stats *>(rec);
+        const bool begun = q && q->it >= 0;   // the first descent has ended
+        c.iterations = begun ? q->it : 0; c.accepted = q ? q->accepted : 0; c.last_improved = q ? q->last_improved : -1;
+        c.start_cost = begun ? q->start_cost : start_cost;
+    }
+    if (!(out.parts & kNlStatsDlb)) return;
+    if (chain) {
+        tsp_ils_dlb_stats &d = *reinterpret_cast<tsp_ils_dlb_stats *>(rec);
+        d.active_nodes = z.active_nodes; d.closing_scans = z.closing_scans;
+    } else {
+        tsp_nl_dlb_stats &d = *reinterpret_cast<tsp_nl_dlb_stats *>(rec);
+        d.active_nodes = z.active_nodes; d.closing_scans = z.closing_scans;
+    }
+}
+
 int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
-               int64_t max_moves, double time_limit_s, void *stats, size_t stats_stride, const NlState **states, int dlb_mode,
-               const unsigned char *active) {
+               int64_t max_moves, double time_limit_s, const NlStatsOut &out, int dlb_mode, const unsigned char *active) {
     int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
     Descent run;
@@ -546,31 +575,18 @@ int tsp_nl_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int
     NlData *x = nullptr;
     rc = tsp_nl_prepare(inst, B, &x);
     if (rc) return rc;
-    const bool trivial = kinds == 0 || max_moves == 0;
-    int status;
-    if (!dlb_mode) {
-        status = run.run(x->d_st, x->h_st, x->d_cost, trivial, 256, max_moves, time_limit_s,
-                         [&](bool) { tsp_nl_launch_decision(run.t, x, kinds); });
-    } else {
-        std::vector<int> nact;
+    std::vector<int> nact;
+    NlHooks hooks;
+    if (dlb_mode) {
         rc = tsp_nl_dlb_start(inst, x, B, active, &nact);
         if (rc) return rc;
-        DlbHooks hooks;
         hooks.nact = nact.data();
-        status = run.run(x->d_st, x->h_st, x->d_cost, trivial, 256, max_moves, time_limit_s,
-                         [&](bool) { tsp_nl_launch_decision(run.t, x, kinds, dlb_mode); }, hooks);
     }
+    const int status = run.run(x->d_st, x->h_st, x->d_cost, kinds == 0 || max_moves == 0, 256, max_moves, time_limit_s,
+                               [&](bool) { tsp_nl_launch_decision(run.t, x, kinds, dlb_mode); }, hooks);
     if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
-    for (int b = 0; b < B && stats; ++b) {
-        const NlState &z = x->h_st[b];
-        tsp_nl_opt_stats &o = *reinterpret_cast<tsp_nl_opt_stats *>(static_cast<char *>(stats) + (size_t)b * stats_stride);
-        memset(&o, 0, sizeof o);
-        o.decisions = z.decisions; o.moves = z.moves; o.moves_2opt = z.moves_2opt; o.moves_oropt = z.moves_oropt;
-        for (int q = 0; q < 3; ++q) o.moves_by_len[q] = z.moves_len[q];
-        o.moves_reversed = z.moves_rev; o.reversed = z.reversed; o.deltas_executed = z.deltas;
-        o.seconds = wall_s() - run.t0; o.device_ms = run.device_ms;
-    }
-    if (states) *states = x->h_st;
+    const double seconds = wall_s() - run.t0;
+    for (int b = 0; b < B; ++b) tsp_nl_write_stats(out, b, x->h_st[b], nullptr, obj[b], seconds, run.device_ms);
     return status;
 }
 
@@ -641,8 +657,8 @@ int tsp_dev_inst_knn_get(tsp_dev_inst *inst, int *K, int *nbr) {
 
 int tsp_dev_nl_opt(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
                    int64_t max_moves, double time_limit_s, tsp_nl_opt_stats *stats) {
-    return tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT, B, succ, succ_stride, tour_stride, obj, max_moves, time_limit_s, stats,
-                      sizeof *stats, nullptr);
+    return tsp_nl_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT, B, succ, succ_stride, tour_stride, obj, max_moves, time_limit_s,
+                      NlStatsOut{stats, sizeof *stats, 0}, TSP_DLB_OFF, nullptr);
 }
 
 }  // extern "C"

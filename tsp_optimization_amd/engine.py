@@ -25,84 +25,59 @@ class TspDeviceError(RuntimeError):
     pass
 
 
-class Stats(C.Structure):
+class _Stats(C.Structure):
+    """What every stats structure below is: as_dict() has its fields by name, the array fields as lists."""
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        return {k: list(v) if isinstance(v, C.Array) else v for k, v in d.items()}
+
+
+class Stats(_Stats):
     _fields_ = [("sweeps", C.c_int64), ("evals", C.c_int64), ("moves", C.c_int64),
                 ("reversed", C.c_int64), ("pairs_scanned", C.c_int64), ("steps", C.c_int64),
                 ("seconds", C.c_double), ("device_ms", C.c_double),
                 ("lane_pairs", C.c_int64), ("tier1_pairs", C.c_int64), ("exact_pairs", C.c_int64),
                 ("staged_recs", C.c_int64)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class OrOptStats(C.Structure):
+class OrOptStats(_Stats):
     _fields_ = [("sweeps", C.c_int64), ("evals", C.c_int64), ("moves", C.c_int64), ("moves_by_len", C.c_int64 * 3),
                 ("moves_reversed", C.c_int64), ("deltas_executed", C.c_int64), ("rounds", C.c_int64),
                 ("seconds", C.c_double), ("device_ms", C.c_double)]
 
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_}
-        d["moves_by_len"] = list(self.moves_by_len)
-        return d
 
-
-class NlOptStats(C.Structure):
+class NlOptStats(_Stats):
     _fields_ = [("decisions", C.c_int64), ("moves", C.c_int64), ("moves_2opt", C.c_int64), ("moves_oropt", C.c_int64),
                 ("moves_by_len", C.c_int64 * 3), ("moves_reversed", C.c_int64), ("reversed", C.c_int64),
                 ("deltas_executed", C.c_int64), ("seconds", C.c_double), ("device_ms", C.c_double)]
 
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_}
-        d["moves_by_len"] = list(self.moves_by_len)
-        return d
 
-
-class Nl3OptStats(C.Structure):
+class Nl3OptStats(_Stats):
     _fields_ = NlOptStats._fields_ + [("moves_3opt", C.c_int64), ("moves_by_type", C.c_int64 * 4)]
 
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_}
-        d["moves_by_len"] = list(self.moves_by_len)
-        d["moves_by_type"] = list(self.moves_by_type)
-        return d
 
-
-class IlsStats(C.Structure):
+class IlsStats(_Stats):
     _fields_ = Nl3OptStats._fields_ + [("iterations", C.c_int64), ("accepted", C.c_int64), ("last_improved", C.c_int64),
                                        ("start_cost", C.c_double)]
 
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_}
-        d["moves_by_len"] = list(self.moves_by_len)
-        d["moves_by_type"] = list(self.moves_by_type)
-        return d
 
-
-class NlDlbStats(C.Structure):
+class NlDlbStats(_Stats):
     _fields_ = Nl3OptStats._fields_ + [("active_nodes", C.c_int64), ("closing_scans", C.c_int64)]
-    as_dict = IlsStats.as_dict
 
 
-class IlsDlbStats(C.Structure):
+class IlsDlbStats(_Stats):
     _fields_ = IlsStats._fields_ + [("active_nodes", C.c_int64), ("closing_scans", C.c_int64)]
-    as_dict = IlsStats.as_dict
 
 
-class LbStats(C.Structure):
+class LbStats(_Stats):
     _fields_ = [("iterations", C.c_int64), ("trees", C.c_int64), ("rounds", C.c_int64), ("dists_executed", C.c_int64),
                 ("tour_found", C.c_int), ("lambda_final", C.c_double), ("seconds", C.c_double), ("device_ms", C.c_double)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class AlphaStats(C.Structure):
+class AlphaStats(_Stats):
     _fields_ = [("trees", C.c_int64), ("rounds", C.c_int64), ("pairs_executed", C.c_int64), ("tree_value", C.c_double),
                 ("seconds", C.c_double), ("device_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 _lib = None
@@ -248,6 +223,22 @@ def _d(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _obj(obj, B):
+    """the obj argument of a call on B tours: zeros, or the caller's value(s) as a [B] array of the call's own"""
+    if obj is None:
+        return np.zeros(B, dtype=np.float64)
+    return np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)), copy=True)
+
+
+def _result(rc, single, succ2, o, *stats):
+    """-> (status, succ', obj', one list of stats dicts per stats array); for a single tour its own row of each"""
+    _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
+    dicts = tuple([s.as_dict() for s in st] for st in stats)
+    if single:
+        return (rc, succ2[0], float(o[0])) + tuple(d[0] for d in dicts)
+    return (rc, succ2, o) + dicts
+
+
 def device_count():
     return lib().tsp_dev_count()
 
@@ -349,23 +340,6 @@ class Instance:
         return succ, obj.value
 
     # -- alg_2opt / alg_2opt_tabu(NULL) ---------------------------------------------------
-    def two_opt(self, succ, obj, mode=FIRST, engine=ENGINE_AUTO, time_limit=-1.0):
-        """succ [n] or [B,n]; obj scalar or [B].  -> (status, succ', obj', [stats dict])"""
-        succ = np.array(succ, dtype=np.int32, copy=True, order="C")
-        single = succ.ndim == 1
-        succ2 = succ.reshape(1, -1) if single else succ
-        B, n = succ2.shape
-        assert n == self.n
-        o = np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)), copy=True)
-        st = (Stats * B)()
-        rc = lib().tsp_dev_two_opt(self._h, mode, engine, B, _i(succ2), 1, n, _d(o), time_limit, st)
-        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
-        stats = [s.as_dict() for s in st]
-        if single:
-            return rc, succ2[0], float(o[0]), stats[0]
-        return rc, succ2, o, stats
-
-    # -- Or-opt (extension) ---------------------------------------------------------------
     def _tours(self, succ):
         succ = np.array(succ, dtype=np.int32, copy=True, order="C")
         single = succ.ndim == 1
@@ -373,34 +347,35 @@ class Instance:
         assert succ2.shape[1] == self.n
         return single, succ2
 
+    def two_opt(self, succ, obj, mode=FIRST, engine=ENGINE_AUTO, time_limit=-1.0):
+        """succ [n] or [B,n]; obj scalar or [B].  -> (status, succ', obj', [stats dict])"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = _obj(obj, B)
+        st = (Stats * B)()
+        rc = lib().tsp_dev_two_opt(self._h, mode, engine, B, _i(succ2), 1, n, _d(o), time_limit, st)
+        return _result(rc, single, succ2, o, st)
+
+    # -- Or-opt (extension) ---------------------------------------------------------------
     def or_opt(self, succ, obj=None, max_moves=-1, time_limit=-1.0):
         """Or-opt descent (tsp_dev_or_opt).  succ [n] or [B,n].  -> (status, succ', obj' (recomputed cost), stats dict(s))"""
         single, succ2 = self._tours(succ)
         B, n = succ2.shape
-        o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
+        o = _obj(obj, B)
         st = (OrOptStats * B)()
         rc = lib().tsp_dev_or_opt(self._h, B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
-        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
-        stats = [s.as_dict() for s in st]
-        if single:
-            return rc, succ2[0], float(o[0]), stats[0]
-        return rc, succ2, o, stats
+        return _result(rc, single, succ2, o, st)
 
     def two_opt_or_opt(self, succ, obj, mode=FIRST, time_limit=-1.0):
         """2-opt + Or-opt rounds to a joint local optimum (tsp_dev_two_opt_or_opt).
         -> (status, succ', obj' (recomputed cost), 2-opt stats dict(s), Or-opt stats dict(s))"""
         single, succ2 = self._tours(succ)
         B, n = succ2.shape
-        o = np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)), copy=True)
+        o = _obj(obj, B)
         st2 = (Stats * B)()
         sto = (OrOptStats * B)()
         rc = lib().tsp_dev_two_opt_or_opt(self._h, mode, B, _i(succ2), 1, n, _d(o), time_limit, st2, sto)
-        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
-        s2 = [s.as_dict() for s in st2]
-        so = [s.as_dict() for s in sto]
-        if single:
-            return rc, succ2[0], float(o[0]), s2[0], so[0]
-        return rc, succ2, o, s2, so
+        return _result(rc, single, succ2, o, st2, sto)
 
     # -- candidate neighbour lists (extension) ----------------------------------------------
     def knn_build(self, K=NL_DEFAULT_K):
@@ -431,14 +406,10 @@ class Instance:
         -> (status, succ', obj' (recomputed cost), stats dict(s))"""
         single, succ2 = self._tours(succ)
         B, n = succ2.shape
-        o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
+        o = _obj(obj, B)
         st = (NlOptStats * B)()
         rc = lib().tsp_dev_nl_opt(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
-        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
-        stats = [s.as_dict() for s in st]
-        if single:
-            return rc, succ2[0], float(o[0]), stats[0]
-        return rc, succ2, o, stats
+        return _result(rc, single, succ2, o, st)
 
     def nl_3opt(self, succ, obj=None, kinds=NL_2OPT | NL_OROPT | NL_3OPT, max_moves=-1, time_limit=-1.0, dlb=DLB_OFF, active=None):
         """The list descent with the 3-opt kind (tsp_dev_nl_3opt): kinds is any non-empty subset of NL_2OPT | NL_OROPT | NL_3OPT.
@@ -447,23 +418,20 @@ class Instance:
         `active` ([n] or [B,n], non-zero = active; None: every node); the stats then carry active_nodes and closing_scans"""
         single, succ2 = self._tours(succ)
         B, n = succ2.shape
-        o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
+        o = _obj(obj, B)
+        tours = (B, _i(succ2), 1, n, _d(o))
         if dlb != DLB_OFF:
             act = None
             if active is not None:
                 act = np.ascontiguousarray(np.asarray(active).reshape(B, n) != 0, dtype=np.uint8)
             st = (NlDlbStats * B)()
-            rc = lib().tsp_dev_nl_3opt_dlb(self._h, int(kinds), int(dlb), B, _i(succ2), 1, n, _d(o),
+            rc = lib().tsp_dev_nl_3opt_dlb(self._h, int(kinds), int(dlb), *tours,
                                            None if act is None else act.ctypes.data_as(C.POINTER(C.c_ubyte)), int(max_moves),
                                            time_limit, st)
         else:
             st = (Nl3OptStats * B)()
-            rc = lib().tsp_dev_nl_3opt(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(max_moves), time_limit, st)
-        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
-        stats = [s.as_dict() for s in st]
-        if single:
-            return rc, succ2[0], float(o[0]), stats[0]
-        return rc, succ2, o, stats
+            rc = lib().tsp_dev_nl_3opt(self._h, int(kinds), *tours, int(max_moves), time_limit, st)
+        return _result(rc, single, succ2, o, st)
 
     # -- iterated local search (extension) ---------------------------------------------------
     def ils(self, succ, iterations, seed=0, span=0, kinds=NL_2OPT | NL_OROPT | NL_3OPT, max_moves_per_descent=-1, time_limit=-1.0,
@@ -475,20 +443,16 @@ class Instance:
         descent with don't-look bits (tsp_dev_ils_dlb), the stats with active_nodes and closing_scans"""
         single, succ2 = self._tours(succ)
         B, n = succ2.shape
-        o = np.zeros(B, dtype=np.float64) if obj is None else np.array(np.broadcast_to(np.asarray(obj, dtype=np.float64), (B,)))
+        o = _obj(obj, B)
+        args = (self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations), int(span),
+                int(max_moves_per_descent), time_limit)
         if dlb != DLB_OFF:
             st = (IlsDlbStats * B)()
-            rc = lib().tsp_dev_ils_dlb(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations),
-                                       int(span), int(max_moves_per_descent), time_limit, int(dlb), st)
+            rc = lib().tsp_dev_ils_dlb(*args, int(dlb), st)
         else:
             st = (IlsStats * B)()
-            rc = lib().tsp_dev_ils(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations),
-                                   int(span), int(max_moves_per_descent), time_limit, st)
-        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
-        stats = [s.as_dict() for s in st]
-        if single:
-            return rc, succ2[0], float(o[0]), stats[0]
-        return rc, succ2, o, stats
+            rc = lib().tsp_dev_ils(*args, st)
+        return _result(rc, single, succ2, o, st)
 
     def ils_kick(self, succ, seed, it, span=0):
         """The kick of iteration `it` of chain b applied to tour b and nothing else (tsp_dev_ils_kick).  succ [n] or [B,n]
