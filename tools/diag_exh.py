@@ -1,6 +1,6 @@
 """Diagnostic build only (lib_diag, -DTSP_STAMPS; recipe in tools/diag_stamps.py): the timeline of one exhaustive sweep
-(k_exh, two_opt_exh.hpp) on rand10000 -- when the first / last wave starts, leaves its rows, when the last candidate is
-published and when the last block's apply is done, in microseconds after the first wave's start.
+(k_exh, two_opt_exh.hpp) on rand10000 -- when the first / last wave starts, leaves its rows and when the last block's
+candidate is stored (the end of the launch: the move is decided by the next k_move_pos), in microseconds after the first wave's start.
 usage: diag_exh.py"""
 import os, sys, ctypes as C
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,8 +30,8 @@ for _ in range(N):
     L.tsp_dev_debug_exh_stamps(buf)
     acc += np.array(list(buf))
 acc /= N
-for name, v in zip(["last wave starts", "first wave out of its rows", "mean wave out of its rows", "last wave out of its rows", "last candidate published",
-                    "apply done", "shader clock in the rows (MHz)", "waves", "bookkeeping branches per wave", "cycles in them per wave",
+for name, v in zip(["last wave starts", "first wave out of its rows", "mean wave out of its rows", "last wave out of its rows", "last block's candidate stored",
+                    "shader clock in the rows (MHz)", "waves", "bookkeeping branches per wave", "cycles in them per wave",
                     "cycles in the rows per wave"], acc):
     print("  %-32s %8.2f" % (name, v))
 

@@ -43,7 +43,11 @@ struct alignas(16) TourState {
     long long lane_pairs, tier1_pairs, exact_pairs, staged_recs;
     // FIRST on the CLUSTER engine: running mean of the rows between two hits (decides between the tiles scan and the
     // box-pruned scan of a step; survives k_rearm, so that a driver's next call starts with what the last one learnt)
-    int hit_rows, pad0, pad1, pad2;
+    int hit_rows;
+    // exhaustive sweep (k_move_pos + k_exh): the sweep's candidates are written and its move is not decided yet -- the next
+    // k_move_pos decides it, or k_exh_close before the host looks.  Never set together with `pending`, never seen by the host.
+    int open;
+    int pad1, pad2;
 };
 
 constexpr int kScanThreads = 256;
@@ -154,7 +158,7 @@ struct tsp_dev_tours {
     int *d_pos = nullptr;            // B x n : position of node v
     int *d_order2 = nullptr, *d_pos2 = nullptr;   // second copies (sorted sweep: moves are applied out of place)
     tsp::TourState *d_state = nullptr;       // the current control blocks: d_state_base + slot * B
-    tsp::TourState *d_state_base = nullptr;  // 2 x B: k_first reads one slot and writes the other
+    tsp::TourState *d_state_base = nullptr;  // 2 x B: k_first and k_move_pos read one slot and write the other
     int slot = 0;
     tsp::Partial *d_partial = nullptr;
     size_t partial_per_tour = 0;

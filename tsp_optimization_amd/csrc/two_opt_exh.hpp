@@ -18,10 +18,16 @@
 // tie-break (strict '<' at tabusearch.c:151 keeps the first pair in (i < j) order), which is what every lane keeps.
 // Every delta is still computed exactly (integer-valued distances from the exact roots of tsp_dist.hpp's int_root).
 //
-// Layout.  k_move_pos (one thread per position) carries the previous sweep's move out of place (as k_move_recs does)
+// Layout.  k_move_pos (one thread per position) DECIDES the previous sweep's move -- every block for itself, from the
+// candidates k_exh left (sweep_decide, two_opt_step.hpp) --, carries it out of place (as k_move_recs does)
 // and writes, in position order and padded: rec[p] = the record of u_p (exh_arith.hpp: -2x, -2y and the norm of its
 // coordinates relative to node 0, and e[p - 1]; position n repeats position 0; further pads lie far outside the instance),
 // pid[p] = u_p.
+// Hand-off.  k_exh ends at its block's candidate: no counter, no last block.  No word is read and written by different blocks
+// of one launch: a tour has two control blocks, k_move_pos reads slot s and its block 0 writes the advanced block to slot
+// s ^ 1; k_exh reads `done` there and one thread of it sets `open` there ("candidates written, not decided"), which nobody
+// else in that launch reads.  The host flips s per pair of launches; before it looks at a control block k_exh_close (one
+// block per tour) turns an open sweep into a pending move, which the next k_move_pos or the flush carries out.
 // k_exh: the pair-columns are cut into strips of W - 1 (W = 64 RJ columns of D per wave, RJ adjacent columns per lane),
 // laid out from the RIGHT end (exh_strip: the partial strip is the leftmost one, which has the fewest rows);
 // a strip's rows are its units of work, and the units of all strips, laid end to end, are dealt to the waves in
@@ -45,14 +51,13 @@ namespace tsp {
 
 #ifdef TSP_STAMPS
 // diagnostic build: per wave {100 MHz wall clock at start, at the end of its rows, shader cycles in between, 0}; [4] last
-// candidate published, [5] apply done in g_exh_t (tools/diag_exh.py reads them).  Plain stores to slots of their own: 4 096
+// block's candidate stored in g_exh_t (tools/diag_exh.py reads them).  Plain stores to slots of their own: 4 096
 // atomics on one word at the start of a kernel would be the thing measured.
 __device__ unsigned long long g_exh_w[8192 * 4];
 __device__ unsigned long long g_exh_t[8];
 #endif
 
 constexpr int kExhPad = 1152;          // positions past n that k_move_pos fills (>= the widest strip + 2)
-constexpr int kExhCluster = 32;        // blocks per first-level arrival counter
 constexpr int kRowBatch = 4;           // rows whose records one batch of scalar loads fetches
 constexpr int kExhRJ = 4;              // k_exh: columns per lane (8 and 16, and 1 and 2, measured slower)
 
@@ -104,16 +109,44 @@ __device__ __forceinline__ void exh_dist_row(const double (&cx)[RJ], const doubl
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// (1) the pending move, out of place; (2) the tour AFTER that move in position order: records and ids.
+// (1) the move: the open sweep's, decided here by every block for itself, or a pending one (decided by k_exh_close); (2) that move,
+// out of place; (3) the tour AFTER it in position order: records and ids.  Reads the control block `states`, which no block of
+// this launch writes; block 0 writes the advanced one to `states_next` (the tour's other slot), which no block of this launch reads.
 template <int WT, bool INT>
 __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__restrict__ coord, int *orders, int *poss, int *orders2,
-                                                           int *poss2, const TourState *__restrict__ states, ExhRec *__restrict__ rec,
+                                                           int *poss2, const TourState *__restrict__ states,
+                                                           TourState *__restrict__ states_next, const Partial *__restrict__ partials,
+                                                           size_t partial_per_tour, int flat_slots, ExhRec *__restrict__ rec,
                                                            int *__restrict__ pid, int n) {
+    static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only (integer costs: the tour cost needs no staging)");
+    __shared__ double s_d[kScanThreads / 64];
+    __shared__ u64 s_k[kScanThreads / 64];
     const int tour = blockIdx.y;
     const TourState *st = states + tour;
-    if (st->done) return;
+    const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
+    if (st->done) {   // a finished tour stays finished in both slots
+        if (writer) states_next[tour] = *st;
+        return;
+    }
     const size_t base = (size_t)tour * n, pbase = (size_t)tour * (n + kExhPad);
-    const MoveView mv = move_view(st, orders + base, poss + base, orders2 + base, poss2 + base, n);
+    MoveView mv = move_view(st, orders + base, poss + base, orders2 + base, poss2 + base, n);
+    const bool open = st->open != 0;   // (then nothing is pending: mv.L == 0)
+    SweepDecision dec;
+    if (open) {
+        dec = sweep_decide(partials + (size_t)tour * partial_per_tour, flat_slots, mv.pos, n, s_d, s_k);
+        if (!dec.found) {   // the local optimum: block 0 recomputes the cost (tabusearch.c:168-172), nobody has records to build
+            if (blockIdx.x != 0) return;
+            const double cost = tour_cost_block<WT, INT>(coord, mv.order, mv.pos, n, s_d, nullptr);
+            if (writer) {
+                TourState z = *st;
+                sweep_count(z, dec, n, cost);
+                z.pending = 0;
+                states_next[tour] = z;
+            }
+            return;
+        }
+        mv.L = dec.L; mv.pa1 = dec.pa + 1 == n ? 0 : dec.pa + 1;
+    }
     const int k = blockIdx.x * kScanThreads + threadIdx.x;
     if (k >= n + kExhPad) return;
     // every load of the current copy (which this kernel never writes) comes before the first store
@@ -135,6 +168,42 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__rest
     r.pad_ = 0;
     rec[pbase + k] = r;
     pid[pbase + k] = u;
+    if (writer) {   // the next control block: the sweep counted, the move carried out (the other copy is the current one now)
+        // (the writer is thread 0 of block 0: k = 0, never past the early return above)
+        TourState z = *st;
+        if (open) sweep_count(z, dec, n, 0.0);
+        if (mv.L > 0) z.parity ^= 1;
+        z.pending = 0;
+        states_next[tour] = z;
+    }
+}
+
+// Before the host looks at a control block (a poll, the end of a run): an open sweep becomes a decided one -- the counters, and
+// either a pending move, which the next k_move_pos or the flush carries out, or the finished tour's recomputed cost.  One block
+// per tour, so it updates the control block it reads (behind the barriers of the decision).
+template <int WT, bool INT>
+__global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__restrict__ coord, const int *orders, const int *poss,
+                                                            const int *orders2, const int *poss2, TourState *states,
+                                                            const Partial *__restrict__ partials, size_t partial_per_tour,
+                                                            int flat_slots, int n) {
+    static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only");
+    __shared__ double s_d[kScanThreads / 64];
+    __shared__ u64 s_k[kScanThreads / 64];
+    const int tour = blockIdx.x;
+    TourState *st = states + tour;
+    if (st->done || !st->open) return;
+    const size_t base = (size_t)tour * n;
+    const bool second = st->parity != 0;
+    const int *order = (second ? orders2 : orders) + base, *pos = (second ? poss2 : poss) + base;
+    const SweepDecision dec = sweep_decide(partials + (size_t)tour * partial_per_tour, flat_slots, pos, n, s_d, s_k);
+    double cost = 0.0;
+    if (!dec.found) cost = tour_cost_block<WT, INT>(coord, order, pos, n, s_d, nullptr);
+    if (threadIdx.x == 0) {
+        TourState z = *st;
+        sweep_count(z, dec, n, cost);
+        z.pending = dec.found;
+        *st = z;
+    }
 }
 
 // RJ = kExhRJ columns per lane, four workgroups of four waves per CU (the host pins that with its LDS request)
@@ -143,7 +212,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
                                                       const int *__restrict__ pid_all, int waves_total, int4 share, int gens) {
     // the position arrays are kernel arguments of their own, restrict-qualified: the row operands are wave-uniform loads, and
     // the compiler only issues them as scalar loads (s_load: no vector-memory slot, no VGPRs) when it can prove that the
-    // kernel's own stores and atomics (candidate slots, tickets) never touch them
+    // kernel's own stores (the candidate slot, `open`) never touch them
     static_assert(exh_metric<WT>(), "integer-coordinate metrics only");
     constexpr int W = 64 * RJ, WEFF = W - 1;
     const int tour = blockIdx.z;
@@ -275,7 +344,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
         }
     }
 
-    // ---- the wave's, the block's, the tour's arg-min (delta, (i, j)) ------------------------------------------------
+    // ---- the wave's and the block's arg-min (delta, (i, j)); the tour's is taken by the next launch -----------------------
 #ifdef TSP_STAMPS
     if (lane == 0 && tour == 0) {
         const int w = (int)blockIdx.x * (kScanThreads / 64) + (tid >> 6);
@@ -298,35 +367,18 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
     }
     __shared__ double s_d[kScanThreads / 64];
     __shared__ u64 s_k[kScanThreads / 64];
-    __shared__ int s_last;
     block_argmin<true>(d, key, s_d, s_k);
+    // The launch ends here: the block's candidate, empty or not, as plain stores -- its readers (every block of the next
+    // k_move_pos, or k_exh_close) are later launches.  `open` tells them so; nothing in this launch reads it.
     if (tid == 0) {
-        publish_partial(a.partials + (size_t)tour * a.partial_per_tour + blockIdx.x, d, key_i(key), key_j(key));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stores have left this CU before the ticket
+        Partial p;
+        p.delta = d; p.i = key_i(key); p.j = key_j(key);
+        a.partials[(size_t)tour * a.partial_per_tour + blockIdx.x] = p;
+        if (blockIdx.x == 0) a.states[tour].open = 1;
 #ifdef TSP_STAMPS
         atomicMax(&g_exh_t[4], wall_clock64());
 #endif
-        // arrivals on one word are served one after the other: count per cluster of blocks first, then the clusters
-        const int Q = ((int)gridDim.x + kExhCluster - 1) / kExhCluster, q = (int)blockIdx.x / kExhCluster;
-        const int members = min(kExhCluster, (int)gridDim.x - q * kExhCluster);
-        gi32 *ct = (gi32 *)(a.cl_tickets + ((size_t)tour * 64 + q) * 64);
-        s_last = 0;
-        if (__hip_atomic_fetch_add(ct, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == members) {
-            __hip_atomic_store(ct, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int old = __hip_atomic_fetch_add((gi32 *)(a.tickets + tour), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = (old + 1 == Q);
-            if (s_last) __hip_atomic_store((gi32 *)(a.tickets + tour), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
     }
-    __syncthreads();
-    if (!s_last) return;
-#ifdef TSP_STAMPS
-    __shared__ unsigned long long stamps[16];
-    apply_step<WT, INT, TSP_2OPT_BEST, 2, false, true>(a, tour, 0, n - 1, stamps, nullptr);
-    if (tid == 0) atomicMax(&g_exh_t[5], wall_clock64());
-#else
-    apply_step<WT, INT, TSP_2OPT_BEST, 2, false, true>(a, tour, 0, n - 1, nullptr);
-#endif
 }
 
 }  // namespace tsp

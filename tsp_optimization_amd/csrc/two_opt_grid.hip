@@ -303,6 +303,17 @@ void launch_flush(tsp_dev_tours *t) {
     hipLaunchKernelGGL(k_flush_state, dim3((t->B + 255) / 256), dim3(256), 0, s, t->d_state, t->B);
 }
 
+// Exhaustive sweeps (k_move_pos + k_exh) leave their last sweep undecided: before the host copies a control block, and before
+// anything else works on the tours, that sweep is decided and its move recorded as pending (k_exh_close).
+void launch_exh_close(tsp_dev_tours *t) {
+    hipStream_t s = t->inst->ctx->stream;
+    TSP_DISPATCH_METRIC(t->inst->wtype, t->inst->integer_cost, {
+        if constexpr (exh_metric<WTC>())
+            hipLaunchKernelGGL((k_exh_close<WTC, INTC>), dim3(t->B), dim3(kScanThreads), 0, s, t->inst->d_coord, t->d_order, t->d_pos,
+                               t->d_order2, t->d_pos2, t->d_state, t->d_partial, t->partial_per_tour, t->exh_blocks, t->n);
+    });
+}
+
 StepArgs make_args(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int tenure) {
     StepArgs a;
     a.coord = t->inst->d_coord; a.orders = t->d_order; a.poss = t->d_pos; a.states = t->d_state;
@@ -338,8 +349,14 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
     StepArgs a = make_args(t, mode, tabu, iter, tenure);
     if constexpr (exh_metric<WT>()) {
         if (exh_run(t, mode, tabu)) {
+            // k_move_pos reads the current control blocks and writes the other slot, which is the current one from then on
+            TourState *cur = t->d_state;
+            t->slot ^= 1;
+            t->d_state = t->d_state_base + (size_t)t->slot * t->B;
             hipLaunchKernelGGL((k_move_pos<WT, INT>), dim3((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B), dim3(kScanThreads), 0, s,
-                               t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2, t->d_state, t->d_prec, t->d_pid, t->n);
+                               t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2, cur, t->d_state, t->d_partial,
+                               t->partial_per_tour, t->exh_blocks, t->d_prec, t->d_pid, t->n);
+            a.states = t->d_state;
             a.flat_slots = t->exh_blocks;
             const int wt_ = t->exh_blocks * (kScanThreads / 64);
             const dim3 g(t->exh_blocks, 1, t->B);
@@ -451,7 +468,8 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
     int status = TSP_OK;
     bool finished = false;
     if (all_done) *all_done = 0;
-    launch_arm(t, mode);
+    const bool exh = exh_run(t, mode, tabu);   // the last queued sweep is open until k_exh_close has decided it
+    if (!exh) launch_arm(t, mode);             // (the exhaustive sweep takes no tickets, and k_move_pos writes the slot it hands on whole)
     for (;;) {
         int64_t todo = burst;
         burst = std::min(batch, burst * 2);
@@ -459,11 +477,15 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
         if (todo <= 0) break;
         for (int64_t k = 0; k < todo; ++k) {
             int rc = launch_step_rt(t, mode, tabu, iter, tenure);
-            if (rc) return rc;
+            if (rc) {   // no sweep stays open behind a failed launch either: decided, and the tour back in the first copy
+                if (exh) { launch_exh_close(t); launch_flush(t); }
+                return rc;
+            }
         }
         queued += todo;
         TSP_HIP_TRY(hipGetLastError());
         if (!sync) continue;
+        if (exh) launch_exh_close(t);
         TSP_HIP_TRY(hipMemcpyAsync(t->h_state, t->d_state, sizeof(TourState) * (size_t)t->B, hipMemcpyDeviceToHost, s));
         TSP_HIP_TRY(hipStreamSynchronize(s));
         bool done = true;
@@ -473,7 +495,8 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
     }
     if (tabu && t->tabu_list_run)   // the sweeps counted every non-adjacent pair; the skipped ones come off
         hipLaunchKernelGGL(k_tabu_fix_evals, dim3(1), dim3(64), 0, s, t->d_state, tabu->d_tabu_pairs);
-    if (sorted_run(t, mode, tabu) || exh_run(t, mode, tabu) || mode == TSP_2OPT_FIRST) {
+    if (exh && !sync) launch_exh_close(t);   // (a synchronous run's last poll has closed the sweep)
+    if (sorted_run(t, mode, tabu) || exh || mode == TSP_2OPT_FIRST) {
         launch_flush(t);
         TSP_HIP_TRY(hipGetLastError());
         if (sync == 1) TSP_HIP_TRY(hipStreamSynchronize(s));   // sync == 2: the caller queues more work and waits once
@@ -1192,12 +1215,13 @@ int tsp_dev_tours_time_scan(tsp_dev_tours *t, int reps, float *mean_ms, int64_t 
     TSP_HIP_TRY(hipEventCreate(&e0));
     TSP_HIP_TRY(hipEventCreate(&e1));
     double total = 0.0;
-    launch_arm(t, TSP_2OPT_BEST);
+    if (!exh_run(t, TSP_2OPT_BEST, nullptr)) launch_arm(t, TSP_2OPT_BEST);
     launch_step_rt(t, TSP_2OPT_BEST, nullptr, 0, 0);   // warm
     TSP_HIP_TRY(hipEventRecord(e0, s));
     for (int r = 0; r < reps; ++r) launch_step_rt(t, TSP_2OPT_BEST, nullptr, 0, 0);   // back to back on the engine's stream
     TSP_HIP_TRY(hipEventRecord(e1, s));
     TSP_HIP_TRY(hipEventSynchronize(e1));
+    if (exh_run(t, TSP_2OPT_BEST, nullptr)) launch_exh_close(t);
     if (sorted_sweep(t) || exh_run(t, TSP_2OPT_BEST, nullptr)) { launch_flush(t); TSP_HIP_TRY(hipStreamSynchronize(s)); }
     {
         float ms = 0.f;
@@ -1372,8 +1396,9 @@ int tsp_dev_two_opt_tabu(tsp_dev_inst *inst, tsp_dev_tabu *tabu, int iter, int t
 #ifdef TSP_STAMPS
 // diagnostic: mean 100 MHz ticks per segment of the last block of a step; resets the sums
 // diagnostic build: the timeline of the last exhaustive sweep (two_opt_exh.hpp), microseconds after the first wave's start:
-// out[0] last wave start, [1] / [2] / [3] first / mean / last wave out of its rows, [4] last candidate published, [5] apply done,
-// [6] shader clock during the rows (MHz), [7] waves seen
+// out[0] last wave start, [1] / [2] / [3] first / mean / last wave out of its rows, [4] last block's candidate stored (the end of
+// the launch's work; the decision belongs to the next k_move_pos), [5] shader clock during the rows (MHz), [6] waves seen,
+// [7] / [8] / [9] per wave: bookkeeping branches taken, shader cycles in them, cycles in the rows
 int tsp_dev_debug_exh_stamps(double *out8) {
     std::vector<unsigned long long> w(8192 * 4);
     unsigned long long h[8];
@@ -1392,9 +1417,9 @@ int tsp_dev_debug_exh_stamps(double *out8) {
     }
     if (!nw) return 0;
     out8[0] = (double)(s1 - t0) / 100.0; out8[1] = (double)(e0 - t0) / 100.0; out8[2] = (esum / nw - (double)t0) / 100.0;
-    out8[3] = (double)(e1 - t0) / 100.0; out8[4] = ((double)h[4] - (double)t0) / 100.0; out8[5] = ((double)h[5] - (double)t0) / 100.0;
-    out8[6] = rsum > 0 ? csum / rsum * 100.0 : 0.0; out8[7] = nw;
-    out8[8] = hsum / nw; out8[9] = hcsum / nw; out8[10] = csum / nw;   // per wave: bookkeeping branches taken, shader cycles in them, cycles in the rows
+    out8[3] = (double)(e1 - t0) / 100.0; out8[4] = ((double)h[4] - (double)t0) / 100.0;
+    out8[5] = rsum > 0 ? csum / rsum * 100.0 : 0.0; out8[6] = nw;
+    out8[7] = hsum / nw; out8[8] = hcsum / nw; out8[9] = csum / nw;
     if (const char *dump = getenv("TSP_EXH_DUMP")) {   // per wave: exit time (us after the first start), XCC, HW_ID
         if (FILE *fp = fopen(dump, "w")) {
             for (int k = 0; k < 8192; ++k)

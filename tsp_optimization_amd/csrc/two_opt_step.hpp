@@ -1,5 +1,6 @@
 // two_opt_step.hpp -- what every step kernel of the GRID engine shares: launch arguments, the in-launch hand-off,
-// the tour seen through a pending move, the tour cost, and the apply executed by a step's last block
+// the tour seen through a pending move, the tour cost, the decision of a sweep a finished launch left (exhaustive sweep),
+// and the apply executed by a step's last block
 // Part of the GRID engine; included by two_opt_grid.hip only (one translation unit).
 #pragma once
 #include "two_opt_common.hpp"
@@ -103,6 +104,62 @@ __device__ __forceinline__ MoveView move_view(const TourState *st, const int *o1
         m.L = L; m.pa1 = st->mv_pa + 1 == n ? 0 : st->mv_pa + 1;
     }
     return m;
+}
+
+// ---- the decision of a sweep whose block candidates a FINISHED launch has left in memory ----------------------
+// Block-wide (kScanThreads threads), for every block that wants the answer: the arg-min of (delta, (i, j)) over the `nslots`
+// candidates of a tour -- apply_step's rule: better() on (delta, key), a move only when delta < 0 -- and the winner's
+// positions in the current copy of pos.  The candidates were written by an earlier launch: ordinary loads, all of a thread's
+// in flight at once, then one more latency for pos[i] and pos[j].  The reduction order differs from apply_step's; the
+// arg-min with a strict tie-break does not depend on it.  s_d, s_k: >= kScanThreads / 64 entries each.
+struct SweepDecision {
+    int found = 0, i = -1, j = -1;   // found == 0: local optimum (i = j = -1)
+    int pa = 0, pb = 0, L = 0;       // pos[i], pos[j]; reverse positions pa + 1 .. pb (cyclic), L = (pb - pa) mod n of them
+};
+
+__device__ __forceinline__ SweepDecision sweep_decide(const Partial *__restrict__ part, int nslots, const int *__restrict__ pos, int n,
+                                                      double *s_d, u64 *s_k) {
+    const int tid = threadIdx.x;
+    double bd = 0.0;
+    u64 key = kNoKey;
+    constexpr int PU = 8;   // 2 048 candidates = 8 per thread: one round
+    for (int s0 = tid; s0 < nslots; s0 += PU * kScanThreads) {
+        Partial p[PU];
+#pragma unroll
+        for (int k = 0; k < PU; ++k) {
+            const int s = s0 + k * kScanThreads;
+            p[k].delta = 0.0; p[k].i = -1; p[k].j = -1;
+            if (s < nslots) p[k] = part[s];
+        }
+#pragma unroll
+        for (int k = 0; k < PU; ++k) {
+            const u64 kk = make_key(p[k].i, p[k].j);
+            if (better(p[k].delta, kk, bd, key)) { bd = p[k].delta; key = kk; }
+        }
+    }
+    block_argmin<true>(bd, key, s_d, s_k);
+    SweepDecision d;
+    d.found = key != kNoKey && bd < 0;
+    if (d.found) {
+        d.i = key_i(key); d.j = key_j(key);
+        d.pa = pos[d.i]; d.pb = pos[d.j];
+        d.L = d.pb - d.pa; if (d.L < 0) d.L += n;
+    }
+    return d;
+}
+
+// What apply_step's thread 0 adds to the control block for one exhaustive sweep, at the moment the sweep is decided; without a
+// move the tour is done and `cost` is its recomputed cost.  parity and pending are the caller's: they depend on who decides
+// (two_opt_exh.hpp).
+__device__ __forceinline__ void sweep_count(TourState &z, const SweepDecision &d, int n, double cost) {
+    z.steps += 1;
+    z.sweeps += 1;
+    z.evals += (long long)n * (n - 1) / 2 - n;   // non-adjacent pairs (n >= 4)
+    z.pairs_scanned += (long long)n * (n - 1) / 2;
+    if (d.found) { z.moves += 1; z.reversed += d.L - 1; }
+    else { z.obj = cost; z.done = 1; }
+    z.mv_pa = d.pa; z.mv_pb = d.pb;
+    z.open = 0;
 }
 
 
