@@ -10,22 +10,6 @@
 
 using namespace tsp;
 
-// implemented in two_opt_grid.hip / two_opt_lds.hip
-int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int tenure, int64_t max_steps,
-                 double time_limit_s, int sync, int *all_done);
-int tsp_lds_run(tsp_dev_tours *t, int mode, double time_limit_s, int *all_done);
-bool tsp_lds_fits(const tsp_dev_inst *inst);
-// two_opt_cluster.hip
-bool tsp_cluster_fits(const tsp_dev_tours *t, int mode);
-bool tsp_cluster_sorted(const tsp_dev_tours *t, int mode);
-int tsp_cluster_size(const tsp_dev_tours *t, int mode);
-int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double time_limit_s, int *all_done, int *fell_through,
-                    tsp_dev_tabu *tabu = nullptr, int iter = 0, int tenure = 0);
-
-void tsp_or_scratch_free(void *p);   // or_opt.hip
-void tsp_nl_data_free(void *p);      // nl_opt.hip
-void tsp_hk_data_free(void *p);      // held_karp.hip
-
 void *tsp_io_pool(tsp_dev_inst *inst, size_t bytes) {
     bytes = (bytes + 255) & ~(size_t)255;
     if (bytes > inst->io_pool_bytes) {
@@ -163,17 +147,6 @@ int tsp_perm_cost_device(tsp_dev_inst *inst, const int *d_perm, long long stride
     TSP_HIP_TRY(hipGetLastError());
     return TSP_OK;
 }
-
-// two_opt_grid.hip: drivers on resident tours
-int tsp_grid_rearm(tsp_dev_tours *t, int mode);
-int tsp_grid_tabu_kick(tsp_dev_tours *t, tsp_dev_tabu *tabu, int a, int b, int iter, int tenure, int *accepted);
-int tsp_grid_vns_kick(tsp_dev_tours *t, int p1, int p2, int p3, double *obj);
-int tsp_grid_snapshot(tsp_dev_tours *t, bool restore);
-int tsp_grid_resident_tabu(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int tenure, double time_limit_s, double *obj);
-int tsp_grid_tabu_iteration(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int tenure, double time_limit_s, int a, int b,
-                            double *best_obj, double *obj, int *improved, int *accepted);
-int tsp_grid_tabu_iterations(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter0, int count, const int *tenure, int pairs, const int *ab, double time_limit_s,
-                             double *best_obj, double *obj, int *improved, int *trials, int *completed, int *last_accepted);
 
 extern "C" {
 

@@ -114,7 +114,7 @@ struct tsp_dev_inst {
     // d_gbox[g] = {min x, max x, min y, max y} of group g's nodes (the padding group sits far away).
     int *d_sperm = nullptr;
     double4 *d_gbox = nullptr;
-    std::vector<double4> h_gbox;   // host copy (pair table of the sorted sweep)
+    std::vector<double4> h_gbox;   // host copy (pair tables of the sorted sweep and scan: read as ng x 4 doubles, cluster_deal.hpp)
     int ng = 0, n_slots = 0;
     double org_x = 0.0, org_y = 0.0;   // min corner of the coordinates
     double cost_bound = 1e300;         // no distance of the instance exceeds this (bounding-box diagonal + rounding)
@@ -132,6 +132,7 @@ struct tsp_dev_inst {
     void *nl_data = nullptr;    // neighbour lists and the buffers of their descent (nl_opt.hip)
     void *hk_data = nullptr;    // 1-tree / Held-Karp buffers (held_karp.hip)
 };
+static_assert(sizeof(double4) == 4 * sizeof(double), "tsp_dev_inst::h_gbox is handed to cluster_deal as ng x {min x, max x, min y, max y}");
 
 struct tsp_dev_tabu {
     tsp_dev_inst *inst = nullptr;
@@ -187,7 +188,6 @@ struct tsp_dev_tours {
     size_t cl_slot_words = 0;
     int cl_C = 0;
     long long *d_cl_stats = nullptr; // B x 256 x 4: the CLUSTER engine's executed-work counters per workgroup (summed at download)
-    bool cl_tabu_plan = false;       // the CLUSTER engine is being asked about / run for a descent with a tabu list
     unsigned cl_epoch = 0;           // exchange epochs handed out so far (they run on from launch to launch)
     int *d_cl_pairtab = nullptr;
     int cl_ntests = 0;
@@ -196,27 +196,7 @@ struct tsp_dev_tours {
     std::vector<double> h_obj_snap;
     int *d_kick_result = nullptr;    // 8 ints: {accepted, a1, b1, 0, acted, improved, 0, 0}
     int *h_kick_result = nullptr;    // pinned
-    // work a driver wants queued right behind the FIRST launch of a CLUSTER run, before the run's wait for the device
-    // (tabu(): incumbent snapshot + kick decided on the device from the finished descent -- one wait per iteration, not two)
-    void (*cl_post)(void *ctx, hipStream_t s, const int *d_err) = nullptr;
-    void *cl_post_ctx = nullptr;
-    bool cl_post_ran = false;
-    // ... and FURTHER runs of the same kind queued behind it without a wait in between (K iterations of tabu() per wait for the
-    // device): cl_chain(ctx, s, k, &iter, &tenure) queues what precedes launch k >= 1 (a re-arm that a stop word on the device
-    // can veto) and says with which iter / tenure it runs, or returns false when the chain ends; after launch k the run calls
-    // cl_post_k(ctx, s, k, d_err).  cl_chain_launched = launches queued in all (1 + the chained ones).
-    bool (*cl_chain)(void *ctx, hipStream_t s, int k, int *iter, int *tenure) = nullptr;
-    void (*cl_post_k)(void *ctx, hipStream_t s, int k, const int *d_err) = nullptr;
-    int cl_chain_launched = 0;
-    // device words of a chain: [0] stop (set by a post kernel: every later launch of the chain is a no-op), [2..3] the incumbent's
-    // cost (double), then per launch 8 ints of result + 1 double of cost
-    int *d_chain = nullptr;
-    int *h_chain = nullptr;          // pinned mirror
-    // ... or INSIDE one launch (TSP_TABU_INKERNEL, the default): the kernel runs cl_ik_n iterations with the kick's first trials
-    // the tenures and the host-drawn kick trials behind the result words of d_chain, keeps the incumbent in d_order_snap and writes the same result words
-    int cl_ik_n = 0;
-    int cl_ik_par = 0;               // offsets into d_chain: the tenures, ...
-    int cl_ik_pairs = 0, cl_ik_ab = 0, cl_ik_pp = 0;   // ... the kick trials (count; 0 = one per iteration), and where the next trial's index lives
+    int *d_chain = nullptr, *h_chain = nullptr;   // device words of a chain of tabu() iterations (tabu_chain.hpp), pinned mirror
     bool h_state_fresh = false;   // h_state holds what d_state holds (set by a CLUSTER run's last poll, cleared by whatever queues work after it)
     int *h_cl_err = nullptr;         // pinned: the CLUSTER engine's error word, read with every poll
     bool tabu_list_run = false;      // the current tsp_grid_run goes through k_sweep<TABU> (two_opt_tabu_list.hpp)
@@ -264,11 +244,58 @@ struct HkTree {
     long long rounds = 0;
     float device_ms = 0.f;
 };
+// What a tabu() driver hands down through tsp_tabu_run to tsp_cluster_run: the list the descent runs with, and the work the
+// CLUSTER run queues for the driver behind its launches, before the run's wait for the device (one wait per iteration of tabu(),
+// or per chain of them, instead of two).  Plain data; the arrays are the caller's.
+struct TabuRide {
+    tsp_dev_tabu *tabu = nullptr;   // the list counts when tabu && iter >= 0 && tenure >= 0 (check_tenure, tabusearch.c:84)
+    int iter = 0, tenure = 0;
+    // iterations INSIDE the launch (TSP_TABU_INKERNEL, the default): the kernel runs ik_n of them from the words the driver has
+    // put into d_chain (tabu_chain.hpp) and keeps the incumbent in d_order_snap; ik_pairs = kick trials there (0: one per iteration)
+    int ik_n = 0, ik_pairs = 0;
+    // ... or queued behind the run's FIRST launch (tsp_grid_tabu_follow).  kPost: k_tabu_post -- incumbent (cost `best`) and the
+    // kick's trial a, b decided on the device from the finished descent.  kChain: the same by k_tabu_post_chain, then launch
+    // k = 1 .. count - 1 of the same kernel as iteration iter + k with tenures[k], each followed by its own k_tabu_post_chain
+    // (trial ab[2k], ab[2k + 1]): a stop word on the device turns what follows a failed iteration into no-ops.
+    enum Follow { kNone, kPost, kChain } follow = kNone;
+    int a = 0, b = 0, count = 0;
+    double best = 0.0;
+    const int *tenures = nullptr, *ab = nullptr;
+    // what the run reports back
+    bool follow_ran = false;   // the follow-up of the first launch was queued
+    int launched = 0;          // launches queued in all (1 + the chained ones)
+};
 }
 int tsp_hk_tree(tsp_dev_inst *inst, const double *pi, tsp::HkTree *out, tsp_lb_stats *stats);   // held_karp.hip
 int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr);                                  // nl_opt.hip: takes d_nbr over
 tsp_dev_tours *tsp_scratch_tours(tsp_dev_inst *inst, int B, bool *owned, int *rc);             // api.hip
-int tsp_grid_tour_cost(tsp_dev_tours *t, double *d_out);                                        // two_opt_grid.hip
+int tsp_perm_cost_device(tsp_dev_inst *inst, const int *d_perm, long long stride, int B, double *d_out, size_t out_stride_bytes);   // api.hip
+void tsp_or_scratch_free(void *p);   // or_opt.hip
+void tsp_nl_data_free(void *p);      // nl_opt.hip
+void tsp_hk_data_free(void *p);      // held_karp.hip
+int tsp_lds_run(tsp_dev_tours *t, int mode, double time_limit_s, int *all_done);   // two_opt_lds.hip
+bool tsp_lds_fits(const tsp_dev_inst *inst);
+// two_opt_cluster.hip.  tabu_list: the run carries a tabu list (it takes the sorted scan at any size); ride: nullptr = none
+bool tsp_cluster_fits(const tsp_dev_tours *t, int mode, bool tabu_list = false);
+bool tsp_cluster_sorted(const tsp_dev_tours *t, int mode, bool tabu_list = false);
+int tsp_cluster_size(const tsp_dev_tours *t, int mode, bool tabu_list = false);
+int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double time_limit_s, int *all_done, int *fell_through,
+                    tsp::TabuRide *ride = nullptr);
+// two_opt_grid.hip
+int tsp_grid_tour_cost(tsp_dev_tours *t, double *d_out);
+int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int tenure, int64_t max_steps,
+                 double time_limit_s, int sync, int *all_done);
+int tsp_grid_after_external_run(tsp_dev_tours *t, int mode, int timed_out, bool pos_written = false);
+void tsp_grid_tabu_follow(tsp_dev_tours *t, const tsp::TabuRide &r, int k, const int *d_err);
+int tsp_grid_rearm(tsp_dev_tours *t, int mode);
+int tsp_grid_tabu_kick(tsp_dev_tours *t, tsp_dev_tabu *tabu, int a, int b, int iter, int tenure, int *accepted);
+int tsp_grid_vns_kick(tsp_dev_tours *t, int p1, int p2, int p3, double *obj);
+int tsp_grid_snapshot(tsp_dev_tours *t, bool restore);
+int tsp_grid_resident_tabu(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int tenure, double time_limit_s, double *obj);
+int tsp_grid_tabu_iteration(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int tenure, double time_limit_s, int a, int b,
+                            double *best_obj, double *obj, int *improved, int *accepted);
+int tsp_grid_tabu_iterations(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter0, int count, const int *tenure, int pairs, const int *ab, double time_limit_s,
+                             double *best_obj, double *obj, int *improved, int *trials, int *completed, int *last_accepted);
 
 // Per-instance scratch for the host-array entry points (not for concurrent use, like every handle): >= bytes, 256-aligned.
 void *tsp_io_pool(tsp_dev_inst *inst, size_t bytes);

@@ -30,6 +30,8 @@
 // Residency: the cluster protocol needs all B C workgroups on the chip at once; the host launches at most one per CU
 // and every spin is bounded (a workgroup that gives up raises `err`, everybody leaves, the host falls back to GRID).
 #include "two_opt_common.hpp"
+#include "cluster_deal.hpp"
+#include "tabu_chain.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -89,8 +91,8 @@ struct ClusterArgs {
     const int *tabu_list_n;
     int tabu_list_cap, iter, tenure;
     unsigned long long *tabu_side;
-    // iterations of tabu() inside the launch (TABU variant; chain_n == 0: one descent, as ever): chain = {stop word, next iteration
-    // of the chain, the incumbent's cost (double), 10 result words per iteration}, chain_par = the tenure per iteration; the kick's trials are host-drawn (chain_ab), snap = the incumbent's tour (nodes by position)
+    // iterations of tabu() inside the launch (TABU variant; chain_n == 0: one descent, as ever): chain = the handle's d_chain
+    // (tabu_chain.hpp: stop word, next iteration, the incumbent's cost, the result words per iteration), chain_par = the tenure per iteration; the kick's trials are host-drawn (chain_ab), snap = the incumbent's tour (nodes by position)
     int *chain;
     const int *chain_par;
     int chain_n;
@@ -507,16 +509,16 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
     int *order_g = a.orders + (size_t)tour * n;
     gu64 *area = (gu64 *)a.slots + (size_t)tour * 2 * kClCopies * C * kClSlotGranules;
     // the iteration of tabu() this launch is at (its number and tenure decide what is tabu): a launch that carries a chain of
-    // iterations goes on where the launch before it stopped (chain[1])
+    // iterations goes on where the launch before it stopped (chain[kChainResume])
     int cur_iter = a.iter, cur_ten = a.tenure, ck = 0, kpp = 0;   // kpp: the pair the next kick trial takes
     int4 nx_pair = make_int4(0, 0, 0, 0);   // ... fetched ahead ({a, b, a and b inside the replica}: asked for when the kick before it is through)
     int nx_pp = -1;
     double inc_best = 0.0;
     if constexpr (TABU) {
         if (a.chain_n > 0) {
-            ck = a.chain[1];
+            ck = a.chain[kChainResume];
             cur_iter = a.iter + ck; cur_ten = a.chain_par[ck];
-            inc_best = *reinterpret_cast<const double *>(a.chain + 2);
+            inc_best = *reinterpret_cast<const double *>(a.chain + kChainBest);
             kpp = a.chain_pairs > 0 ? *a.chain_pp : ck;
             if (kpp < (a.chain_pairs > 0 ? a.chain_pairs : a.chain_n)) { nx_pair = reinterpret_cast<const int4 *>(a.chain_ab)[kpp]; nx_pp = kpp; }
         }
@@ -1316,10 +1318,11 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                     // accounting can ask for (live() has no side effect: reading one the reference's && chain would not have
                     // reached changes nothing) -- two round trips to memory instead of six to eight.  What is left of them costs
                     // 1.5 us of a sweep (the workgroup that publishes last has only the rest of the exchange to hide its entry
-                    // behind).  Measured and not kept: the entry's last contribution remembered with the neighbours it was
-                    // computed from (no load at all in most sweeps: +6 us per iteration); the first round trip issued before
-                    // the scan (+3 us: every wait for a load in the scan then waits for it too); the first workgroup left out of
-                    // the group-pair table (no difference).
+                    // behind).  The workgroup's first entry (k0) keeps its last contribution with the four tour neighbours it was
+                    // computed from (tl_state / tl_cnt / tl_edge, tl_nb0 / tl_nb1: replica ids, two 16-bit halves each -- cl_plan's
+                    // n <= 65534): as long as they are the same, and no kick has come between, the stamps are not read again.
+                    // Measured and not kept: the first round trip issued before the scan (+3 us: every wait for a load in the scan
+                    // then waits for it too); the first workgroup left out of the group-pair table (no difference).
                     const bool mine = k == k0;
                     if (mine && tl_state == 1) {
 #ifdef TSP_STAMPS
@@ -1528,7 +1531,7 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                     // unchanged (111.2 us with two-sided fences at the boundary, 108.4 with the one-sided ones): the boundary's exchange,
                     // behind 256 simultaneous L2 write-backs, is what the tail waits for.
                     const int npairs = a.chain_pairs > 0 ? a.chain_pairs : a.chain_n;
-                    int *res = a.chain + 4 + 10 * ck;
+                    int *res = a.chain + kChainRes + kChainResWords * ck;
                     int *s_kick = reinterpret_cast<int *>(s_chunk);   // {accepted, have0, have1, a1, b1, entries appended, pair taken}: the cost's chunks are through
                     int better_inc = 0, trials = 0;
                     __syncthreads();
@@ -1658,13 +1661,13 @@ __global__ __launch_bounds__(kClThreads) void k_cluster_two_opt(const ClusterArg
                     }
 #endif
                     if (c == 0 && tid == 0) {   // res as k_tabu_post_chain leaves it; read by the host after the launch
-                        res[0] = kicked ? 1 : 0; res[1] = kicked ? ka1 : s_kick[3]; res[2] = kicked ? kb1 : s_kick[4]; res[3] = trials;
-                        res[4] = 1; res[5] = better_inc; res[6] = 0; res[7] = 0;
-                        *reinterpret_cast<double *>(res + 8) = obj;
-                        *reinterpret_cast<double *>(a.chain + 2) = inc_best;
-                        a.chain[1] = ck + 1;
+                        res[kResAccepted] = kicked ? 1 : 0; res[kResA1] = kicked ? ka1 : s_kick[3]; res[kResB1] = kicked ? kb1 : s_kick[4]; res[kResTrials] = trials;
+                        res[kResRan] = 1; res[kResImproved] = better_inc; res[kResWhy] = 0; res[7] = 0;
+                        *reinterpret_cast<double *>(res + kResCost) = obj;
+                        *reinterpret_cast<double *>(a.chain + kChainBest) = inc_best;
+                        a.chain[kChainResume] = ck + 1;
                         if (a.chain_pairs > 0) *a.chain_pp = kpp + trials;
-                        if (!kicked) a.chain[0] = 1;   // rejected (and no pair left to try): the host draws the next trial (tabusearch.c:262-287)
+                        if (!kicked) a.chain[kChainStop] = 1;   // rejected (and no pair left to try): the host draws the next trial (tabusearch.c:262-287)
                     }
                     ck += 1;
                     if ((a.dbg & 2048) && c == 1 && ck >= 2) return;   // test hook: a workgroup stops answering in the middle of a chain
@@ -1793,16 +1796,17 @@ struct ClPlan {
 
 // Which scan a run in `mode` uses on this handle, and whether the replica fits in LDS.
 // want_fs: first improvement on the rank-order replica (the variant a sparse phase of a single tour's descent is handed to)
-ClPlan cl_plan(const tsp_dev_tours *t, int mode, bool want_fs = false) {
+ClPlan cl_plan(const tsp_dev_tours *t, int mode, bool tabu_list, bool want_fs = false) {
     ClPlan p;
     const tsp_dev_inst *inst = t->inst;
-    if (inst->n > 65534) return p;
+    if (inst->n > 65534) return p;   // replica ids are 16 bits wide (idx_t; the tabu scan's remembered neighbours pack two into a word)
+    static_assert(sizeof(idx_t) == 2, "the replicas and the tabu scan's remembered neighbours (tl_nb0 / tl_nb1) hold 16-bit ids");
     const int wt = inst->wtype;
     p.float_coords = wt == WT_EUC_2D_ICOORD || wt == WT_CEIL_2D_ICOORD || wt == WT_ATT_ICOORD;
     // (runs with a tabu list take the sorted scan at any size: their list code rides on it, and the alternative reads four
     // stamps per pair -- two_opt_tabu_list.hpp)
     p.sorted = inst->d_sperm && inst->prune_margin < 1e299 && inst->ng <= 32768 &&
-               (mode == TSP_2OPT_BEST ? (inst->n >= t->cl_sorted_min_n || (t->cl_tabu_plan && inst->n >= 8))
+               (mode == TSP_2OPT_BEST ? (inst->n >= t->cl_sorted_min_n || (tabu_list && inst->n >= 8))
                                       // first improvement: sparse phases of larger instances (a sweep of the tiles scan that finds
                                       // nothing is 217 us at n = 10 000; a box-pruned step 12 us).  Measured on HEU_VNS rounds
                                       // (tools/vns_time.py): no gain at n = 1 002 / 2 000, -7 % at 5 000, -19 % at 10 000
@@ -1866,56 +1870,35 @@ hipError_t cl_launch(tsp_dev_tours *t, int mode, const ClPlan &p, const ClusterA
 }
 }  // namespace
 
-// implemented in two_opt_grid.hip
-int tsp_grid_after_external_run(tsp_dev_tours *t, int mode, int timed_out, bool pos_written = false);
-
 #ifdef TSP_STAMPS
-// diagnostic: per workgroup of tour 0, 100 MHz ticks per phase {tests, scan, block arg-min, exchange, counters, move, -, steps}; resets
-extern "C" int tsp_dev_debug_cluster(unsigned long long *out /* 256 x 8 */) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(tsp::g_cl_prof), sizeof(unsigned long long) * 256 * 8) != hipSuccess) return -1;
-    static unsigned long long z[256 * 8];
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(tsp::g_cl_prof), z, sizeof z);
+// diagnostics: one of the kernel's stamp arrays read, and zeroed
+template <typename S>
+static int cl_debug_take(S &sym, unsigned long long *out) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(sym), sizeof(S)) != hipSuccess) return -1;
+    static const S z = {};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(sym), &z, sizeof(S));
     return 0;
 }
-extern "C" int tsp_dev_debug_cluster_tail(unsigned long long *out /* 256 x 12 */) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(tsp::g_cl_tail), sizeof(unsigned long long) * 256 * 12) != hipSuccess) return -1;
-    static unsigned long long z[256 * 12];
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(tsp::g_cl_tail), z, sizeof z);
-    return 0;
-}
-extern "C" int tsp_dev_debug_cluster_wstat(unsigned long long *out /* 256 x 4 */) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(tsp::g_cl_wstat), sizeof(unsigned long long) * 256 * 4) != hipSuccess) return -1;
-    static unsigned long long z[256 * 4];
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(tsp::g_cl_wstat), z, sizeof z);
-    return 0;
-}
-extern "C" int tsp_dev_debug_cluster_b0(unsigned long long *out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(tsp::g_cl_b0), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    unsigned long long z[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(tsp::g_cl_b0), z, sizeof z);
-    return 0;
-}
-extern "C" int tsp_dev_debug_cluster_counts(unsigned long long *out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(tsp::g_cl_cnt), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    unsigned long long z[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(tsp::g_cl_cnt), z, sizeof z);
-    return 0;
-}
+// per workgroup of tour 0, 100 MHz ticks per phase {tests, scan, block arg-min, exchange, counters, move, -, steps}
+extern "C" int tsp_dev_debug_cluster(unsigned long long *out /* 256 x 8 */) { return cl_debug_take(tsp::g_cl_prof, out); }
+extern "C" int tsp_dev_debug_cluster_tail(unsigned long long *out /* 256 x 12 */) { return cl_debug_take(tsp::g_cl_tail, out); }
+extern "C" int tsp_dev_debug_cluster_wstat(unsigned long long *out /* 256 x 4 */) { return cl_debug_take(tsp::g_cl_wstat, out); }
+extern "C" int tsp_dev_debug_cluster_b0(unsigned long long *out8) { return cl_debug_take(tsp::g_cl_b0, out8); }
+extern "C" int tsp_dev_debug_cluster_counts(unsigned long long *out8) { return cl_debug_take(tsp::g_cl_cnt, out8); }
 #endif
 
-bool tsp_cluster_fits(const tsp_dev_tours *t, int mode) { return t && cl_plan(t, mode).ok; }
-bool tsp_cluster_sorted(const tsp_dev_tours *t, int mode) { return t && cl_plan(t, mode).sorted; }
+bool tsp_cluster_fits(const tsp_dev_tours *t, int mode, bool tabu_list) { return t && cl_plan(t, mode, tabu_list).ok; }
+bool tsp_cluster_sorted(const tsp_dev_tours *t, int mode, bool tabu_list) { return t && cl_plan(t, mode, tabu_list).sorted; }
 
 // Cluster size for B tours on this device: one workgroup per CU at most, whole clusters only.
-int tsp_cluster_size(const tsp_dev_tours *t, int mode) {
+int tsp_cluster_size(const tsp_dev_tours *t, int mode, bool tabu_list) {
     const int cus = std::max(1, t->inst->ctx->num_cus);
     int C = std::max(1, std::min(256, cus / std::max(1, t->B)));
-    const ClPlan p = cl_plan(t, mode);
+    const ClPlan p = cl_plan(t, mode, tabu_list);
     if (p.sorted) {   // no more workgroups than a few group pairs each
         const long long npairs = (long long)t->inst->ng * (t->inst->ng + 1) / 2;
         C = (int)std::max<long long>(1, std::min<long long>(C, (npairs + 3) / 4));
-    }
-    if (!p.sorted) {
+    } else {
         const long long nb = (t->n + kClThreads - 1) / kClThreads, nrb = (t->n - 1 + kClRows - 1) / kClRows;
         C = (int)std::max<long long>(1, std::min<long long>(C, nb * nrb));
         // first improvement: a step scans a few dozen rows, and the exchange gets slower with every workgroup that takes part
@@ -1925,174 +1908,94 @@ int tsp_cluster_size(const tsp_dev_tours *t, int mode) {
     return std::max(1, TSP_SW(t->inst, CLUSTER_BLOCKS, C));
 }
 
-// Runs the tours of `t` to their local optima with C workgroups per tour.  Returns TSP_DEV_E_HIP with
-// *fell_through = 1 when the cluster protocol gave up (a workgroup was not resident): the tours in HBM are
-// then exactly as uploaded by the last launch that completed and the caller may continue with another engine.
-// max_steps >= 0 caps the steps per tour (a capped best-improvement run gets its recomputed cost like a timed-out one).
-int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double time_limit_s, int *all_done, int *fell_through,
-                    tsp_dev_tabu *tabu, int iter, int tenure) {
-    if (fell_through) *fell_through = 0;
-    if (all_done) *all_done = 0;
-    if (!t || C < 1 || C > 256) return TSP_DEV_E_ARG;
-    const ClPlan p = cl_plan(t, mode);
-    if (!p.ok) return TSP_DEV_E_ARG;
-    tsp_dev_inst *inst = t->inst;
+// ---- the stages of tsp_cluster_run ----------------------------------------------------------------------------------------
+namespace {
+
+// per-instance tables of the sorted scan: coordinates in rank order (padding far away), node -> rank
+int cl_instance_tables(tsp_dev_inst *inst) {
+    if (inst->d_rcoord) return TSP_OK;
+    const int nid_sorted = inst->ng * 64;
+    std::vector<double2> rc((size_t)nid_sorted);
+    std::vector<int> sperm((size_t)inst->n_slots);
+    TSP_HIP_TRY(hipMemcpy(sperm.data(), inst->d_sperm, sizeof(int) * sperm.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < nid_sorted; ++k) {
+        const int v = sperm[k];
+        rc[k] = v >= 0 ? make_double2(inst->h_xy[2 * (size_t)v], inst->h_xy[2 * (size_t)v + 1]) : make_double2(1e30, 1e30);
+    }
+    TSP_HIP_TRY(hipMalloc(&inst->d_rcoord, sizeof(double2) * rc.size()));
+    TSP_HIP_TRY(hipMemcpy(inst->d_rcoord, rc.data(), sizeof(double2) * rc.size(), hipMemcpyHostToDevice));
+    TSP_HIP_TRY(hipMalloc(&inst->d_sinv, sizeof(int) * (size_t)inst->n));
+    TSP_HIP_TRY(hipMemcpy(inst->d_sinv, inst->h_sinv.data(), sizeof(int) * (size_t)inst->n, hipMemcpyHostToDevice));
+    return TSP_OK;
+}
+
+// per-handle: the exchange area (+ the error word) of C workgroups per tour; the group-pair table dealt for another C goes
+int cl_exchange_area(tsp_dev_tours *t, int C) {
+    if (t->cl_C == C && t->d_cl_slots) return TSP_OK;
+    hipStream_t s = t->inst->ctx->stream;
+    (void)hipFree(t->d_cl_slots); t->d_cl_slots = nullptr;
+    (void)hipFree(t->d_cl_pairtab); t->d_cl_pairtab = nullptr;
+    t->cl_ntests = 0;
+    const size_t words = (size_t)t->B * 2 * kClCopies * C * kClSlotGranules + 2;   // + the error word
+    TSP_HIP_TRY(hipMalloc(&t->d_cl_slots, sizeof(unsigned long long) * words));
+    t->cl_slot_words = words;
+    TSP_HIP_TRY(hipMemsetAsync(t->d_cl_slots, 0, sizeof(unsigned long long) * words, s));
+    t->cl_epoch = 0;
+    t->cl_C = C;
+    return TSP_OK;
+}
+
+// per-handle: the group-pair table dealt to C workgroups (cluster_deal.hpp) -- a single tour's by estimated cost on the tour
+// the handle holds now, else in turn
+int cl_pair_table(tsp_dev_tours *t, int C) {
+    if (t->d_cl_pairtab) return TSP_OK;
+    const tsp_dev_inst *inst = t->inst;
+    hipStream_t s = inst->ctx->stream;
+    const bool by_cost = C > 1 && t->B == 1;
+    std::vector<int> order, sperm;
+    if (by_cost) {
+        order.resize((size_t)t->n);
+        // on the engine's stream (created non-blocking: a null-stream copy is not ordered behind work queued on it -- a kick
+        // that was not waited for could still be rewriting the tour), then one wait
+        TSP_HIP_TRY(hipMemcpyAsync(order.data(), t->d_order, sizeof(int) * (size_t)t->n, hipMemcpyDeviceToHost, s));
+        TSP_HIP_TRY(hipStreamSynchronize(s));
+        sperm.resize((size_t)inst->n_slots);
+        TSP_HIP_TRY(hipMemcpy(sperm.data(), inst->d_sperm, sizeof(int) * sperm.size(), hipMemcpyDeviceToHost));   // per-instance, written once at creation
+    }
+    std::vector<int> tab;
+    const long long ntests = cluster_deal(reinterpret_cast<const double *>(inst->h_gbox.data()), sperm.data(), inst->h_xy.data(),
+                                          by_cost ? order.data() : nullptr, t->n, inst->ng, C, by_cost,
+                                          inst->wtype_public == TSP_ATT ? 1.0 / sqrt(10.0) : 1.0, tab);
+    TSP_HIP_TRY(hipMalloc(&t->d_cl_pairtab, tab.size() * sizeof(int)));
+    TSP_HIP_TRY(hipMemcpy(t->d_cl_pairtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    t->cl_ntests = (int)ntests;
+    return TSP_OK;
+}
+
+// what depends on the numbering of the replica
+void cl_set_plan(ClusterArgs &a, const tsp_dev_inst *inst, const ClPlan &q) {
+    a.coord = q.sorted ? inst->d_rcoord : inst->d_coord;
+    a.gid = q.sorted ? inst->d_sperm : nullptr;
+    a.iid = q.sorted ? inst->d_sinv : nullptr;
+    a.nid = q.nid;
+    a.stage_pairs = q.stage_pairs;
+}
+
+// The kernel's arguments from the handle, the plan, the switches and what rides on the run; max_iters and epoch0 are each
+// launch's own.  tabu: the ride's list when it counts (the caller has brought it up to date, tsp_tabu_list_prepare, and zeroed
+// the side words), else nullptr.
+int cl_args(tsp_dev_tours *t, int mode, int C, const ClPlan &p, bool fs_avail, int fs_rows, int64_t max_steps, tsp_dev_tabu *tabu,
+            const TabuRide *ride, ClusterArgs &a) {
+    const tsp_dev_inst *inst = t->inst;
     hipStream_t s = inst->ctx->stream;
     const int n = t->n, B = t->B;
-    // all workgroups must be resident (TSP_CLUSTER_ALLOW_OVERSUB=1 lifts the check: the tests use it to drive the give-up path)
-    if (C > 1 && (long long)B * C > std::max(1, inst->ctx->num_cus) && !TSP_SW(inst, CLUSTER_ALLOW_OVERSUB, 0)) return TSP_DEV_E_ARG;
-
-    // First improvement of a single tour: two variants of the kernel hand the descent to each other between launches -- the plain
-    // replica (probe + tiles at full speed) while hits come close together, the replica in rank order with the box-pruned step
-    // once the running mean of the rows between hits (TourState::hit_rows, kept by both) passes fs_rows, back below fs_rows / 4.
-    ClPlan pf;   // the rank-order variant's plan
-    bool fs_avail = false;
-    const int fs_rows = std::max(0, TSP_SW(inst, CLUSTER_FS_ROWS, 120));   // 80 .. 200 measure alike (rand10000: alg_2opt 20.7 ms, VNS round 3.4 ms)
-    if (mode == TSP_2OPT_FIRST && B == 1 && fs_rows > 0 && max_steps < 0) {
-        pf = cl_plan(t, mode, /*want_fs=*/true);
-        const long long npairs = (long long)inst->ng * (inst->ng + 1) / 2;
-        fs_avail = pf.ok && pf.sorted && C <= (npairs + 3) / 4;
-    }
-    // per-instance tables of the sorted scan: coordinates in rank order (padding far away), node -> rank
-    if ((p.sorted || fs_avail) && !inst->d_rcoord) {
-        const int nid_sorted = inst->ng * 64;
-        std::vector<double2> rc((size_t)nid_sorted);
-        std::vector<int> sperm((size_t)inst->n_slots);
-        TSP_HIP_TRY(hipMemcpy(sperm.data(), inst->d_sperm, sizeof(int) * sperm.size(), hipMemcpyDeviceToHost));
-        for (int k = 0; k < nid_sorted; ++k) {
-            const int v = sperm[k];
-            rc[k] = v >= 0 ? make_double2(inst->h_xy[2 * (size_t)v], inst->h_xy[2 * (size_t)v + 1]) : make_double2(1e30, 1e30);
-        }
-        TSP_HIP_TRY(hipMalloc(&inst->d_rcoord, sizeof(double2) * rc.size()));
-        TSP_HIP_TRY(hipMemcpy(inst->d_rcoord, rc.data(), sizeof(double2) * rc.size(), hipMemcpyHostToDevice));
-        TSP_HIP_TRY(hipMalloc(&inst->d_sinv, sizeof(int) * (size_t)n));
-        TSP_HIP_TRY(hipMemcpy(inst->d_sinv, inst->h_sinv.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    }
-    // per-handle: exchange area, error word, and the group-pair table dealt to C workgroups
-    if (t->cl_C != C || !t->d_cl_slots) {
-        (void)hipFree(t->d_cl_slots); t->d_cl_slots = nullptr;
-        (void)hipFree(t->d_cl_pairtab); t->d_cl_pairtab = nullptr;
-        t->cl_ntests = 0;
-        const size_t words = (size_t)B * 2 * kClCopies * C * kClSlotGranules + 2;   // + the error word
-        TSP_HIP_TRY(hipMalloc(&t->d_cl_slots, sizeof(unsigned long long) * words));
-        t->cl_slot_words = words;
-        TSP_HIP_TRY(hipMemsetAsync(t->d_cl_slots, 0, sizeof(unsigned long long) * words, s));
-        t->cl_epoch = 0;
-        t->cl_C = C;
-    }
-    if ((p.sorted || fs_avail) && !t->d_cl_pairtab) {
-        const int ng = inst->ng;
-        const long long npairs = (long long)ng * (ng + 1) / 2;
-        const long long ntests = (npairs + C - 1) / C;
-        std::vector<std::pair<double, int>> pr((size_t)npairs);
-        size_t w = 0;
-        for (int r = 0; r < ng; ++r)
-            for (int cg = r; cg < ng; ++cg) {
-                const double4 &rb = inst->h_gbox[r], &cb = inst->h_gbox[cg];
-                const double gx = std::max(0.0, std::max(rb.x - cb.y, cb.x - rb.y)), gy = std::max(0.0, std::max(rb.z - cb.w, cb.z - rb.w));
-                pr[w++] = {gx * gx + gy * gy, (r << 16) | cg};
-            }
-        std::sort(pr.begin(), pr.end());
-        std::vector<int> tab((size_t)C * ntests, -1);
-        bool dealt = false;
-        if (C > 1 && B == 1) {
-            // Deal by estimated cost instead of in turn.  A step costs the time of its slowest workgroup (1.9 us of an 11.4 us
-            // best-improvement step at n = 10 000 were spent waiting for it), and what a group pair costs is decided by the tour:
-            // whether it survives the box test and how many of its rows survive the culling.  Both are estimated here on the
-            // tour the handle holds now (Euclidean lengths: a cost model, not a decision), the survivors are dealt heaviest
-            // first to the least loaded workgroup (LPT), the others fill the tables up in turn.  Every pair is still tested in
-            // every step; only who tests it changes.
-            std::vector<int> order((size_t)n);
-            // on the engine's stream (created non-blocking: a null-stream copy is not ordered behind work queued on it -- a kick
-            // that was not waited for could still be rewriting the tour), then one wait
-            TSP_HIP_TRY(hipMemcpyAsync(order.data(), t->d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
-            TSP_HIP_TRY(hipStreamSynchronize(s));
-            const double sc = (inst->wtype_public == TSP_ATT) ? 1.0 / sqrt(10.0) : 1.0;
-            auto X = [&](int v) { return inst->h_xy[2 * (size_t)v]; };
-            auto Y = [&](int v) { return inst->h_xy[2 * (size_t)v + 1]; };
-            auto len = [&](int u, int v) { return sc * sqrt((X(u) - X(v)) * (X(u) - X(v)) + (Y(u) - Y(v)) * (Y(u) - Y(v))) + 1.0; };
-            std::vector<double> ds((size_t)n, 0.0), inc((size_t)n, 0.0), gmx((size_t)ng, 0.0);
-            bool tour_ok = true;
-            for (int q = 0; q < n && tour_ok; ++q) tour_ok = order[q] >= 0 && order[q] < n;
-            if (tour_ok) {
-                for (int q = 0; q < n; ++q) {
-                    const int v = order[q], su = order[q + 1 == n ? 0 : q + 1], pv = order[q == 0 ? n - 1 : q - 1];
-                    ds[v] = len(v, su);
-                    inc[v] = std::max(ds[v], len(v, pv));
-                }
-                std::vector<int> sperm((size_t)inst->n_slots);
-                TSP_HIP_TRY(hipMemcpy(sperm.data(), inst->d_sperm, sizeof(int) * sperm.size(), hipMemcpyDeviceToHost));   // per-instance, written once at creation
-                for (int g = 0; g < ng; ++g)
-                    for (int k = 0; k < 64; ++k) { const int v = sperm[(size_t)g * 64 + k]; if (v >= 0) gmx[g] = std::max(gmx[g], inc[v]); }
-                struct Item { double cost; int e; };
-                std::vector<Item> heavy, light;
-                for (long long k = 0; k < npairs; ++k) {
-                    const int e = pr[(size_t)k].second, r = e >> 16, cg = e & 0xffff;
-                    const double T = gmx[r] + gmx[cg] + 2.0;
-                    double cost = 0.0;
-                    if (sc * sc * pr[(size_t)k].first < T * T) {
-                        const double4 &cb = inst->h_gbox[cg];
-                        int live = 0;
-                        for (int q = 0; q < 64; ++q) {
-                            const int v = sperm[(size_t)r * 64 + q];
-                            if (v < 0) continue;
-                            const double gx = std::max(0.0, std::max(cb.x - X(v), X(v) - cb.y)), gy = std::max(0.0, std::max(cb.z - Y(v), Y(v) - cb.w));
-                            const double Tr = ds[v] + gmx[cg] + 2.0;
-                            live += sc * sc * (gx * gx + gy * gy) < Tr * Tr;
-                        }
-                        cost = 8.0 + live;   // staging the pair's 128 records + its live rows against 64 columns
-                    }
-                    (cost > 0.0 ? heavy : light).push_back({cost, e});
-                }
-                std::stable_sort(heavy.begin(), heavy.end(), [](const Item &x, const Item &y) { return x.cost > y.cost; });
-                std::vector<double> load((size_t)C, 0.0);
-                std::vector<int> cnt((size_t)C, 0);
-                // least loaded workgroup with room: a heap keyed by load
-                std::vector<std::pair<double, int>> heap;
-                for (int w = 0; w < C; ++w) heap.push_back({0.0, w});
-                auto cmp = [](const std::pair<double, int> &x, const std::pair<double, int> &y) { return x.first > y.first || (x.first == y.first && x.second > y.second); };
-                std::make_heap(heap.begin(), heap.end(), cmp);
-                for (const Item &it : heavy) {
-                    std::pop_heap(heap.begin(), heap.end(), cmp);
-                    auto top = heap.back(); heap.pop_back();
-                    const int w = top.second;
-                    tab[(size_t)w * ntests + (size_t)cnt[w]++] = it.e;
-                    load[w] += it.cost;
-                    if (cnt[w] < ntests) { heap.push_back({load[w], w}); std::push_heap(heap.begin(), heap.end(), cmp); }
-                }
-                int w = 0;
-                for (const Item &it : light) {   // the rest in turn, wherever there is room
-                    while (cnt[w] >= ntests) w = (w + 1) % C;
-                    tab[(size_t)w * ntests + (size_t)cnt[w]++] = it.e;
-                    w = (w + 1) % C;
-                }
-                dealt = true;
-            }
-        }
-        if (!dealt)
-            for (long long k = 0; k < npairs; ++k) tab[(size_t)(k % C) * ntests + (size_t)(k / C)] = pr[(size_t)k].second;
-        TSP_HIP_TRY(hipMalloc(&t->d_cl_pairtab, tab.size() * sizeof(int)));
-        TSP_HIP_TRY(hipMemcpy(t->d_cl_pairtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-        t->cl_ntests = (int)ntests;
-    }
-
-    ClusterArgs a;
-    auto set_plan = [&](const ClPlan &q) {   // what depends on the numbering of the replica
-        a.coord = q.sorted ? inst->d_rcoord : inst->d_coord;
-        a.gid = q.sorted ? inst->d_sperm : nullptr;
-        a.iid = q.sorted ? inst->d_sinv : nullptr;
-        a.nid = q.nid;
-        a.stage_pairs = q.stage_pairs;
-    };
-    set_plan(p);
+    cl_set_plan(a, inst, p);
     a.orders = t->d_order; a.states = t->d_state;
     a.gbox = inst->d_gbox;
     a.pairtab = t->d_cl_pairtab;
     a.slots = t->d_cl_slots;
-    {
-        const int want = TSP_SW(inst, CLUSTER_COPIES, 0);   // 0: by cluster size
-        a.copies = want > 0 ? std::min(want, kClCopies) : (C >= 128 ? kClCopies : 1);
-    }
+    const int want = TSP_SW(inst, CLUSTER_COPIES, 0);   // 0: by cluster size
+    a.copies = want > 0 ? std::min(want, kClCopies) : (C >= 128 ? kClCopies : 1);
     a.poss = t->d_pos;
     if (!t->d_cl_stats) {
         TSP_HIP_TRY(hipMalloc(&t->d_cl_stats, sizeof(long long) * (size_t)B * 256 * 4));
@@ -2102,17 +2005,18 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
     a.err = reinterpret_cast<int *>(t->d_cl_slots + (t->cl_slot_words - 2));
     a.n = n; a.ng = inst->ng; a.ntests = t->cl_ntests; a.C = C;
     a.xcd_local = (B > 1 && C <= 32 && (B * C) % (8 * C) == 0 && TSP_SW(inst, CLUSTER_XCD_LOCAL, 1)) ? 1 : 0;
-    a.tabu = nullptr; a.tabu_list = nullptr; a.tabu_list_n = nullptr; a.tabu_list_cap = 0; a.iter = iter; a.tenure = tenure; a.tabu_side = nullptr;
-    if (tabu) {   // the caller has brought the handle's list up to date (tsp_tabu_list_prepare) and zeroed the side words
+    a.tabu = nullptr; a.tabu_list = nullptr; a.tabu_list_n = nullptr; a.tabu_list_cap = 0; a.tabu_side = nullptr;
+    a.iter = tabu ? ride->iter : 0; a.tenure = tabu ? ride->tenure : 0;
+    if (tabu) {
         if (mode != TSP_2OPT_BEST || !p.sorted || B != 1 || !tabu->list_valid) return TSP_DEV_E_ARG;
         a.tabu = tabu->d_stamp; a.tabu_list = tabu->d_list; a.tabu_list_n = tabu->d_list_n; a.tabu_list_cap = tabu->list_cap;
         a.tabu_side = tabu->d_tabu_pairs;
     }
     a.chain = nullptr; a.chain_par = nullptr; a.chain_n = 0; a.snap = nullptr; a.chain_pairs = 0; a.chain_ab = nullptr; a.chain_pp = nullptr;
-    if (tabu && t->cl_ik_n > 0) {   // iterations of tabu() inside the launch (tsp_grid_tabu_iterations has filled the words)
+    if (tabu && ride->ik_n > 0) {   // iterations of tabu() inside the launch (tsp_grid_tabu_iterations has filled the words)
         if (!t->d_chain || !t->d_order_snap || max_steps >= 0) return TSP_DEV_E_ARG;
-        a.chain = t->d_chain; a.chain_par = t->d_chain + t->cl_ik_par; a.chain_n = t->cl_ik_n; a.snap = t->d_order_snap;
-        a.chain_pairs = t->cl_ik_pairs; a.chain_ab = t->d_chain + t->cl_ik_ab; a.chain_pp = t->d_chain + t->cl_ik_pp;
+        a.chain = t->d_chain; a.chain_par = t->d_chain + kChainPar; a.chain_n = ride->ik_n; a.snap = t->d_order_snap;
+        a.chain_pairs = ride->ik_pairs; a.chain_ab = t->d_chain + kChainAb; a.chain_pp = t->d_chain + kChainPp;
     }
     a.probe = TSP_SW(inst, CLUSTER_PROBE, 4096);
     a.fs_rows = fs_rows;
@@ -2134,6 +2038,83 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
         a.rbs = C / nb;
     }
     a.rmax = std::max(a.rmin, std::min(2048, TSP_SW(inst, CLUSTER_MAX_ROWS, C == 1 ? kClRows : std::max(kClRows, 8 * C))));
+    return TSP_OK;
+}
+
+// Hands the next launch its exchange epochs (a.epoch0 on).  They run on from launch to launch (a tag of an earlier launch never
+// equals a later epoch), so the area is zeroed only when it is new, after a failed launch, and here: before the 32-bit epoch
+// would wrap.
+int cl_take_epochs(tsp_dev_tours *t, ClusterArgs &a) {
+    const unsigned epochs = (unsigned)a.max_iters + (unsigned)a.chain_n;   // (a chain of iterations: one more exchange per kick)
+    if ((unsigned long long)t->cl_epoch + epochs + 6ull >= 0xffffffffull) {
+        TSP_HIP_TRY(hipMemsetAsync(t->d_cl_slots, 0, sizeof(unsigned long long) * t->cl_slot_words, t->inst->ctx->stream));
+        t->cl_epoch = 0;
+    }
+    a.epoch0 = t->cl_epoch;
+    t->cl_epoch += (epochs + 5u) & ~1u;   // even: the parity of an epoch picks the half of the area (+1: the arrival rendezvous)
+    return TSP_OK;
+}
+
+// The exchange gave up (the poll found the error word set): what has to be put back and remembered.
+void cl_gave_up(tsp_dev_tours *t, tsp_dev_tabu *tabu, int launches_done) {
+    hipStream_t s = t->inst->ctx->stream;
+    (void)hipMemsetAsync(t->d_cl_slots, 0, sizeof(unsigned long long) * t->cl_slot_words, s);   // the error word too
+    t->cl_epoch = 0;
+    {   // remember it: the next AUTO decisions on this device leave the CLUSTER engine out (64 calls, doubling up to 4096
+        // with every further give-up), so that a driver making thousands of calls on a shared device stalls once
+        tsp_dev_ctx *cx = t->inst->ctx;
+        cx->cl_giveups += 1;
+        cx->cl_backoff = std::min(4096, std::max(64, 2 * cx->cl_backoff));
+        cx->cl_skip = cx->cl_backoff;
+    }
+    if (tabu) {
+        // the failed launch may have consumed or added to the side words of the tabu-list accounting: back to what
+        // they were after the last launch that completed (zero before the first)
+        if (launches_done > 0) (void)hipMemcpyAsync(tabu->d_tabu_pairs, tabu->d_tabu_pairs + kTabuSideWords, kTabuSideWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s);
+        else (void)hipMemsetAsync(tabu->d_tabu_pairs, 0, kTabuSideWords * sizeof(unsigned long long), s);
+    }
+    tsp::set_last_error("k_cluster_two_opt: a workgroup of the cluster was not resident (exchange gave up)",
+                        hipErrorLaunchFailure, __FILE__, __LINE__);
+}
+
+}  // namespace
+
+// Runs the tours of `t` to their local optima with C workgroups per tour.  Returns TSP_DEV_E_HIP with
+// *fell_through = 1 when the cluster protocol gave up (a workgroup was not resident): the tours in HBM are
+// then exactly as uploaded by the last launch that completed and the caller may continue with another engine.
+// max_steps >= 0 caps the steps per tour (a capped best-improvement run gets its recomputed cost like a timed-out one).
+// ride: the tabu list the descent runs with and the follow-ups of a tabu() driver (tsp::TabuRide), or nullptr.
+int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double time_limit_s, int *all_done, int *fell_through,
+                    TabuRide *ride) {
+    if (fell_through) *fell_through = 0;
+    if (all_done) *all_done = 0;
+    if (!t || C < 1 || C > 256) return TSP_DEV_E_ARG;
+    tsp_dev_tabu *tabu = ride && ride->iter >= 0 && ride->tenure >= 0 ? ride->tabu : nullptr;   // (check_tenure answers 0 before it reads anything, tabusearch.c:84)
+    const ClPlan p = cl_plan(t, mode, tabu != nullptr);
+    if (!p.ok) return TSP_DEV_E_ARG;
+    tsp_dev_inst *inst = t->inst;
+    hipStream_t s = inst->ctx->stream;
+    const int B = t->B;
+    // all workgroups must be resident (TSP_CLUSTER_ALLOW_OVERSUB=1 lifts the check: the tests use it to drive the give-up path)
+    if (C > 1 && (long long)B * C > std::max(1, inst->ctx->num_cus) && !TSP_SW(inst, CLUSTER_ALLOW_OVERSUB, 0)) return TSP_DEV_E_ARG;
+
+    // First improvement of a single tour: two variants of the kernel hand the descent to each other between launches -- the plain
+    // replica (probe + tiles at full speed) while hits come close together, the replica in rank order with the box-pruned step
+    // once the running mean of the rows between hits (TourState::hit_rows, kept by both) passes fs_rows, back below fs_rows / 4.
+    ClPlan pf;   // the rank-order variant's plan
+    bool fs_avail = false;
+    const int fs_rows = std::max(0, TSP_SW(inst, CLUSTER_FS_ROWS, 120));   // 80 .. 200 measure alike (rand10000: alg_2opt 20.7 ms, VNS round 3.4 ms)
+    if (mode == TSP_2OPT_FIRST && B == 1 && fs_rows > 0 && max_steps < 0) {
+        pf = cl_plan(t, mode, false, /*want_fs=*/true);
+        const long long npairs = (long long)inst->ng * (inst->ng + 1) / 2;
+        fs_avail = pf.ok && pf.sorted && C <= (npairs + 3) / 4;
+    }
+    int rc = (p.sorted || fs_avail) ? cl_instance_tables(inst) : TSP_OK;
+    if (!rc) rc = cl_exchange_area(t, C);
+    if (!rc && (p.sorted || fs_avail)) rc = cl_pair_table(t, C);
+    ClusterArgs a;
+    if (!rc) rc = cl_args(t, mode, C, p, fs_avail, fs_rows, max_steps, tabu, ride, a);
+    if (rc) return rc;
     // steps per launch: a time limit is honoured between launches (the reference checks it per sweep / per pair), so a
     // limited run is cut into launches of a millisecond or two (a relaunch reloads the replicas: ~0.1 ms)
     const int launch_iters = time_limit_s > 0 ? (mode == TSP_2OPT_FIRST ? 256 : 128) : (mode == TSP_2OPT_FIRST ? 16384 : 4096);
@@ -2147,7 +2128,7 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
         if (fs_avail) {   // t->h_state: as the last launch (or the upload) left it
             const int hr = t->h_state[0].hit_rows;
             on_fs = on_fs ? hr >= a.fs_leave : hr >= a.fs_exit;
-            set_plan(on_fs ? pf : p);
+            cl_set_plan(a, inst, on_fs ? pf : p);
             // inside the rank-order variant a tiles step reads through the id maps (+1.8 us at n = 10 000) and covers ~400 rows
             // per round of tiles: the box-pruned step takes over from half the switching distance on
             a.fs_rows = on_fs ? std::max(1, fs_rows / 2) : fs_rows;
@@ -2158,40 +2139,27 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
             a.max_iters = (int)std::min<int64_t>(launch_iters, max_steps - queued);
         }
         queued += a.max_iters;
-        // exchange epochs run on from launch to launch (a tag of an earlier launch never equals a later epoch), so the area is
-        // zeroed only when it is new, after a failed launch, and before the 32-bit epoch would wrap
-        const unsigned epochs = (unsigned)a.max_iters + (unsigned)a.chain_n;   // (a chain of iterations: one more exchange per kick)
-        if ((unsigned long long)t->cl_epoch + epochs + 6ull >= 0xffffffffull) {
-            TSP_HIP_TRY(hipMemsetAsync(t->d_cl_slots, 0, sizeof(unsigned long long) * t->cl_slot_words, s));
-            t->cl_epoch = 0;
-        }
-        a.epoch0 = t->cl_epoch;
-        t->cl_epoch += (epochs + 5u) & ~1u;   // even: the parity of an epoch picks the half of the area (+1: the arrival rendezvous)
+        rc = cl_take_epochs(t, a);
+        if (rc) return rc;
         hipError_t e = hipSuccess;
         TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, { e = cl_launch<WTC, INTC>(t, mode, on_fs ? pf : p, a); });
-        if (e == hipSuccess && launches_done == 0 && t->cl_post) {   // a driver's follow-up, decided on the device (see tsp_dev_tours::cl_post)
-            t->cl_post(t->cl_post_ctx, s, a.err);
-            t->cl_post = nullptr; t->cl_post_ran = true;
-            // the driver's next iterations, queued behind this one without a wait (tsp_dev_tours::cl_chain): the same kernel on
-            // the tour the follow-up leaves, with the epochs running on; a stop word on the device turns the launches that
-            // follow a failed iteration into no-ops (their re-arm is vetoed, the control block says `done`)
-            t->cl_chain_launched = 1;
-            if (t->cl_chain && max_steps < 0 && !fs_avail) {
-                for (int k = 1; e == hipSuccess && t->cl_chain(t->cl_post_ctx, s, k, &a.iter, &a.tenure); ++k) {
-                    if ((unsigned long long)t->cl_epoch + (unsigned)a.max_iters + 6ull >= 0xffffffffull) {
-                        TSP_HIP_TRY(hipMemsetAsync(t->d_cl_slots, 0, sizeof(unsigned long long) * t->cl_slot_words, s));
-                        t->cl_epoch = 0;
-                    }
-                    a.epoch0 = t->cl_epoch;
-                    t->cl_epoch += ((unsigned)a.max_iters + 5u) & ~1u;
-                    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, { e = cl_launch<WTC, INTC>(t, mode, p, a); });
-                    if (e != hipSuccess) break;
-                    if (t->cl_post_k) t->cl_post_k(t->cl_post_ctx, s, k, a.err);
-                    t->cl_chain_launched = k + 1;
-                }
-                if (e != hipSuccess) { (void)hipGetLastError(); e = hipSuccess; }   // the chain simply ends here: the iterations queued so far stand
+        if (e == hipSuccess && launches_done == 0 && ride && ride->follow != TabuRide::kNone) {
+            // The driver's follow-up of this launch, decided on the device -- and, for a queued chain, its next iterations behind
+            // it without a wait: the same kernel on the tour the follow-up leaves, with the epochs running on; a stop word on the
+            // device turns the launches that follow a failed iteration into no-ops (their re-arm is vetoed, the control block
+            // says `done`).
+            const int chain = ride->follow == TabuRide::kChain && max_steps < 0 && !fs_avail ? ride->count : 1;
+            ride->follow_ran = true;
+            for (int k = 0;;) {
+                tsp_grid_tabu_follow(t, *ride, k, a.err);
+                ride->launched = ++k;
+                if (k >= chain) break;
+                a.iter = ride->iter + k; a.tenure = ride->tenures[k];   // (the re-arm was the follow-up's last act, unless it stopped the chain)
+                rc = cl_take_epochs(t, a);
+                if (rc) return rc;
+                TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, { e = cl_launch<WTC, INTC>(t, mode, p, a); });
+                if (e != hipSuccess) { (void)hipGetLastError(); e = hipSuccess; break; }   // the chain simply ends here: the iterations queued so far stand
             }
-            t->cl_chain = nullptr; t->cl_post_k = nullptr;
         }
         if (e != hipSuccess) {
             // the attribute or the launch was refused (an LDS size this device does not grant): nothing ran, the tours in
@@ -2205,25 +2173,8 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
         if (!t->h_cl_err) TSP_HIP_TRY(hipHostMalloc(&t->h_cl_err, sizeof(int)));
         TSP_HIP_TRY(hipMemcpyAsync(t->h_cl_err, a.err, sizeof(int), hipMemcpyDeviceToHost, s));   // pinned: no staging copy
         TSP_HIP_TRY(hipStreamSynchronize(s));
-        const int err = *t->h_cl_err;
-        if (err) {
-            (void)hipMemsetAsync(t->d_cl_slots, 0, sizeof(unsigned long long) * t->cl_slot_words, s);   // the error word too
-            t->cl_epoch = 0;
-            {   // remember it: the next AUTO decisions on this device leave the CLUSTER engine out (64 calls, doubling up to 4096
-                // with every further give-up), so that a driver making thousands of calls on a shared device stalls once
-                tsp_dev_ctx *cx = inst->ctx;
-                cx->cl_giveups += 1;
-                cx->cl_backoff = std::min(4096, std::max(64, 2 * cx->cl_backoff));
-                cx->cl_skip = cx->cl_backoff;
-            }
-            if (tabu) {
-                // the failed launch may have consumed or added to the side words of the tabu-list accounting: back to what
-                // they were after the last launch that completed (zero before the first)
-                if (launches_done > 0) (void)hipMemcpyAsync(tabu->d_tabu_pairs, tabu->d_tabu_pairs + kTabuSideWords, kTabuSideWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s);
-                else (void)hipMemsetAsync(tabu->d_tabu_pairs, 0, kTabuSideWords * sizeof(unsigned long long), s);
-            }
-            tsp::set_last_error("k_cluster_two_opt: a workgroup of the cluster was not resident (exchange gave up)",
-                                hipErrorLaunchFailure, __FILE__, __LINE__);
+        if (*t->h_cl_err) {
+            cl_gave_up(t, tabu, launches_done);
             if (fell_through) *fell_through = 1;
             return TSP_DEV_E_HIP;
         }
@@ -2233,12 +2184,12 @@ int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double
         for (int b = 0; b < B; ++b) done = done && t->h_state[b].done;
         if (done) { if (all_done) *all_done = 1; break; }
         if (time_limit_s > 0 && wall_s() - t0 > time_limit_s) { status = TSP_TIME_LIMIT_EXCEEDED; break; }
-        // another launch follows: keep the tabu-list side words as they stand after this one (see the give-up path)
+        // another launch follows: keep the tabu-list side words as they stand after this one (see cl_gave_up)
         if (tabu) TSP_HIP_TRY(hipMemcpyAsync(tabu->d_tabu_pairs + kTabuSideWords, tabu->d_tabu_pairs, kTabuSideWords * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
     }
     bool unfinished = status == TSP_TIME_LIMIT_EXCEEDED;
     for (int b = 0; b < B; ++b) unfinished = unfinished || !t->h_state[b].done;
-    const int rc = tsp_grid_after_external_run(t, mode, unfinished, /*pos_written=*/true);
+    rc = tsp_grid_after_external_run(t, mode, unfinished, /*pos_written=*/true);
     t->h_state_fresh = rc == 0 && !(unfinished && mode == TSP_2OPT_BEST);   // (a cut-short best-improvement run has its cost recomputed after the poll)
     return rc ? rc : status;
 }

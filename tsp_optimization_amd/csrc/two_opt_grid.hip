@@ -27,6 +27,8 @@
 // The pair (i,j) always denotes removing (i,succ i) and (j,succ j) and reversing the FORWARD path
 // succ(i)..j (src/utility.c:708-717): that path is the cyclic position range pos[i]+1 .. pos[j],
 // so reversing exactly that range keeps succ() identical to the reference's after every move.
+#include "cluster_deal.hpp"
+#include "tabu_chain.hpp"
 #include "two_opt_exh.hpp"
 #include "two_opt_first.hpp"
 #include "two_opt_step.hpp"
@@ -145,11 +147,11 @@ __global__ __launch_bounds__(kApplyThreads) void k_tabu_post(const TourState *st
 }
 
 // ---- K iterations of tabu() per wait for the device ------------------------------------------------------------------------
-// The same tail for launch k of a chain of iterations queued without a wait in between (tsp_dev_tours::cl_chain).  chain[0] is
+// The same tail for launch k of a chain of iterations queued without a wait in between (tsp::TabuRide::kChain).  chain[kChainStop] is
 // the stop word: once an iteration could not be completed on the device -- its descent did not finish in its launch, the
 // exchange gave up, or the kick's trial was rejected (the host must draw again) -- every later launch of the chain is a no-op:
-// nobody re-arms the control block, which says `done`.  The incumbent's cost lives in chain[2..3] (double).
-// res = {accepted, a1, b1, 0, ran, improved, why-not (1 descent unfinished / give-up), 0, cost (double)}.
+// nobody re-arms the control block, which says `done`.  The incumbent's cost lives at chain[kChainBest] (double).
+// res = the iteration's result words (tabu_chain.hpp): {accepted, a1, b1, 0, ran, improved, why-not, 0, cost (double)}.
 // The kernel also does what k_tabu_fix_evals does after a run (the skipped pairs come off the evaluation count, the side words
 // go back to zero) and, when the iteration is complete and another one follows, the re-arm for it (k_rearm's stores): one
 // launch between two CLUSTER launches instead of three.
@@ -159,11 +161,11 @@ __global__ __launch_bounds__(kApplyThreads) void k_tabu_post_chain(TourState *st
                                                                    int rearm_chunk /* > 0: another iteration follows */) {
     __shared__ int s_go, s_better;
     const int tid = threadIdx.x;
-    int *res = chain + 4 + 10 * k;
+    int *res = chain + kChainRes + kChainResWords * k;
     if (tid == 0) {
-        double *best = reinterpret_cast<double *>(chain + 2);
+        double *best = reinterpret_cast<double *>(chain + kChainBest);
         int go = 0, better = 0, why = 0;
-        if (!chain[0]) {
+        if (!chain[kChainStop]) {
             {   // k_tabu_fix_evals: read-and-zero as returning atomics (see there)
                 long long skipped = (long long)atomicExch(side, 0ull);
                 for (int p = 1; p <= kTabuSideSlots; ++p) {
@@ -173,12 +175,12 @@ __global__ __launch_bounds__(kApplyThreads) void k_tabu_post_chain(TourState *st
                 state->evals -= skipped;
             }
             go = state->done && !(err && *err);
-            if (!go) { why = 1; chain[0] = 1; state->done = 1; }   // the host finishes this iteration its own way
+            if (!go) { why = 1; chain[kChainStop] = 1; state->done = 1; }   // the host finishes this iteration its own way
             else if (state->obj < *best) { better = 1; *best = state->obj; }
         }
         s_go = go; s_better = better;
-        res[0] = 0; res[1] = 0; res[2] = 0; res[3] = 0; res[4] = go; res[5] = better; res[6] = why; res[7] = 0;
-        *reinterpret_cast<double *>(res + 8) = go ? state->obj : 0.0;
+        res[kResAccepted] = 0; res[kResA1] = 0; res[kResB1] = 0; res[kResTrials] = 0; res[kResRan] = go; res[kResImproved] = better; res[kResWhy] = why; res[7] = 0;
+        *reinterpret_cast<double *>(res + kResCost) = go ? state->obj : 0.0;
     }
     __syncthreads();
     if (!s_go) return;
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(kApplyThreads) void k_tabu_post_chain(TourState *st
     }
     tabu_kick_body(order, pos, stamp, n, a, b, iter, tenure, res, list, list_n, list_cap);
     if (tid == 0) {
-        if (!res[0]) chain[0] = 1;   // rejected: the host draws the next trial (tabusearch.c:262-287); done stays set
+        if (!res[kResAccepted]) chain[kChainStop] = 1;   // rejected: the host draws the next trial (tabusearch.c:262-287); done stays set
         else if (rearm_chunk > 0) {  // the next iteration's alg_2opt_tabu starts on the kicked tour (k_rearm)
             state->ci = 0; state->cj = 0; state->chunk_rows = rearm_chunk; state->done = 0;
             state->seen_cost = state->obj;
@@ -524,19 +526,32 @@ int tsp_grid_after_external_run(tsp_dev_tours *t, int mode, int timed_out, bool 
     return TSP_OK;
 }
 
-// two_opt_cluster.hip
-int tsp_cluster_run(tsp_dev_tours *t, int mode, int C, int64_t max_steps, double time_limit_s, int *all_done, int *fell_through,
-                    tsp_dev_tabu *tabu, int iter, int tenure);
-bool tsp_cluster_fits(const tsp_dev_tours *t, int mode);
-bool tsp_cluster_sorted(const tsp_dev_tours *t, int mode);
-int tsp_cluster_size(const tsp_dev_tours *t, int mode);
+// Queues, behind launch k of a CLUSTER run, the follow-up its driver asked for (tsp::TabuRide::follow; called by tsp_cluster_run).
+void tsp_grid_tabu_follow(tsp_dev_tours *t, const TabuRide &r, int k, const int *d_err) {
+    hipStream_t s = t->inst->ctx->stream;
+    tsp_dev_tabu *tabu = r.tabu;
+    if (r.follow == TabuRide::kPost) {
+        hipLaunchKernelGGL(k_tabu_post, dim3(1), dim3(kApplyThreads), 0, s, t->d_state, d_err, t->d_order, t->d_pos, tabu->d_stamp, t->n,
+                           r.a, r.b, r.iter, r.tenure, t->d_kick_result, tabu->list_valid ? tabu->d_list : nullptr, tabu->d_list_n,
+                           tabu->list_cap, r.best, t->d_order_snap);
+        (void)hipMemcpyAsync(t->h_kick_result, t->d_kick_result, 8 * sizeof(int), hipMemcpyDeviceToHost, s);
+        return;
+    }
+    // ONE launch between two CLUSTER launches: evaluation count, incumbent, kick, re-arm
+    const int chunk = k + 1 < r.count ? std::min(t->first_min_rows, std::max(1, t->n - 1)) : 0;
+    hipLaunchKernelGGL(k_tabu_post_chain, dim3(1), dim3(kApplyThreads), 0, s, t->d_state, d_err, t->d_order, t->d_pos, tabu->d_stamp,
+                       t->n, r.ab[2 * k], r.ab[2 * k + 1], r.iter + k, r.tenures[k], t->d_chain, k, tabu->d_list, tabu->d_list_n,
+                       tabu->list_cap, t->d_order_snap, tabu->d_tabu_pairs, chunk);
+}
 
 // alg_2opt_tabu with a list on tour 0 of a handle: the CLUSTER engine when the tour fits its sorted scan and the handle's
 // list of non-zero stamps is usable (one launch per descent, 11 us per sweep at n = 10 000), else the GRID engine (which
 // works from the list as well when it can, and reads four stamps per pair when it cannot).  sync as tsp_grid_run.
-int tsp_tabu_run(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int tenure, double time_limit_s, int sync, int *all_done) {
-    struct PlanGuard { tsp_dev_tours *t; ~PlanGuard() { t->cl_tabu_plan = false; } } plan_guard{t};
-    t->cl_tabu_plan = tabu && iter >= 0 && tenure >= 0;   // the cluster's sorted scan at any size (see cl_plan)
+// ride: the list, iter, tenure and a driver's follow-ups (tsp::TabuRide); nullptr = no list.
+int tsp_tabu_run(tsp_dev_tours *t, TabuRide *ride, double time_limit_s, int sync, int *all_done) {
+    tsp_dev_tabu *tabu = ride ? ride->tabu : nullptr;
+    const int iter = ride ? ride->iter : 0, tenure = ride ? ride->tenure : 0;
+    const bool listed = tabu && iter >= 0 && tenure >= 0;   // the cluster's sorted scan at any size (see cl_plan)
     // after a give-up (a workgroup was not resident) the CLUSTER engine is left out for a while: tsp_dev_ctx::cl_skip
     auto cluster_allowed = [&]() {
         tsp_dev_ctx *cx = t->inst->ctx;
@@ -544,8 +559,8 @@ int tsp_tabu_run(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int tenure, dou
         --cx->cl_skip;
         return false;
     };
-    if (tabu && iter >= 0 && tenure >= 0 && t->B == 1 && TSP_SW(t->inst, TABU_DENSE, 0) == 0 && TSP_SW(t->inst, ENGINE, 0) != 1 &&
-        tsp_cluster_fits(t, TSP_2OPT_BEST) && tsp_cluster_sorted(t, TSP_2OPT_BEST) && cluster_allowed()) {
+    if (listed && t->B == 1 && TSP_SW(t->inst, TABU_DENSE, 0) == 0 && TSP_SW(t->inst, ENGINE, 0) != 1 &&
+        tsp_cluster_fits(t, TSP_2OPT_BEST, true) && tsp_cluster_sorted(t, TSP_2OPT_BEST, true) && cluster_allowed()) {
         bool usable = false;
         int rc = tabu_list_prepare(t, tabu, &usable);
         if (rc) return rc;
@@ -553,33 +568,28 @@ int tsp_tabu_run(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int tenure, dou
             hipStream_t s = t->inst->ctx->stream;
             TSP_HIP_TRY(hipMemsetAsync(tabu->d_tabu_pairs, 0, kTabuSideWords * sizeof(unsigned long long), s));
             int fell = 0;
-            const int status = tsp_cluster_run(t, TSP_2OPT_BEST, tsp_cluster_size(t, TSP_2OPT_BEST), -1, time_limit_s, all_done, &fell,
-                                               tabu, iter, tenure);
-            t->cl_tabu_plan = false;
+            const int status = tsp_cluster_run(t, TSP_2OPT_BEST, tsp_cluster_size(t, TSP_2OPT_BEST, true), -1, time_limit_s, all_done, &fell, ride);
+            if (!fell && status < 0) return status;
+            // the skipped pairs come off the evaluation count (after a give-up: those of the launches that completed)
+            hipLaunchKernelGGL(k_tabu_fix_evals, dim3(1), dim3(64), 0, s, t->d_state, tabu->d_tabu_pairs);
+            TSP_HIP_TRY(hipGetLastError());
             if (!fell) {
-                if (status < 0) return status;
                 tabu->last_run_list = true;
-                hipLaunchKernelGGL(k_tabu_fix_evals, dim3(1), dim3(64), 0, s, t->d_state, tabu->d_tabu_pairs);
-                TSP_HIP_TRY(hipGetLastError());
                 if (sync == 1) TSP_HIP_TRY(hipStreamSynchronize(s));
                 return status;
             }
             // A workgroup was not resident.  The tour and the control block in HBM are as the last launch that COMPLETED left
             // them (a run of more than 4096 sweeps, or a time-limited one, is several launches), the side words of the list
             // accounting have been put back to that point too (tsp_cluster_run), and stamps the failed launch cleared stay
-            // cleared (expired either way: the same decisions, the same clears are due again).  The skipped pairs of the
-            // completed launches come off the evaluation count now -- tsp_grid_run starts its own count at zero -- and the
-            // rest of the descent goes through the GRID engine.
-            hipLaunchKernelGGL(k_tabu_fix_evals, dim3(1), dim3(64), 0, s, t->d_state, tabu->d_tabu_pairs);
-            TSP_HIP_TRY(hipGetLastError());
+            // cleared (expired either way: the same decisions, the same clears are due again).  tsp_grid_run starts its own
+            // count of skipped pairs at zero, and the rest of the descent goes through the GRID engine.
         }
     }
-    if ((!tabu || iter < 0 || tenure < 0) && t->B == 1 && TSP_SW(t->inst, ENGINE, 0) != 1 && tsp_cluster_fits(t, TSP_2OPT_BEST) && cluster_allowed()) {
+    if (!listed && t->B == 1 && TSP_SW(t->inst, ENGINE, 0) != 1 && tsp_cluster_fits(t, TSP_2OPT_BEST) && cluster_allowed()) {
         // no list (check_tenure answers 0 before it reads anything, tabusearch.c:84): the plain best-improvement descent
         hipStream_t s = t->inst->ctx->stream;
         int fell = 0;
-        const int status = tsp_cluster_run(t, TSP_2OPT_BEST, tsp_cluster_size(t, TSP_2OPT_BEST), -1, time_limit_s, all_done, &fell,
-                                           nullptr, 0, 0);
+        const int status = tsp_cluster_run(t, TSP_2OPT_BEST, tsp_cluster_size(t, TSP_2OPT_BEST), -1, time_limit_s, all_done, &fell, ride);
         if (!fell) {
             if (status >= 0 && sync == 1) TSP_HIP_TRY(hipStreamSynchronize(s));
             return status;
@@ -587,7 +597,6 @@ int tsp_tabu_run(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int tenure, dou
     }
     return tsp_grid_run(t, TSP_2OPT_BEST, tabu, iter, tenure, -1, time_limit_s, sync, all_done);
 }
-int tsp_perm_cost_device(tsp_dev_inst *inst, const int *d_perm, long long stride, int B, double *d_out, size_t out_stride_bytes);   // api.hip
 
 // ---- resident-tour drivers (called by the extern "C" wrappers in api.hip) ---------------------------------------
 int tsp_grid_rearm(tsp_dev_tours *t, int mode) {
@@ -607,6 +616,13 @@ static int kick_buffers(tsp_dev_tours *t) {
     return TSP_OK;
 }
 
+// An accepted kick appended (at most) two entries to the handle's list of non-zero stamps.
+static void kick_appended(tsp_dev_tabu *tabu, int accepted) {
+    if (!accepted || !tabu->list_valid) return;
+    tabu->list_ub += 2;
+    if (tabu->list_ub > tabu->list_cap) tabu->list_valid = false;   // entries may have been dropped: scan before the next use
+}
+
 int tsp_grid_tabu_kick(tsp_dev_tours *t, tsp_dev_tabu *tabu, int a, int b, int iter, int tenure, int *accepted) {
     if (!t || !tabu || t->B != 1 || a < 0 || b < 0 || a >= t->n || b >= t->n) return TSP_DEV_E_ARG;
     int rc = kick_buffers(t);
@@ -617,10 +633,7 @@ int tsp_grid_tabu_kick(tsp_dev_tours *t, tsp_dev_tabu *tabu, int a, int b, int i
     TSP_HIP_TRY(hipMemcpyAsync(t->h_kick_result, t->d_kick_result, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     TSP_HIP_TRY(hipStreamSynchronize(s));
     TSP_HIP_TRY(hipGetLastError());
-    if (t->h_kick_result[0] && tabu->list_valid) {
-        tabu->list_ub += 2;
-        if (tabu->list_ub > tabu->list_cap) tabu->list_valid = false;   // entries may have been dropped: scan before the next use
-    }
+    kick_appended(tabu, t->h_kick_result[0]);
     if (accepted) *accepted = t->h_kick_result[0];
     return TSP_OK;
 }
@@ -667,6 +680,22 @@ int tsp_grid_snapshot(tsp_dev_tours *t, bool restore) {
     return TSP_OK;
 }
 
+// The run was cut short (time limit; tabusearch.c:255-258: no kick): its recomputed cost was written after the last poll, so the
+// control block of tour 0 is fetched; with best_obj (a tabu() driver) the incumbent is updated before the status is looked at
+// (:241-249, :255): cost, improved, snapshot.
+static int cut_short(tsp_dev_tours *t, double *best_obj, double *obj, int *improved) {
+    hipStream_t s = t->inst->ctx->stream;
+    TSP_HIP_TRY(hipMemcpyAsync(t->h_state, t->d_state, sizeof(TourState), hipMemcpyDeviceToHost, s));
+    TSP_HIP_TRY(hipStreamSynchronize(s));
+    const double c = t->h_state[0].obj;
+    if (obj) *obj = c;
+    if (improved) *improved = 0;
+    if (!best_obj || !(c < *best_obj)) return TSP_OK;
+    *best_obj = c;
+    if (improved) *improved = 1;
+    return tsp_grid_snapshot(t, false);
+}
+
 // One iteration of tabu() (src/tabusearch.c:238-309) with two waits for the device instead of five: alg_2opt_tabu on the
 // resident tour; the poll that finds it finished also brings its cost (:168-172), so the host decides about the incumbent
 // (:241-249) and queues, behind the run's last launches, the device-to-device snapshot and the first trial of the kick with
@@ -682,26 +711,16 @@ int tsp_grid_tabu_iteration(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int 
     // The CLUSTER engine finishes the descent in one launch (almost always): the incumbent's update and the kick are queued
     // behind that launch and decided on the device, and the iteration is ONE wait for the device.  Anything else (another
     // engine, a second launch, a give-up, the time limit) leaves result[4] = 0 and takes the two waits below.
-    struct Post { tsp_dev_tours *t; tsp_dev_tabu *tabu; int a, b, iter, tenure; double best; } post{t, tabu, a, b, iter, tenure, *best_obj};
     const size_t bn = (size_t)t->n;
     if (!t->d_order_snap) TSP_HIP_TRY(hipMalloc(&t->d_order_snap, bn * sizeof(int)));
     t->h_kick_result[4] = 0;
-    t->cl_post_ctx = &post; t->cl_post_ran = false;
-    t->cl_post = [](void *ctx, hipStream_t st, const int *d_err) {
-        Post *q = static_cast<Post *>(ctx);
-        tsp_dev_tours *tt = q->t;
-        hipLaunchKernelGGL(k_tabu_post, dim3(1), dim3(kApplyThreads), 0, st, tt->d_state, d_err, tt->d_order, tt->d_pos, q->tabu->d_stamp, tt->n,
-                           q->a, q->b, q->iter, q->tenure, tt->d_kick_result, q->tabu->list_valid ? q->tabu->d_list : nullptr, q->tabu->d_list_n,
-                           q->tabu->list_cap, q->best, tt->d_order_snap);
-        (void)hipMemcpyAsync(tt->h_kick_result, tt->d_kick_result, 8 * sizeof(int), hipMemcpyDeviceToHost, st);
-    };
-    const int status = tsp_tabu_run(t, tabu, iter, tenure, time_limit_s, 2, &done);
-    const bool post_ran = t->cl_post_ran;
-    t->cl_post = nullptr; t->cl_post_ctx = nullptr; t->cl_post_ran = false;
+    TabuRide ride{tabu, iter, tenure};
+    ride.follow = TabuRide::kPost; ride.a = a; ride.b = b; ride.best = *best_obj;
+    const int status = tsp_tabu_run(t, &ride, time_limit_s, 2, &done);
     if (status < 0) return status;
     if (improved) *improved = 0;
     if (accepted) *accepted = 0;
-    if (post_ran && t->h_kick_result[4]) {   // the run's own wait has brought the result back
+    if (ride.follow_ran && t->h_kick_result[4]) {   // the run's own wait has brought the result back
         TSP_HIP_TRY(hipGetLastError());
         const double cost = t->h_state[0].obj;
         if (obj) *obj = cost;
@@ -710,47 +729,44 @@ int tsp_grid_tabu_iteration(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int 
             if (improved) *improved = 1;
             t->h_obj_snap.assign(1, cost);
         }
-        if (t->h_kick_result[0] && tabu->list_valid) {
-            tabu->list_ub += 2;
-            if (tabu->list_ub > tabu->list_cap) tabu->list_valid = false;
-        }
+        kick_appended(tabu, t->h_kick_result[0]);
         if (accepted) *accepted = t->h_kick_result[0];
         return status;
     }
     if (status != TSP_OK || !done) {   // time limit: the cost was recomputed by the run; no kick (tabusearch.c:255-258)
-        TSP_HIP_TRY(hipMemcpyAsync(t->h_state, t->d_state, sizeof(TourState), hipMemcpyDeviceToHost, s));
-        TSP_HIP_TRY(hipStreamSynchronize(s));
-        const double c = t->h_state[0].obj;
-        if (obj) *obj = c;
-        if (c < *best_obj) {   // the incumbent is updated before the status is looked at (:241-249, :255)
-            *best_obj = c;
-            if (improved) *improved = 1;
-            const int rc2 = tsp_grid_snapshot(t, false);
-            if (rc2) return rc2;
-        }
-        return status;
+        rc = cut_short(t, best_obj, obj, improved);
+        return rc ? rc : status;
     }
     const double cost = t->h_state[0].obj;   // the poll that saw `done` carried the recomputed cost
     if (obj) *obj = cost;
     if (cost < *best_obj) {
         *best_obj = cost;
         if (improved) *improved = 1;
-        const size_t bn = (size_t)t->n;
-        if (!t->d_order_snap) TSP_HIP_TRY(hipMalloc(&t->d_order_snap, bn * sizeof(int)));
         TSP_HIP_TRY(hipMemcpyAsync(t->d_order_snap, t->d_order, bn * sizeof(int), hipMemcpyDeviceToDevice, s));
         t->h_obj_snap.assign(1, cost);
     }
-    hipLaunchKernelGGL(k_tabu_kick, dim3(1), dim3(kApplyThreads), 0, s, t->d_order, t->d_pos, tabu->d_stamp, t->n, a, b, iter,
-                       tenure, t->d_kick_result, tabu->list_valid ? tabu->d_list : nullptr, tabu->d_list_n, tabu->list_cap);
-    TSP_HIP_TRY(hipMemcpyAsync(t->h_kick_result, t->d_kick_result, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    TSP_HIP_TRY(hipStreamSynchronize(s));
-    TSP_HIP_TRY(hipGetLastError());
-    if (t->h_kick_result[0] && tabu->list_valid) {
-        tabu->list_ub += 2;
-        if (tabu->list_ub > tabu->list_cap) tabu->list_valid = false;
+    rc = tsp_grid_tabu_kick(t, tabu, a, b, iter, tenure, accepted);
+    return rc ? rc : status;
+}
+
+// What the device left in the result words of a chain's iterations 0 .. limit - 1 (tabu_chain.hpp), up to the first that did
+// not run to its kick's trial; returns how many did.  in_kernel: the kick's trials were counted on the device, else one each.
+static int harvest_chain(tsp_dev_tours *t, tsp_dev_tabu *tabu, int limit, bool in_kernel, double *obj, int *improved, int *trials,
+                         int *last_accepted) {
+    int k = 0;
+    for (; k < limit; ++k) {
+        const int *res = t->h_chain + kChainRes + kChainResWords * k;
+        if (!res[kResRan]) break;
+        double c;
+        memcpy(&c, res + kResCost, sizeof c);
+        if (obj) obj[k] = c;
+        if (improved) improved[k] = res[kResImproved];
+        if (trials) trials[k] = in_kernel ? res[kResTrials] : 1;
+        if (res[kResImproved]) t->h_obj_snap.assign(1, c);
+        kick_appended(tabu, res[kResAccepted]);
+        if (last_accepted) *last_accepted = res[kResAccepted];
     }
-    if (accepted) *accepted = t->h_kick_result[0];
-    return status;
+    return k;
 }
 
 // `count` iterations of tabu() (src/tabusearch.c:238-309) in ONE wait for the device: the CLUSTER engine's launches of iterations
@@ -762,7 +778,6 @@ int tsp_grid_tabu_iteration(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int 
 // engine, a long list): nothing was touched.
 int tsp_grid_tabu_iterations(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter0, int count, const int *tenure, int pairs, const int *ab, double time_limit_s,
                              double *best_obj, double *obj, int *improved, int *trials, int *completed, int *last_accepted) {
-    constexpr int kMaxChain = 128, kMaxPairs = 256;
     if (!t || !tabu || t->B != 1 || tabu->inst != t->inst || !best_obj || !tenure || !ab || !completed || count < 1) return TSP_DEV_E_ARG;
     *completed = 0;
     if (last_accepted) *last_accepted = 0;
@@ -779,15 +794,10 @@ int tsp_grid_tabu_iterations(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter0, in
     if (iter0 < 0) return TSP_DEV_E_ARG;
     // the chain rides on the CLUSTER engine's tabu variant: the conditions of tsp_tabu_run's first branch, and room in the list
     // of non-zero stamps for the two entries every accepted kick appends (no scan, no compaction inside a chain)
-    if (TSP_SW(t->inst, TABU_DENSE, 0) != 0 || TSP_SW(t->inst, ENGINE, 0) == 1 || !tsp_cluster_fits(t, TSP_2OPT_BEST) ||
-        !tsp_cluster_sorted(t, TSP_2OPT_BEST))
+    if (TSP_SW(t->inst, TABU_DENSE, 0) != 0 || TSP_SW(t->inst, ENGINE, 0) == 1 || !tsp_cluster_fits(t, TSP_2OPT_BEST, true) ||
+        !tsp_cluster_sorted(t, TSP_2OPT_BEST, true))
         return TSP_OK;
-    {
-        tsp_dev_ctx *cx = t->inst->ctx;
-        if (TSP_SW(t->inst, ENGINE, 0) != 3 && cx->cl_skip > 0) return TSP_OK;   // after a give-up: the single-iteration path counts the back-off down
-    }
-    t->cl_tabu_plan = true;
-    struct PlanGuard { tsp_dev_tours *t; ~PlanGuard() { t->cl_tabu_plan = false; } } plan_guard{t};
+    if (TSP_SW(t->inst, ENGINE, 0) != 3 && t->inst->ctx->cl_skip > 0) return TSP_OK;   // after a give-up: the single-iteration path counts the back-off down
     bool usable = false;
     int rc = tabu_list_prepare(t, tabu, &usable, 2ll * count);   // (compacts now if the chain's entries would not fit before the next compaction)
     if (rc) return rc;
@@ -796,158 +806,82 @@ int tsp_grid_tabu_iterations(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter0, in
     rc = kick_buffers(t);
     if (rc) return rc;
     hipStream_t s = t->inst->ctx->stream;
-    // + in-kernel chains: the tenure per iteration, {a, b, a and b in rank order} per kick trial, the index of the next trial
-    const int par_at = 4 + 10 * kMaxChain, ab_at = par_at + kMaxChain, pp_at = ab_at + 4 * kMaxPairs;
-    const size_t chain_ints = (size_t)pp_at + 4;
     if (!t->d_chain) {
-        TSP_HIP_TRY(hipMalloc(&t->d_chain, chain_ints * sizeof(int)));
-        TSP_HIP_TRY(hipHostMalloc(&t->h_chain, chain_ints * sizeof(int)));
+        TSP_HIP_TRY(hipMalloc(&t->d_chain, kChainInts * sizeof(int)));
+        TSP_HIP_TRY(hipHostMalloc(&t->h_chain, kChainInts * sizeof(int)));
     }
     if (!t->d_order_snap) TSP_HIP_TRY(hipMalloc(&t->d_order_snap, (size_t)t->n * sizeof(int)));
-    memset(t->h_chain, 0, chain_ints * sizeof(int));
-    memcpy(t->h_chain + 2, best_obj, sizeof(double));
+    memset(t->h_chain, 0, kChainInts * sizeof(int));
+    memcpy(t->h_chain + kChainBest, best_obj, sizeof(double));
     const bool in_kernel = TSP_SW(t->inst, TABU_INKERNEL, 1) != 0;
     if (in_kernel) {
-        for (int k = 0; k < count; ++k) t->h_chain[par_at + k] = tenure[k];
+        for (int k = 0; k < count; ++k) t->h_chain[kChainPar + k] = tenure[k];
         for (int k = 0; k < npairs; ++k) {
-            int *q = t->h_chain + ab_at + 4 * k;
+            int *q = t->h_chain + kChainAb + 4 * k;
             q[0] = ab[2 * k]; q[1] = ab[2 * k + 1];
             q[2] = t->inst->h_sinv[(size_t)ab[2 * k]]; q[3] = t->inst->h_sinv[(size_t)ab[2 * k + 1]];   // the two nodes inside the rank-order replica
         }
     } else if (pairs > 0) return TSP_OK;   // (queued chains take one trial per iteration: the caller falls back)
-    TSP_HIP_TRY(hipMemcpyAsync(t->d_chain, t->h_chain, chain_ints * sizeof(int), hipMemcpyHostToDevice, s));
+    TSP_HIP_TRY(hipMemcpyAsync(t->d_chain, t->h_chain, kChainInts * sizeof(int), hipMemcpyHostToDevice, s));
     rc = tsp_grid_rearm(t, TSP_2OPT_BEST);
     if (rc) return rc;
     TSP_HIP_TRY(hipMemsetAsync(tabu->d_tabu_pairs, 0, kTabuSideWords * sizeof(unsigned long long), s));
+    // in_kernel: the iterations run INSIDE the CLUSTER launch (k_cluster_two_opt, TABU variant, chain_n > 0): between two descents
+    // the kernel itself keeps the incumbent, decides the kick's first trial and carries it out on the replicas -- what
+    // k_tabu_post_chain does between two launches of a queued chain, without the write-back, the replica load and the two
+    // kernel boundaries (28 + 4.6 + ~8 us of an iteration of ~140 at n = 10 000).  A launch that runs out of sweeps in the
+    // middle of an iteration writes its state back and the next launch goes on at chain[kChainResume].
+    TabuRide ride{tabu, iter0, tenure[0]};
+    if (in_kernel) { ride.ik_n = count; ride.ik_pairs = pairs; }
+    else { ride.follow = TabuRide::kChain; ride.count = count; ride.tenures = tenure; ride.ab = ab; }
+    int done = 0, fell = 0;
+    const int status = tsp_cluster_run(t, TSP_2OPT_BEST, tsp_cluster_size(t, TSP_2OPT_BEST, true), -1, time_limit_s, &done, &fell, &ride);
+    t->h_state_fresh = false;
     if (in_kernel) {
-        // The iterations run INSIDE the CLUSTER launch (k_cluster_two_opt, TABU variant, chain_n > 0): between two descents the
-        // kernel itself keeps the incumbent, decides the kick's first trial and carries it out on the replicas -- what
-        // k_tabu_post_chain does between two launches of a queued chain, without the write-back, the replica load and the two
-        // kernel boundaries (28 + 4.6 + ~8 us of an iteration of ~140 at n = 10 000).  A launch that runs out of sweeps in the
-        // middle of an iteration writes its state back and the next launch goes on at chain[1].
-        t->cl_ik_n = count; t->cl_ik_par = par_at; t->cl_ik_pairs = pairs; t->cl_ik_ab = ab_at; t->cl_ik_pp = pp_at;
-        int done = 0, fell = 0;
-        const int status = tsp_cluster_run(t, TSP_2OPT_BEST, tsp_cluster_size(t, TSP_2OPT_BEST), -1, time_limit_s, &done, &fell, tabu, iter0, tenure[0]);
-        t->cl_ik_n = 0;
-        t->h_state_fresh = false;
         if (status < 0 && !fell) return status;
         if (!fell) {
             hipLaunchKernelGGL(k_tabu_fix_evals, dim3(1), dim3(64), 0, s, t->d_state, tabu->d_tabu_pairs);
             TSP_HIP_TRY(hipGetLastError());
         }
-        TSP_HIP_TRY(hipMemcpyAsync(t->h_chain, t->d_chain, chain_ints * sizeof(int), hipMemcpyDeviceToHost, s));
-        TSP_HIP_TRY(hipStreamSynchronize(s));
-        (void)hipGetLastError();
-        int nc = 0;
-        for (int k = 0; k < count; ++k) {
-            const int *res = t->h_chain + 4 + 10 * k;
-            if (!res[4]) break;
-            double c;
-            memcpy(&c, res + 8, sizeof c);
-            if (obj) obj[k] = c;
-            if (improved) improved[k] = res[5];
-            if (trials) trials[k] = res[3];
-            if (res[5]) t->h_obj_snap.assign(1, c);
-            if (res[0] && tabu->list_valid) {
-                tabu->list_ub += 2;
-                if (tabu->list_ub > tabu->list_cap) tabu->list_valid = false;
-            }
-            if (last_accepted) *last_accepted = res[0];
-            ++nc;
-        }
-        if (fell) {
-            // The exchange gave up.  In the launch's first exchanges nothing of the search state has been touched (the list may have
-            // two entries more than stamps: a superset is what it has to be): the host takes the other path.  Later -- a workgroup
-            // that had been resident stopped answering in the middle of a chain -- the kicks of the completed iterations are in
-            // the stamps while the tour in HBM is the one the launch started from.
-            if (nc == 0) { if (tabu->list_valid) tabu->list_ub += 2; return TSP_OK; }
-            // Degraded, not aborted: the incumbent (tour and cost) and the stamps are intact, so the search goes on FROM THE
-            // INCUMBENT -- a valid tabu search, no longer the reference's trajectory (which a device shared to the point of a
-            // give-up has lost anyway: its runs end on the wall clock).  The event is counted and left in tsp_dev_last_error().
-            tsp::set_last_error("k_cluster_two_opt: the exchange gave up in the middle of a chain of tabu() iterations; the search goes on from the incumbent",
-                                hipErrorLaunchFailure, __FILE__, __LINE__);
-            t->inst->ctx->cl_chain_losses += 1;
-            memcpy(best_obj, t->h_chain + 2, sizeof(double));
-            if (!t->h_obj_snap.empty()) {
-                const int rc2 = tsp_grid_snapshot(t, /*restore=*/true);
-                if (rc2) return rc2;
-            }
-            tabu->list_valid = false;   // (entries may be missing for stamps of the lost iterations: rebuilt by a scan before the next use)
-            *completed = nc;
-            if (last_accepted) *last_accepted = 1;
-            return TSP_OK;
-        }
-        tabu->last_run_list = true;
-        memcpy(best_obj, t->h_chain + 2, sizeof(double));
-        *completed = nc;
-        if (status == TSP_TIME_LIMIT_EXCEEDED && nc < count) {
-            // iteration nc was cut short: its tour and recomputed cost are in HBM, and the incumbent is updated before the status is
-            // looked at (tabusearch.c:241-249, :255) -- reported in slot nc, which is not counted as completed
-            TSP_HIP_TRY(hipMemcpyAsync(t->h_state, t->d_state, sizeof(TourState), hipMemcpyDeviceToHost, s));
-            TSP_HIP_TRY(hipStreamSynchronize(s));
-            const double c = t->h_state[0].obj;
-            if (obj) obj[nc] = c;
-            if (improved) improved[nc] = 0;
-            if (c < *best_obj) {
-                *best_obj = c;
-                if (improved) improved[nc] = 1;
-                const int rc2 = tsp_grid_snapshot(t, false);
-                if (rc2) return rc2;
-            }
-        }
-        return status == TSP_TIME_LIMIT_EXCEEDED ? status : TSP_OK;
-    }
-    struct Chain { tsp_dev_tours *t; tsp_dev_tabu *tabu; int iter0, count; const int *tenure, *ab; } ch{t, tabu, iter0, count, tenure, ab};
-    auto post = [](void *ctx, hipStream_t st, int k, const int *d_err) {   // ONE launch between two CLUSTER launches: evaluation count, incumbent, kick, re-arm
-        Chain *q = static_cast<Chain *>(ctx);
-        tsp_dev_tours *tt = q->t;
-        const int chunk = k + 1 < q->count ? std::min(tt->first_min_rows, std::max(1, tt->n - 1)) : 0;
-        hipLaunchKernelGGL(k_tabu_post_chain, dim3(1), dim3(kApplyThreads), 0, st, tt->d_state, d_err, tt->d_order, tt->d_pos, q->tabu->d_stamp,
-                           tt->n, q->ab[2 * k], q->ab[2 * k + 1], q->iter0 + k, q->tenure[k], tt->d_chain, k, q->tabu->d_list, q->tabu->d_list_n,
-                           q->tabu->list_cap, tt->d_order_snap, q->tabu->d_tabu_pairs, chunk);
-    };
-    t->cl_post_ctx = &ch; t->cl_post_ran = false;
-    t->cl_post_k = post;
-    t->cl_post = [](void *ctx, hipStream_t st, const int *d_err) { static_cast<Chain *>(ctx)->t->cl_post_k(ctx, st, 0, d_err); };
-    t->cl_chain = [](void *ctx, hipStream_t, int k, int *iter, int *ten) {
-        Chain *q = static_cast<Chain *>(ctx);
-        if (k >= q->count) return false;
-        *iter = q->iter0 + k; *ten = q->tenure[k];   // (the re-arm was the previous post kernel's last act, unless it stopped the chain)
-        return true;
-    };
-    int done = 0, fell = 0;
-    const int status = tsp_cluster_run(t, TSP_2OPT_BEST, tsp_cluster_size(t, TSP_2OPT_BEST), -1, time_limit_s, &done, &fell, tabu, iter0, tenure[0]);
-    const bool post_ran = t->cl_post_ran;
-    const int launched = t->cl_chain_launched;
-    t->cl_post = nullptr; t->cl_post_k = nullptr; t->cl_chain = nullptr; t->cl_post_ctx = nullptr; t->cl_post_ran = false; t->cl_chain_launched = 0;
-    t->h_state_fresh = false;
-    if (!post_ran) return status < 0 && !fell ? status : TSP_OK;   // nothing was launched: the tour is as it was
-    // the results: one copy, one wait (the run's own wait came before the chain's last kernels were known to be through only if
-    // the chain was a single launch; the copy below is ordered behind all of them either way)
-    TSP_HIP_TRY(hipMemcpyAsync(t->h_chain, t->d_chain, chain_ints * sizeof(int), hipMemcpyDeviceToHost, s));
+    } else if (!ride.follow_ran) return status < 0 && !fell ? status : TSP_OK;   // nothing was launched: the tour is as it was
+    // the results: one copy, one wait (a queued chain: the run's own wait came before the chain's last kernels were known to be
+    // through only if the chain was a single launch; the copy below is ordered behind all of them either way)
+    TSP_HIP_TRY(hipMemcpyAsync(t->h_chain, t->d_chain, kChainInts * sizeof(int), hipMemcpyDeviceToHost, s));
     TSP_HIP_TRY(hipStreamSynchronize(s));
     (void)hipGetLastError();
-    tabu->last_run_list = true;
-    int nc = 0;
-    for (int k = 0; k < launched && k < count; ++k) {
-        const int *res = t->h_chain + 4 + 10 * k;
-        if (!res[4]) break;
-        double c;
-        memcpy(&c, res + 8, sizeof c);
-        if (obj) obj[k] = c;
-        if (improved) improved[k] = res[5];
-        if (trials) trials[k] = 1;
-        if (res[5]) t->h_obj_snap.assign(1, c);
-        if (res[0] && tabu->list_valid) {
-            tabu->list_ub += 2;
-            if (tabu->list_ub > tabu->list_cap) tabu->list_valid = false;
+    if (!(in_kernel && fell)) tabu->last_run_list = true;
+    const int nc = harvest_chain(t, tabu, in_kernel ? count : std::min(ride.launched, count), in_kernel, obj, improved, trials, last_accepted);
+    if (in_kernel && fell) {
+        // The exchange gave up.  In the launch's first exchanges nothing of the search state has been touched (the list may have
+        // two entries more than stamps: a superset is what it has to be): the host takes the other path.  Later -- a workgroup
+        // that had been resident stopped answering in the middle of a chain -- the kicks of the completed iterations are in
+        // the stamps while the tour in HBM is the one the launch started from.
+        if (nc == 0) { if (tabu->list_valid) tabu->list_ub += 2; return TSP_OK; }
+        // Degraded, not aborted: the incumbent (tour and cost) and the stamps are intact, so the search goes on FROM THE
+        // INCUMBENT -- a valid tabu search, no longer the reference's trajectory (which a device shared to the point of a
+        // give-up has lost anyway: its runs end on the wall clock).  The event is counted and left in tsp_dev_last_error().
+        tsp::set_last_error("k_cluster_two_opt: the exchange gave up in the middle of a chain of tabu() iterations; the search goes on from the incumbent",
+                            hipErrorLaunchFailure, __FILE__, __LINE__);
+        t->inst->ctx->cl_chain_losses += 1;
+        memcpy(best_obj, t->h_chain + kChainBest, sizeof(double));
+        if (!t->h_obj_snap.empty()) {
+            const int rc2 = tsp_grid_snapshot(t, /*restore=*/true);
+            if (rc2) return rc2;
         }
-        if (last_accepted) *last_accepted = res[0];
-        ++nc;
+        tabu->list_valid = false;   // (entries may be missing for stamps of the lost iterations: rebuilt by a scan before the next use)
+        *completed = nc;
+        if (last_accepted) *last_accepted = 1;
+        return TSP_OK;
     }
-    memcpy(best_obj, t->h_chain + 2, sizeof(double));
+    memcpy(best_obj, t->h_chain + kChainBest, sizeof(double));
     *completed = nc;
-    if (fell && nc == 0) return TSP_OK;   // the exchange gave up in the first launch: nothing completed, the host takes the other path
+    if (!in_kernel && fell && nc == 0) return TSP_OK;   // the exchange gave up in the first launch: nothing completed, the host takes the other path
+    if (in_kernel && status == TSP_TIME_LIMIT_EXCEEDED && nc < count) {
+        // iteration nc was cut short: its tour and recomputed cost are in HBM, and the incumbent is updated before the status is
+        // looked at (tabusearch.c:241-249, :255) -- reported in slot nc, which is not counted as completed
+        rc = cut_short(t, best_obj, obj ? obj + nc : nullptr, improved ? improved + nc : nullptr);
+        if (rc) return rc;
+    }
     return status == TSP_TIME_LIMIT_EXCEEDED ? status : TSP_OK;
 }
 
@@ -957,15 +891,12 @@ int tsp_grid_resident_tabu(tsp_dev_tours *t, tsp_dev_tabu *tabu, int iter, int t
     int rc = tsp_grid_rearm(t, TSP_2OPT_BEST);
     if (rc) return rc;
     int done = 0;
-    const int status = tsp_tabu_run(t, tabu, iter, tenure, time_limit_s, 2, &done);
+    TabuRide ride{tabu, iter, tenure};
+    const int status = tsp_tabu_run(t, &ride, time_limit_s, 2, &done);
     if (status < 0) return status;
-    if (status != TSP_OK || !done) {   // cut short: the recomputed cost was written after the last poll
-        hipStream_t s = t->inst->ctx->stream;
-        TSP_HIP_TRY(hipMemcpyAsync(t->h_state, t->d_state, sizeof(TourState), hipMemcpyDeviceToHost, s));
-        TSP_HIP_TRY(hipStreamSynchronize(s));
-    }
-    if (obj) *obj = t->h_state[0].obj;   // the poll that saw `done` carried the cost (tabusearch.c:168-172)
-    return status;
+    if (status != TSP_OK || !done) rc = cut_short(t, nullptr, obj, nullptr);   // the recomputed cost was written after the last poll
+    else if (obj) *obj = t->h_state[0].obj;                                       // the poll that saw `done` carried it (tabusearch.c:168-172)
+    return rc ? rc : status;
 }
 
 extern "C" {
@@ -1014,19 +945,9 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
         const long long npairs = (long long)inst->ng * (inst->ng + 1) / 2;
         if (npairs <= (1ll << 24) && inst->ng <= 32768 && TSP_SW(inst, SWEEP_TABLE, 1)) {
             // group pairs by box distance, dealt to the clusters in turn (see k_sweep)
-            const int ng = inst->ng, Q = t->sweep_blocks / kSweepCluster;
-            const long long ntests = (npairs + Q - 1) / Q;
-            std::vector<std::pair<double, int>> pr((size_t)npairs);
-            size_t w = 0;
-            for (int r = 0; r < ng; ++r)
-                for (int c = r; c < ng; ++c) {
-                    const double4 &rb = inst->h_gbox[r], &cb = inst->h_gbox[c];
-                    const double gx = std::max(0.0, std::max(rb.x - cb.y, cb.x - rb.y)), gy = std::max(0.0, std::max(rb.z - cb.w, cb.z - rb.w));
-                    pr[w++] = {gx * gx + gy * gy, (r << 16) | c};
-                }
-            std::sort(pr.begin(), pr.end());
-            std::vector<int> tab((size_t)Q * ntests, -1);
-            for (long long k = 0; k < npairs; ++k) tab[(size_t)(k % Q) * ntests + (size_t)(k / Q)] = pr[(size_t)k].second;
+            std::vector<int> tab;
+            cluster_deal(reinterpret_cast<const double *>(inst->h_gbox.data()), nullptr, nullptr, nullptr, inst->n, inst->ng,
+                         t->sweep_blocks / kSweepCluster, false, 1.0, tab);
             TSP_HIP_TRY(hipMalloc(&t->d_pairtab, tab.size() * sizeof(int)));
             TSP_HIP_TRY(hipMemcpy(t->d_pairtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
         }
@@ -1383,7 +1304,8 @@ int tsp_dev_two_opt_tabu(tsp_dev_inst *inst, tsp_dev_tabu *tabu, int iter, int t
     rc = tsp_dev_tours_upload(t, succ, succ_stride, inst->n, obj);
     if (rc) return rc;
     int done = 0;
-    const int status = tsp_tabu_run(t, tabu, iter, tenure, time_limit_s, 1, &done);
+    TabuRide ride{tabu, iter, tenure};
+    const int status = tsp_tabu_run(t, &ride, time_limit_s, 1, &done);
     if (status < 0) return status;
     rc = tsp_dev_tours_download(t, succ, succ_stride, inst->n, obj, stats);
     if (rc) return rc;

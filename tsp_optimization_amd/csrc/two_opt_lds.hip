@@ -669,9 +669,6 @@ hipError_t launch_lds(tsp_dev_tours *t, int mode, int rmin, int rmax, int max_it
 }
 }  // namespace
 
-// implemented in two_opt_grid.hip
-int tsp_grid_after_external_run(tsp_dev_tours *t, int mode, int timed_out, bool pos_written = false);
-
 #ifdef TSP_STAMPS
 extern "C" int tsp_dev_debug_lds(unsigned long long *out8) {
     if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(tsp::g_lds_prof), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
