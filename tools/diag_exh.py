@@ -8,7 +8,7 @@ sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
 import numpy as np
 os.environ["TSP_NO_FILTER"] = "1"
 from tsp_optimization_amd import build as B
-B.LIB_DIR = os.path.join(R, 'tsp_optimization_amd', 'lib_diag')
+B.LIB_DIR = os.environ.get('TSP_LIB_DIR') or os.path.join(R, 'tsp_optimization_amd', 'lib_diag')   # (TSP_LIB_DIR: another stamped build, for a before / after)
 from tsp_optimization_amd import engine as E
 from helpers import load_instance
 ctx = E.Context(0)
@@ -32,7 +32,8 @@ for _ in range(N):
 acc /= N
 for name, v in zip(["last wave starts", "first wave out of its rows", "mean wave out of its rows", "last wave out of its rows", "last block's candidate stored",
                     "shader clock in the rows (MHz)", "waves", "bookkeeping branches per wave", "cycles in them per wave",
-                    "cycles in the rows per wave"], acc):
+                    "cycles in the rows per wave", "start -> first row step, mean", "start -> first row step, longest",
+                    "last first row step begins"], acc):
     print("  %-32s %8.2f" % (name, v))
 
 # where the waves ran: HW_ID bits (gfx9): wave_id 3:0, simd_id 5:4, pipe 7:6, cu_id 11:8, sh_id 12, se_id 15:13

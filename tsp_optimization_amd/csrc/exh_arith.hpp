@@ -1,7 +1,8 @@
 // exh_arith.hpp -- the arithmetic of the exhaustive sweep's distances (two_opt_exh.hpp), free of HIP: k_move_pos and k_exh
 // compile exactly this text for the device, tests/test_cpu_exh_arith.py compiles it with the host compiler and checks it against
 // integer arithmetic.  Every function is an exact integer identity on its stated domain; none of them rounds.  The layout of the
-// strips (exh_strip, at the end) lives here for the same reason.
+// strips (exh_strip) and the dealing of their rows to the waves (exh_deal, at the end; tests/test_cpu_exh_deal.py) live here for
+// the same reason.
 //
 // Squared distance from norms.  Positions are stored relative to one node of the instance, so every coordinate is an integer
 // of magnitude < 2^21 (the *_ICOORD metrics bound the instance's diagonal; the pads lie at -6e6).  With the record
@@ -76,8 +77,8 @@ TSP_EXH_HD int exh_round(double s, double g) {
 
 // The strips of pair-columns, right-aligned: strip s holds the D-columns q0 .. q0 + weff of its wave and the pair-rows
 // p' < rows.  The slack strips * weff - n sits in strip 0 (rows from the unclamped q0; q0 itself clamped to 0, so strip 0
-// overlaps strip 1: a pair evaluated twice cannot change an arg-min whose tie-break is strict).  Kernel and host
-// (tsp_dev_tours_create's shares) both count the row units with these.
+// overlaps strip 1: a pair evaluated twice cannot change an arg-min whose tie-break is strict).  The kernel walks the strips
+// with exh_strip; the host (tsp_dev_tours_create's shares, exh_deal) counts the row units with these.
 struct ExhStrip { int q0, rows; };
 TSP_EXH_HD int exh_strips(int n, int weff) { return (n + weff - 1) / weff; }
 TSP_EXH_HD ExhStrip exh_strip(int n, int weff, int s) {
@@ -88,6 +89,43 @@ TSP_EXH_HD long long exh_total_rows(int n, int weff) {
     long long total = 0;
     for (int s = 0, ns = exh_strips(n, weff); s < ns; ++s) total += exh_strip(n, weff, s).rows;
     return total;
+}
+
+// The dealing.  The row units of all strips, laid end to end (strip 0 first), go to the waves of a tour's grid in contiguous
+// ranges, in wave order: equal shares of ceil(total / waves_total) units, or -- share[0] > 0 and gens > 0 -- the grid in `gens`
+// parts of waves_total / gens waves (the last part takes the remainder of that division) whose waves get share[part] units each
+// (tsp_dev_tours_create: the older a workgroup on its CU, the larger its share).  Every input is fixed when the tours handle is
+// created, so the host evaluates this once per wave into a table and k_exh loads its entry: the sum over the strips, the 64-bit
+// division and the search for the first strip are not on the kernel's start-up path.
+// A wave's range: `count` units from row `row` of strip `strip`, running on into the following strips from their row 0 (it may
+// cover several whole strips).  count == 0: nothing to do (strip = row = 0).
+struct alignas(16) ExhDeal {
+    int strip, row;
+    long long count;
+};
+TSP_EXH_HD ExhDeal exh_deal(int n, int weff, int waves_total, const int (&share)[4], int gens, int gw) {
+    const long long total = exh_total_rows(n, weff);
+    long long per = (total + waves_total - 1) / waves_total;
+    long long u_lo = per * gw;
+    if (share[0] > 0 && gens > 0) {
+        const int wq = waves_total / gens, g = gens - 1 < gw / wq ? gens - 1 : gw / wq, idx = gw - g * wq;
+        u_lo = 0;
+        for (int q = 0; q < g; ++q) u_lo += (long long)share[q] * wq;
+        per = share[g];
+        u_lo += per * idx;
+    }
+    const long long u_hi = total < u_lo + per ? total : u_lo + per;
+    ExhDeal d = {0, 0, 0};
+    if (u_lo >= u_hi) return d;
+    long long cum = 0;
+    int s = 0;
+    for (;; ++s) {   // the strip that holds unit u_lo (u_lo < total: it exists; a strip 0 without rows is passed over)
+        const int rows_s = exh_strip(n, weff, s).rows;
+        if (u_lo < cum + rows_s) break;
+        cum += rows_s;
+    }
+    d.strip = s; d.row = (int)(u_lo - cum); d.count = u_hi - u_lo;
+    return d;
 }
 
 }  // namespace tsp

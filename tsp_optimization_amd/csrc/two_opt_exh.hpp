@@ -19,11 +19,13 @@
 // Every delta is still computed exactly (integer-valued distances from the exact roots of tsp_dist.hpp's int_root).
 //
 // Layout.  k_move_pos (one thread per position) DECIDES the previous sweep's move -- every block for itself, from the
-// candidates k_exh left (sweep_decide, two_opt_step.hpp) --, carries it out of place (as k_move_recs does)
+// candidates k_exh left and the positions of their pairs beside them (sweep_decide, two_opt_step.hpp: pos is not read) --,
+// carries it out of place (as k_move_recs does)
 // and writes, in position order and padded: rec[p] = the record of u_p (exh_arith.hpp: -2x, -2y and the norm of its
 // coordinates relative to node 0, and e[p - 1]; position n repeats position 0; further pads lie far outside the instance),
 // pid[p] = u_p.
-// Hand-off.  k_exh ends at its block's candidate: no counter, no last block.  No word is read and written by different blocks
+// Hand-off.  k_exh ends at its block's candidate and, from the lane that owns the winning key, (pos[i], pos[j]) of that pair in
+// an array parallel to the candidates: no counter, no last block.  No word is read and written by different blocks
 // of one launch: a tour has two control blocks, k_move_pos reads slot s and its block 0 writes the advanced block to slot
 // s ^ 1; k_exh reads `done` there and one thread of it sets `open` there ("candidates written, not decided"), which nobody
 // else in that launch reads.  The host flips s per pair of launches; before it looks at a control block k_exh_close (one
@@ -31,7 +33,10 @@
 // k_exh: the pair-columns are cut into strips of W - 1 (W = 64 RJ columns of D per wave, RJ adjacent columns per lane),
 // laid out from the RIGHT end (exh_strip: the partial strip is the leftmost one, which has the fewest rows);
 // a strip's rows are its units of work, and the units of all strips, laid end to end, are dealt to the waves in
-// contiguous ranges (at most two strips per wave).  Per row step a lane
+// contiguous ranges -- by the host, once per tours handle (exh_deal, exh_arith.hpp: strip, row and number of units per wave, in
+// a table the wave reads with one scalar load); the wave walks the strips from there, over as many as its range covers.
+// The start of a wave, which every wave of the launch goes through at once and nothing hides, is three waits on memory: the
+// kernel arguments; `done` and the descriptor; the columns' records, row pa and the first batch of rows.  Per row step a lane
 // computes D(p, q) for its RJ columns (row operands are wave-uniform: scalar loads, no LDS), forms
 //     sum = D(p - 1, q - 1) + D(p, q) - e[q - 1]             (one three-operand add; D(p - 1, q - 1): own register, or
 //                                                             v_mov_b32_dpp wave_shr:1 for the lane's first column)
@@ -55,6 +60,7 @@ namespace tsp {
 // atomics on one word at the start of a kernel would be the thing measured.
 __device__ unsigned long long g_exh_w[8192 * 4];
 __device__ unsigned long long g_exh_t[8];
+__device__ unsigned long long g_exh_f[8192];   // per wave: wall clock when its first row step begins (0: a wave without rows)
 #endif
 
 constexpr int kExhPad = 1152;          // positions past n that k_move_pos fills (>= the widest strip + 2)
@@ -116,7 +122,8 @@ template <int WT, bool INT>
 __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__restrict__ coord, int *orders, int *poss, int *orders2,
                                                            int *poss2, const TourState *__restrict__ states,
                                                            TourState *__restrict__ states_next, const Partial *__restrict__ partials,
-                                                           size_t partial_per_tour, int flat_slots, ExhRec *__restrict__ rec,
+                                                           const int2 *__restrict__ wpos, size_t partial_per_tour, int flat_slots,
+                                                           ExhRec *__restrict__ rec,
                                                            int *__restrict__ pid, int n) {
     static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only (integer costs: the tour cost needs no staging)");
     __shared__ double s_d[kScanThreads / 64];
@@ -133,7 +140,8 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__rest
     const bool open = st->open != 0;   // (then nothing is pending: mv.L == 0)
     SweepDecision dec;
     if (open) {
-        dec = sweep_decide(partials + (size_t)tour * partial_per_tour, flat_slots, mv.pos, n, s_d, s_k);
+        dec = sweep_decide(partials + (size_t)tour * partial_per_tour, wpos + (size_t)tour * partial_per_tour, flat_slots, mv.pos, n,
+                           s_d, s_k);   // the winner's positions came with its candidate: pos is not read
         if (!dec.found) {   // the local optimum: block 0 recomputes the cost (tabusearch.c:168-172), nobody has records to build
             if (blockIdx.x != 0) return;
             const double cost = tour_cost_block<WT, INT>(coord, mv.order, mv.pos, n, s_d, nullptr);
@@ -184,8 +192,8 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__rest
 template <int WT, bool INT>
 __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__restrict__ coord, const int *orders, const int *poss,
                                                             const int *orders2, const int *poss2, TourState *states,
-                                                            const Partial *__restrict__ partials, size_t partial_per_tour,
-                                                            int flat_slots, int n) {
+                                                            const Partial *__restrict__ partials, const int2 *__restrict__ wpos,
+                                                            size_t partial_per_tour, int flat_slots, int n) {
     static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only");
     __shared__ double s_d[kScanThreads / 64];
     __shared__ u64 s_k[kScanThreads / 64];
@@ -195,7 +203,8 @@ __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__res
     const size_t base = (size_t)tour * n;
     const bool second = st->parity != 0;
     const int *order = (second ? orders2 : orders) + base, *pos = (second ? poss2 : poss) + base;
-    const SweepDecision dec = sweep_decide(partials + (size_t)tour * partial_per_tour, flat_slots, pos, n, s_d, s_k);
+    const SweepDecision dec = sweep_decide(partials + (size_t)tour * partial_per_tour, wpos + (size_t)tour * partial_per_tour,
+                                           flat_slots, pos, n, s_d, s_k);
     double cost = 0.0;
     if (!dec.found) cost = tour_cost_block<WT, INT>(coord, order, pos, n, s_d, nullptr);
     if (threadIdx.x == 0) {
@@ -209,44 +218,40 @@ __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__res
 // RJ = kExhRJ columns per lane, four workgroups of four waves per CU (the host pins that with its LDS request)
 template <int WT, bool INT, int RJ>
 __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const ExhRec *__restrict__ rec_all,
-                                                      const int *__restrict__ pid_all, int waves_total, int4 share, int gens) {
-    // the position arrays are kernel arguments of their own, restrict-qualified: the row operands are wave-uniform loads, and
-    // the compiler only issues them as scalar loads (s_load: no vector-memory slot, no VGPRs) when it can prove that the
-    // kernel's own stores (the candidate slot, `open`) never touch them
+                                                      const int *__restrict__ pid_all, const ExhDeal *__restrict__ deal,
+                                                      int2 *__restrict__ wpos_all) {
+    // the position arrays and the table of the dealing are kernel arguments of their own, restrict-qualified: the row operands
+    // and a wave's descriptor are wave-uniform loads, and the compiler only issues them as scalar loads (s_load: no
+    // vector-memory slot, no VGPRs) when it can prove that the kernel's own stores (the candidate slot, `open`) never touch them
     static_assert(exh_metric<WT>(), "integer-coordinate metrics only");
     constexpr int W = 64 * RJ, WEFF = W - 1;
+#ifdef TSP_STAMPS
+    const unsigned long long stamp_r0 = __builtin_amdgcn_s_memrealtime(), stamp_c0 = __builtin_amdgcn_s_memtime();
+    unsigned long long stamp_hits = 0, stamp_hit_cycles = 0, stamp_first = 0;
+#endif
     const int tour = blockIdx.z;
-    const TourState *st = a.states + tour;
-    if (st->done) return;
     const int n = a.n, tid = threadIdx.x, lane = tid & 63;
+    // ---- this wave's share (exh_deal, evaluated by the host when the handle was created) and the tour's `done`: every wave of
+    // the launch is here at once and nothing hides the latency, so the two loads travel together -- one wait, then the branch
+    const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kScanThreads / 64) + (tid >> 6));
+    int done = a.states[tour].done;
+    ExhDeal dl = deal[gw];
+    // (both loaded before the branch; and the kernel arguments of the rows fetched by the entry's one batch of loads, not by
+    // batches of their own further down.  The pointers only as a comparison: handed to the statement themselves they would count
+    // as escaped, and the loads through them would no longer be scalar loads.)
+#ifdef TSP_STAMPS
+    // (in the stamped build the compiler fetches `done` with a vector load: back to scalar registers for the statement below)
+    done = __builtin_amdgcn_readfirstlane(done);
+    dl.strip = __builtin_amdgcn_readfirstlane(dl.strip); dl.row = __builtin_amdgcn_readfirstlane(dl.row);
+    dl.count = (long long)(((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)((u64)dl.count >> 32)) << 32) |
+                           (unsigned)__builtin_amdgcn_readfirstlane((int)(u64)dl.count));
+#endif
+    const int args_null = (int)(rec_all == nullptr) | (int)(pid_all == nullptr) | (int)(wpos_all == nullptr);
+    asm volatile("" : "+s"(done), "+s"(dl.strip), "+s"(dl.row), "+s"(dl.count) : "s"(n), "s"(args_null), "s"(a.partial_per_tour));
+    if (done) return;
     const size_t pbase = (size_t)tour * (n + kExhPad);
     const ExhRec *__restrict__ rec = rec_all + pbase;
     const int *__restrict__ pid = pid_all + pbase;
-
-#ifdef TSP_STAMPS
-    const unsigned long long stamp_r0 = wall_clock64(), stamp_c0 = clock64();
-    unsigned long long stamp_hits = 0, stamp_hit_cycles = 0;
-#endif
-    // ---- this wave's share: units [u_lo, u_hi) of the strips' rows laid end to end --------------------------------
-    const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kScanThreads / 64) + (tid >> 6));
-    const int strips = exh_strips(n, WEFF);                         // pair-columns 0 .. n-1
-    const long long total = exh_total_rows(n, WEFF);                // pair-rows p' < q' <= q0 + WEFF - 1, p' <= n - 2
-    // A SIMD serves its oldest wave first, and the workgroups of a CU are as old as their place in the grid: the first quarter of
-    // the grid leaves its rows at 13.7 us, the others at 20.6 / 28.2 / 35.4 (equal shares; tools/diag_exh.py) -- while four waves
-    // are active the SIMD's issue slots go 53 / 26 / 13 / 8 %.  share = the rows per wave of each part of the grid (quarters at four workgroups per CU) in those
-    // proportions (host: tsp_dev_tours_create), so that the four waves of a SIMD finish together; share.x == 0: equal shares.
-    long long per = (total + waves_total - 1) / waves_total;
-    long long u_lo = per * gw;
-    if (share.x > 0 && gens > 0) {   // gens = workgroups per CU = equal parts of the grid with a share of their own (2 .. 4)
-        const int wq = waves_total / gens, g = min(gens - 1, gw / wq), idx = gw - g * wq;
-        const int sh[4] = {share.x, share.y, share.z, share.w};
-        u_lo = 0;
-        for (int q = 0; q < g; ++q) u_lo += (long long)sh[q] * wq;
-        per = sh[g];
-        u_lo += per * idx;
-    }
-    long long u_hi = min(total, u_lo + per);
-    u_lo = min(u_lo, total);
 
     int bd = -1, bp = -1, bq = -1;     // integer costs: delta < 0  <=>  delta <= -1; (bd, no pair) loses every tie
     int wbd = -1;                      // wave-uniform: the lowest delta any lane of this wave has seen
@@ -265,23 +270,45 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
         }
     };
 
-    long long cum = 0;
-    for (int s = 0; s < strips && u_lo < u_hi; ++s) {
+    // the walk: `count` units from row dl.row of strip dl.strip, on into the following strips (any number of them)
+    const int strips = exh_strips(n, WEFF);
+    int pa = dl.row;
+    long long rem = dl.count;
+    for (int s = dl.strip; rem > 0 && s < strips; ++s) {
         const ExhStrip strip = exh_strip(n, WEFF, s);
-        const int rows_s = strip.rows;
-        if (u_lo >= cum + rows_s) { cum += rows_s; continue; }
         // segment of strip s: pair-rows [pa, pb)
-        const int pa = (int)(u_lo - cum), pb = (int)min<long long>(rows_s, u_hi - cum);
-        u_lo = cum + pb;
-        cum += rows_s;
+        const int pb = (int)min<long long>(strip.rows, pa + rem);
+        rem -= pb - pa;
         const int Q0 = strip.q0;
         double cx[RJ], cy[RJ], cn[RJ];
         int nce[RJ], Dp[RJ], qk[RJ];   // nce[k] = -e[q_k - 1]: what the pair of column k removes on the column side
+        // Every operand of the segment's start in flight together: the columns' whole records (vector loads), row pa's record
+        // and the first batch of rows (scalar loads); the first use of any of them comes behind the barrier below, and the
+        // empty statements keep every one of these loads here (left alone, the compiler fetches the columns' eprev first, waits,
+        // and only then asks for the rest).
+        // The row records are wave-uniform: scalar loads, kRowBatch rows per batch, and the NEXT batch is on its way
+        // while this one is worked (a scalar load that misses the CU's constant cache takes longer than one row step: with a
+        // prefetch distance of one row the waves spent a quarter of their cycles in s_waitcnt, SQ_WAIT_ANY).  Positions up to
+        // n + 2 kRowBatch exist: k_move_pos pads.
+        struct Rows { ExhRec r[kRowBatch]; };
+        ExhRec col[RJ];
 #pragma unroll
         for (int k = 0; k < RJ; ++k) {
             qk[k] = Q0 + RJ * lane + k;
-            const ExhRec c = rec[qk[k]];
-            cx[k] = exh_col(c.m2x); cy[k] = exh_col(c.m2y); cn[k] = c.nrm; nce[k] = -c.eprev;
+            col[k] = rec[qk[k]];
+        }
+        const ExhRec rpa = rec[pa];
+        int p = pa + 1;
+        Rows nx = *reinterpret_cast<const Rows *>(rec + p);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" : : "s"(rpa.m2x), "s"(rpa.m2y), "s"(rpa.nrm), "s"(rpa.eprev));
+#pragma unroll
+        for (int u = 0; u < kRowBatch; ++u) asm volatile("" : : "s"(nx.r[u].m2x), "s"(nx.r[u].m2y), "s"(nx.r[u].nrm), "s"(nx.r[u].eprev));
+#pragma unroll
+        for (int k = 0; k < RJ; ++k) asm volatile("" : : "v"(col[k].m2x), "v"(col[k].m2y), "v"(col[k].nrm), "v"(col[k].eprev));
+#pragma unroll
+        for (int k = 0; k < RJ; ++k) {
+            cx[k] = exh_col(col[k].m2x); cy[k] = exh_col(col[k].m2y); cn[k] = col[k].nrm; nce[k] = -col[k].eprev;
         }
         // lane 0's first column has no left neighbour in this wave (the DPP hands it 0, and position 0 has no edge before it):
         // its pair belongs to the strip on the left; should D alone ever pass the test below, the bookkeeping drops it
@@ -289,9 +316,8 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
 #pragma unroll
         for (int k = 0; k < RJ; ++k) asm("" : "+v"(nce[k]));   // kept negated: an addend of v_add3_u32, not a subtraction of its own
         {   // row pa: distances only
-            const ExhRec r = rec[pa];
 #pragma unroll
-            for (int k = 0; k < RJ; ++k) Dp[k] = exh_dist<WT>(cx[k], cy[k], cn[k], r);
+            for (int k = 0; k < RJ; ++k) Dp[k] = exh_dist<WT>(cx[k], cy[k], cn[k], rpa);
         }
         // rows p = pa + 1 .. pb: D(p, .), then the pairs (p - 1, q - 1).  Up to p = Q0 every column of the strip lies above
         // the row (q_k > p for every evaluated pair); beyond it the pairs on and below the diagonal are masked.
@@ -322,14 +348,10 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
 #endif
             }
         };
-        // The row records are wave-uniform: scalar loads, kRowBatch rows per batch, and the NEXT batch is on its way
-        // while this one is worked (a scalar load that misses the CU's constant cache takes longer than one row step: with a
-        // prefetch distance of one row the waves spent a quarter of their cycles in s_waitcnt, SQ_WAIT_ANY).  Positions up to
-        // n + 2 kRowBatch exist: k_move_pos pads.
-        struct Rows { ExhRec r[kRowBatch]; };
         const int p_plain = min(pb, Q0);
-        int p = pa + 1;
-        Rows nx = *reinterpret_cast<const Rows *>(rec + p);
+#ifdef TSP_STAMPS
+        if (!stamp_first) stamp_first = wall_clock64();   // the first row step begins
+#endif
         for (; p <= pb; p += kRowBatch) {
             const Rows cur = nx;
             nx = *reinterpret_cast<const Rows *>(rec + p + kRowBatch);
@@ -342,13 +364,14 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
                     if (p + u <= pb) step(p + u, cur.r[u], std::true_type{});   // the predicate is harmless above the diagonal
             }
         }
+        pa = 0;
     }
 
     // ---- the wave's and the block's arg-min (delta, (i, j)); the tour's is taken by the next launch -----------------------
 #ifdef TSP_STAMPS
     if (lane == 0 && tour == 0) {
         const int w = (int)blockIdx.x * (kScanThreads / 64) + (tid >> 6);
-        if (w < 8192) { g_exh_w[4 * w] = stamp_r0; g_exh_w[4 * w + 1] = wall_clock64(); unsigned hwid, xcc;
+        if (w < 8192) { g_exh_f[w] = stamp_first; g_exh_w[4 * w] = stamp_r0; g_exh_w[4 * w + 1] = wall_clock64(); unsigned hwid, xcc;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
             g_exh_w[4 * w + 2] = (clock64() - stamp_c0) | ((unsigned long long)hwid << 32); g_exh_w[4 * w + 3] = 1 | (stamp_hits << 8) | ((unsigned long long)(xcc & 0xf) << 60) | ((stamp_hit_cycles & 0xfffffffffull) << 24); }
@@ -357,17 +380,24 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
     // only the lanes that hold the wave's lowest delta need their pair's node ids (usually one lane: one pair of loads)
     double d = 0.0;
     u64 key = kNoKey;
+    int2 wp = make_int2(0, 0);   // (pos[i], pos[j]) of the lane's pair, i < j the node ids of the key
     {
         const int wmin = (int)(unsigned)(wave_min_u64((u64)((unsigned)bd ^ 0x80000000u)) ^ 0x80000000u);
         if (bp >= 0 && bd == wmin) {
             const int i = pid[bp], j = pid[bq];
             d = (double)bd;
             key = make_key(min(i, j), max(i, j));
+            wp = i < j ? make_int2(bp, bq) : make_int2(bq, bp);
         }
     }
+    const u64 mine = key;
     __shared__ double s_d[kScanThreads / 64];
     __shared__ u64 s_k[kScanThreads / 64];
     block_argmin<true>(d, key, s_d, s_k);
+    // The winner's positions travel with the candidate (sweep_decide reads them in the same round and never asks pos): stored by
+    // the lane that owns the winning key.  A key names one pair of positions, so two owners (strip 0 overlaps strip 1) store
+    // the same words.
+    if (mine == key && key != kNoKey) wpos_all[(size_t)tour * a.partial_per_tour + blockIdx.x] = wp;
     // The launch ends here: the block's candidate, empty or not, as plain stores -- its readers (every block of the next
     // k_move_pos, or k_exh_close) are later launches.  `open` tells them so; nothing in this launch reads it.
     if (tid == 0) {

@@ -305,6 +305,17 @@ void launch_flush(tsp_dev_tours *t) {
     hipLaunchKernelGGL(k_flush_state, dim3((t->B + 255) / 256), dim3(256), 0, s, t->d_state, t->B);
 }
 
+// The dealing of the exhaustive sweep's row units (exh_deal, exh_arith.hpp): one descriptor per wave of a tour's grid, the same
+// for every tour of the handle.  To be called again wherever exh_share or exh_gens change.
+int exh_fill_deal(tsp_dev_tours *t) {
+    const int waves_total = t->exh_blocks * (kScanThreads / 64);
+    std::vector<ExhDeal> tab((size_t)waves_total);
+    for (int gw = 0; gw < waves_total; ++gw) tab[(size_t)gw] = exh_deal(t->n, 64 * kExhRJ - 1, waves_total, t->exh_share, t->exh_gens, gw);
+    if (!t->d_exh_deal) TSP_HIP_TRY(hipMalloc(&t->d_exh_deal, tab.size() * sizeof(ExhDeal)));
+    TSP_HIP_TRY(hipMemcpy(t->d_exh_deal, tab.data(), tab.size() * sizeof(ExhDeal), hipMemcpyHostToDevice));
+    return TSP_OK;
+}
+
 // Exhaustive sweeps (k_move_pos + k_exh) leave their last sweep undecided: before the host copies a control block, and before
 // anything else works on the tours, that sweep is decided and its move recorded as pending (k_exh_close).
 void launch_exh_close(tsp_dev_tours *t) {
@@ -312,7 +323,8 @@ void launch_exh_close(tsp_dev_tours *t) {
     TSP_DISPATCH_METRIC(t->inst->wtype, t->inst->integer_cost, {
         if constexpr (exh_metric<WTC>())
             hipLaunchKernelGGL((k_exh_close<WTC, INTC>), dim3(t->B), dim3(kScanThreads), 0, s, t->inst->d_coord, t->d_order, t->d_pos,
-                               t->d_order2, t->d_pos2, t->d_state, t->d_partial, t->partial_per_tour, t->exh_blocks, t->n);
+                               t->d_order2, t->d_pos2, t->d_state, t->d_partial, t->d_exh_wpos, t->partial_per_tour, t->exh_blocks,
+                               t->n);
     });
 }
 
@@ -357,13 +369,12 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
             t->d_state = t->d_state_base + (size_t)t->slot * t->B;
             hipLaunchKernelGGL((k_move_pos<WT, INT>), dim3((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B), dim3(kScanThreads), 0, s,
                                t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2, cur, t->d_state, t->d_partial,
-                               t->partial_per_tour, t->exh_blocks, t->d_prec, t->d_pid, t->n);
+                               t->d_exh_wpos, t->partial_per_tour, t->exh_blocks, t->d_prec, t->d_pid, t->n);
             a.states = t->d_state;
             a.flat_slots = t->exh_blocks;
-            const int wt_ = t->exh_blocks * (kScanThreads / 64);
             const dim3 g(t->exh_blocks, 1, t->B);
-            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_prec, t->d_pid, wt_,
-                               make_int4(t->exh_share[0], t->exh_share[1], t->exh_share[2], t->exh_share[3]), t->exh_gens);
+            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_prec, t->d_pid,
+                               t->d_exh_deal, t->d_exh_wpos);
             return TSP_OK;
         }
     }
@@ -989,6 +1000,9 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
                 t->exh_gens = waves;
                 for (int q = 0; q < waves; ++q) t->exh_share[q] = (int)std::max<long long>(1, (total * pc[q] + sum * wq - 1) / (sum * wq));
             }
+            // exh_share and exh_gens are set here and nowhere else: the table of the dealing is filled once
+            const int rc = exh_fill_deal(t);
+            if (rc) return rc;
         }
     }
     TSP_HIP_TRY(hipMalloc(&t->d_cl_ticket, cl_words * sizeof(int)));
@@ -1001,6 +1015,10 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
     TSP_HIP_TRY(hipMalloc(&t->d_state_base, 2 * (size_t)B * sizeof(TourState)));   // two slots per tour (k_first)
     t->d_state = t->d_state_base; t->slot = 0;
     TSP_HIP_TRY(hipMalloc(&t->d_partial, (size_t)B * t->partial_per_tour * sizeof(Partial)));
+    if (t->exh_blocks > 0) {   // the positions of each block's candidate (k_exh), parallel to d_partial
+        TSP_HIP_TRY(hipMalloc(&t->d_exh_wpos, (size_t)B * t->partial_per_tour * sizeof(int2)));
+        TSP_HIP_TRY(hipMemset(t->d_exh_wpos, 0, (size_t)B * t->partial_per_tour * sizeof(int2)));
+    }
     TSP_HIP_TRY(hipMalloc(&t->d_slot_evals, (size_t)B * t->partial_per_tour * sizeof(int)));
     TSP_HIP_TRY(hipMalloc(&t->d_ticket, (size_t)B * sizeof(int)));
     t->use_recs = TSP_SW(inst, BEST_RECS, 1);
@@ -1023,7 +1041,7 @@ void tsp_dev_tours_destroy(tsp_dev_tours *t) {
     (void)hipFree(t->d_state_base); (void)hipFree(t->d_partial); (void)hipFree(t->d_slot_evals); (void)hipFree(t->d_ticket); (void)hipFree(t->d_rec);
     (void)hipFree(t->d_gmax); (void)hipFree(t->d_order2); (void)hipFree(t->d_pos2); (void)hipFree(t->d_pairtab); (void)hipFree(t->d_cl_ticket);
     (void)hipFree(t->d_row_ticket); (void)hipFree(t->d_row_evals); (void)hipFree(t->d_row_slot);
-    (void)hipFree(t->d_prec); (void)hipFree(t->d_pid);
+    (void)hipFree(t->d_prec); (void)hipFree(t->d_pid); (void)hipFree(t->d_exh_deal); (void)hipFree(t->d_exh_wpos);
     (void)hipFree(t->d_cl_slots); (void)hipFree(t->d_cl_pairtab); (void)hipFree(t->d_cl_stats);
     (void)hipFree(t->d_chain); (void)hipHostFree(t->h_chain); (void)hipFree(t->d_order_snap); (void)hipFree(t->d_kick_result); (void)hipHostFree(t->h_kick_result); (void)hipHostFree(t->h_cl_err);
     (void)hipHostFree(t->h_state);
@@ -1322,19 +1340,22 @@ int tsp_dev_two_opt_tabu(tsp_dev_inst *inst, tsp_dev_tabu *tabu, int iter, int t
 // the launch's work; the decision belongs to the next k_move_pos), [5] shader clock during the rows (MHz), [6] waves seen,
 // [7] / [8] / [9] per wave: bookkeeping branches taken, shader cycles in them, cycles in the rows
 int tsp_dev_debug_exh_stamps(double *out8) {
-    std::vector<unsigned long long> w(8192 * 4);
+    std::vector<unsigned long long> w(8192 * 4), f(8192);
+    if (hipMemcpyFromSymbol(f.data(), HIP_SYMBOL(tsp::g_exh_f), f.size() * 8) != hipSuccess) return -1;
     unsigned long long h[8];
     if (hipMemcpyFromSymbol(w.data(), HIP_SYMBOL(tsp::g_exh_w), w.size() * 8) != hipSuccess) return -1;
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(tsp::g_exh_t), sizeof h) != hipSuccess) return -1;
     unsigned long long t0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0;
-    double esum = 0, csum = 0, rsum = 0, hsum = 0, hcsum = 0;
-    int nw = 0;
+    double esum = 0, csum = 0, rsum = 0, hsum = 0, hcsum = 0, fsum = 0;
+    unsigned long long f1 = 0, fd1 = 0;
+    int nw = 0, nf = 0;
     for (int k = 0; k < 8192; ++k) {
         if (!w[4 * k + 3]) continue;
         ++nw;
         t0 = std::min(t0, w[4 * k]); s1 = std::max(s1, w[4 * k]);
         e0 = std::min(e0, w[4 * k + 1]); e1 = std::max(e1, w[4 * k + 1]);
         esum += (double)w[4 * k + 1]; csum += (double)(w[4 * k + 2] & 0xffffffffull); rsum += (double)(w[4 * k + 1] - w[4 * k]);
+        if (f[k]) { ++nf; fsum += (double)(f[k] - w[4 * k]); fd1 = std::max(fd1, f[k] - w[4 * k]); f1 = std::max(f1, f[k]); }
         hsum += (double)((w[4 * k + 3] >> 8) & 0xffff); hcsum += (double)((w[4 * k + 3] >> 24) & 0xfffffffffull);
     }
     if (!nw) return 0;
@@ -1342,6 +1363,8 @@ int tsp_dev_debug_exh_stamps(double *out8) {
     out8[3] = (double)(e1 - t0) / 100.0; out8[4] = ((double)h[4] - (double)t0) / 100.0;
     out8[5] = rsum > 0 ? csum / rsum * 100.0 : 0.0; out8[6] = nw;
     out8[7] = hsum / nw; out8[8] = hcsum / nw; out8[9] = csum / nw;
+    // [10] / [11] mean / longest "wave starts -> its first row step begins" over the waves with rows, [12] when the last of them begins
+    out8[10] = nf ? fsum / nf / 100.0 : 0.0; out8[11] = (double)fd1 / 100.0; out8[12] = nf ? (double)(f1 - t0) / 100.0 : 0.0;
     if (const char *dump = getenv("TSP_EXH_DUMP")) {   // per wave: exit time (us after the first start), XCC, HW_ID
         if (FILE *fp = fopen(dump, "w")) {
             for (int k = 0; k < 8192; ++k)
@@ -1351,6 +1374,8 @@ int tsp_dev_debug_exh_stamps(double *out8) {
     }
     std::fill(w.begin(), w.end(), 0ull);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(tsp::g_exh_w), w.data(), w.size() * 8);
+    std::fill(f.begin(), f.end(), 0ull);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(tsp::g_exh_f), f.data(), f.size() * 8);
     const unsigned long long z[8] = {0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(tsp::g_exh_t), z, sizeof z);
     return nw;

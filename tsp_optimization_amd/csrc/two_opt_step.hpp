@@ -109,40 +109,58 @@ __device__ __forceinline__ MoveView move_view(const TourState *st, const int *o1
 // ---- the decision of a sweep whose block candidates a FINISHED launch has left in memory ----------------------
 // Block-wide (kScanThreads threads), for every block that wants the answer: the arg-min of (delta, (i, j)) over the `nslots`
 // candidates of a tour -- apply_step's rule: better() on (delta, key), a move only when delta < 0 -- and the winner's
-// positions in the current copy of pos.  The candidates were written by an earlier launch: ordinary loads, all of a thread's
-// in flight at once, then one more latency for pos[i] and pos[j].  The reduction order differs from apply_step's; the
-// arg-min with a strict tie-break does not depend on it.  s_d, s_k: >= kScanThreads / 64 entries each.
+// positions.  The candidates were written by an earlier launch: ordinary loads, all of a thread's in flight at once.
+// The positions: with `wpos` (the exhaustive sweep: k_exh knows its pairs by position and leaves (pos[i], pos[j]) beside each
+// candidate) they are loaded in the same round as the candidates, and the thread that owns the winning key hands them out
+// through LDS; without it (wpos == nullptr) they cost one more latency for pos[i] and pos[j] in the current copy of pos.
+// The reduction order differs from apply_step's; the arg-min with a strict tie-break does not depend on it.  Two slots may
+// hold the same pair (k_exh: strip 0 overlaps strip 1): they hold the same positions.  s_d, s_k: >= kScanThreads / 64
+// entries each.
 struct SweepDecision {
     int found = 0, i = -1, j = -1;   // found == 0: local optimum (i = j = -1)
     int pa = 0, pb = 0, L = 0;       // pos[i], pos[j]; reverse positions pa + 1 .. pb (cyclic), L = (pb - pa) mod n of them
 };
 
-__device__ __forceinline__ SweepDecision sweep_decide(const Partial *__restrict__ part, int nslots, const int *__restrict__ pos, int n,
-                                                      double *s_d, u64 *s_k) {
+__device__ __forceinline__ SweepDecision sweep_decide(const Partial *__restrict__ part, const int2 *__restrict__ wpos, int nslots,
+                                                      const int *__restrict__ pos, int n, double *s_d, u64 *s_k) {
+    __shared__ int2 s_wpos;
     const int tid = threadIdx.x;
     double bd = 0.0;
     u64 key = kNoKey;
+    int2 bw = make_int2(0, 0);
     constexpr int PU = 8;   // 2 048 candidates = 8 per thread: one round
     for (int s0 = tid; s0 < nslots; s0 += PU * kScanThreads) {
         Partial p[PU];
+        int2 w[PU];
 #pragma unroll
         for (int k = 0; k < PU; ++k) {
             const int s = s0 + k * kScanThreads;
             p[k].delta = 0.0; p[k].i = -1; p[k].j = -1;
-            if (s < nslots) p[k] = part[s];
+            w[k] = make_int2(0, 0);
+            if (s < nslots) {
+                p[k] = part[s];
+                if (wpos) w[k] = wpos[s];
+            }
         }
 #pragma unroll
         for (int k = 0; k < PU; ++k) {
             const u64 kk = make_key(p[k].i, p[k].j);
-            if (better(p[k].delta, kk, bd, key)) { bd = p[k].delta; key = kk; }
+            if (better(p[k].delta, kk, bd, key)) { bd = p[k].delta; key = kk; bw = w[k]; }
         }
     }
+    const u64 mine = key;
     block_argmin<true>(bd, key, s_d, s_k);
     SweepDecision d;
-    d.found = key != kNoKey && bd < 0;
+    d.found = key != kNoKey && bd < 0;   // (block-uniform)
     if (d.found) {
         d.i = key_i(key); d.j = key_j(key);
-        d.pa = pos[d.i]; d.pb = pos[d.j];
+        if (wpos) {
+            if (mine == key) s_wpos = bw;   // every owner of the key holds the same pair of positions
+            __syncthreads();
+            d.pa = s_wpos.x; d.pb = s_wpos.y;
+        } else {
+            d.pa = pos[d.i]; d.pb = pos[d.j];
+        }
         d.L = d.pb - d.pa; if (d.L < 0) d.L += n;
     }
     return d;
