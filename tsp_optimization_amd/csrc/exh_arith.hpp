@@ -1,8 +1,9 @@
 // exh_arith.hpp -- the arithmetic of the exhaustive sweep's distances (two_opt_exh.hpp), free of HIP: k_move_pos and k_exh
 // compile exactly this text for the device, tests/test_cpu_exh_arith.py compiles it with the host compiler and checks it against
 // integer arithmetic.  Every function is an exact integer identity on its stated domain; none of them rounds.  The layout of the
-// strips (exh_strip) and the dealing of their rows to the waves (exh_deal, at the end; tests/test_cpu_exh_deal.py) live here for
-// the same reason.
+// strips (exh_strip), the dealing of their rows to the waves (exh_deal, at the end; tests/test_cpu_exh_deal.py) and the rule by
+// which k_move_pos permutes the records of one sweep into those of the next (exh_perm; tests/test_cpu_exh_permute.py) live here
+// for the same reason.
 //
 // Squared distance from norms.  Positions are stored relative to one node of the instance, so every coordinate is an integer
 // of magnitude < 2^21 (the *_ICOORD metrics bound the instance's diagonal; the pads lie at -6e6).  With the record
@@ -34,7 +35,7 @@ struct alignas(32) ExhRec {
     double m2x, m2y;   // -2 x, -2 y (relative coordinates)
     double nrm;        // x^2 + y^2
     int eprev;         // length of the tour edge that ENDS at this position: d(u_{p-1}, u_p); 0 at position 0 and on the pads
-    int pad_;
+    int id;            // the node at this position (position n repeats position 0; -1 on the pads)
 };
 
 TSP_EXH_HD void exh_rec_xy(double x, double y, ExhRec &r) {
@@ -73,6 +74,59 @@ template <int MODE>
 TSP_EXH_HD int exh_round(double s, double g) {
     const double k = exh_k<MODE>(g);
     return exh_d(exh_ki(k), exh_up<MODE>(k, exh_e<MODE>(s, k)));
+}
+
+// the same distance from two records (the first one as the column): what k_exh computes for a pair of positions, and what
+// k_move_pos computes at a cut point of a move.  root(v) is the approximate root of v: the hardware's on the device.
+template <int MODE, class Root>
+TSP_EXH_HD int exh_dist_recs(const ExhRec &c, const ExhRec &r, Root root) {
+    const double s = exh_s(exh_col(c.m2x), exh_col(c.m2y), c.nrm, r.m2x, r.m2y, r.nrm);
+    return exh_round<MODE>(s, root(exh_root_arg<MODE>(s)));
+}
+
+// ---- the records of the tour AFTER a 2-opt move, by permutation of the records before it ------------------------------------
+// The move reverses the L positions pa1 .. pa1 + L - 1 (cyclic) of a tour of n positions: the node at new position p is the node
+// at old position exh_mirror(p) (an involution; MoveView of two_opt_step.hpp is this function).
+TSP_EXH_HD int exh_mirror(int p, int n, int pa1, int L) {
+    int t = p - pa1; if (t < 0) t += n;
+    if (t >= L) return p;
+    int q = pa1 + (L - 1 - t); if (q >= n) q -= n;
+    return q;
+}
+
+// New position k in [0, n] (position n repeats position 0): a = mirror((k - 1) mod n) and b = mirror(k mod n) are old positions.
+// The new record takes -2x, -2y, the norm and the id from old record b; its eprev is
+//   EXH_E_ZERO  0: position 0 has no edge before it;
+//   EXH_E_B     old record b's, when b = a + 1 (mod n) and b > 0: the same edge, walked the same way;
+//   EXH_E_A     old record a's, when a = b + 1 (mod n) and a > 0: the same edge, walked the other way (inside the segment);
+//   EXH_E_WRAP  old record n's -- the closing edge, d(u_{n-1}, u_0) --, when the pair is (n - 1, 0) in either direction;
+//   EXH_E_CUT   exh_dist_recs of old records a and b: a new edge, two per move (none when L = n - 1: the segment's ends
+//               were neighbours already, and the rules above find their old edge).
+// Every case names an OLD EDGE between the two nodes or computes the distance, so the value is right whichever rule matches.
+// Positions past n are pads: copied (a = b = k).  A thread therefore needs old records a and b and old record n's eprev: three
+// loads whose addresses depend on the move alone, one round.
+enum : int { EXH_E_ZERO = 0, EXH_E_B = 1, EXH_E_A = 2, EXH_E_WRAP = 3, EXH_E_CUT = 4 };
+struct ExhPerm { int a, b, e; };
+TSP_EXH_HD ExhPerm exh_perm(int k, int n, int pa1, int L) {
+    if (k > n) return {k, k, EXH_E_B};
+    const int km = k == n ? 0 : k;
+    const int a = exh_mirror(km == 0 ? n - 1 : km - 1, n, pa1, L), b = exh_mirror(km, n, pa1, L);
+    int e = EXH_E_CUT;
+    if (k == 0) e = EXH_E_ZERO;
+    else if (b == (a + 1 == n ? 0 : a + 1)) e = b > 0 ? EXH_E_B : EXH_E_WRAP;
+    else if (a == (b + 1 == n ? 0 : b + 1)) e = a > 0 ? EXH_E_A : EXH_E_WRAP;
+    return {a, b, e};
+}
+
+template <int MODE, class Root>
+TSP_EXH_HD ExhRec exh_perm_rec(const ExhPerm &pm, const ExhRec &ra, const ExhRec &rb, int wrap_eprev, Root root) {
+    ExhRec r = rb;
+    r.eprev = pm.e == EXH_E_ZERO ? 0
+            : pm.e == EXH_E_B    ? rb.eprev
+            : pm.e == EXH_E_A    ? ra.eprev
+            : pm.e == EXH_E_WRAP ? wrap_eprev
+                                 : exh_dist_recs<MODE>(ra, rb, root);
+    return r;
 }
 
 // The strips of pair-columns, right-aligned: strip s holds the D-columns q0 .. q0 + weff of its wave and the pair-rows

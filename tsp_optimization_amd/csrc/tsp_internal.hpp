@@ -169,9 +169,15 @@ struct tsp_dev_tours {
     int cl_sorted_min_n = 8;         // ... the sorted scan (CLUSTER engine: ahead of its tiles scan from n = 52 up, tools/small_best.py)
     int sweep_blocks = 512;          // k_sweep blocks per tour
     int *d_cl_ticket = nullptr;      // k_sweep: arrival counters per tour x cluster
-    // exhaustive sweep in position order (two_opt_exh.hpp): the tour's row records and ids by position (padded)
-    tsp::ExhRec *d_prec = nullptr;
-    int *d_pid = nullptr;
+    // exhaustive sweep in position order (two_opt_exh.hpp): the tour's row records by position (padded), node id included.
+    // Two buffers: k_move_pos writes d_prec[exh_buf ^ 1] -- from d_prec[exh_buf] when exh_hot says that those are the records of
+    // the tour as it stands -- and the k_exh behind it reads what it wrote; the host flips exh_buf with the pair of launches.
+    // exh_hot is true only inside a run call that has queued an exhaustive pair (tsp_grid_run): between calls anything may
+    // move the tour (the flush carries out a pending move, other engines, an upload).
+    tsp::ExhRec *d_prec[2] = {nullptr, nullptr};
+    int exh_buf = 0;
+    bool exh_hot = false;
+    int *d_pid = nullptr;            // ... and the node ids by position, for k_exh
     int exh_share[4] = {0, 0, 0, 0};   // k_exh: rows per wave of each part of the grid (0: equal shares)
     int exh_gens = 0;                  // ... parts (= workgroups per CU)
     tsp::ExhDeal *d_exh_deal = nullptr;   // k_exh: where each wave of a tour's grid starts and how many row units it has (exh_deal)

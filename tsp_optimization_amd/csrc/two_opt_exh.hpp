@@ -19,13 +19,23 @@
 // Every delta is still computed exactly (integer-valued distances from the exact roots of tsp_dist.hpp's int_root).
 //
 // Layout.  k_move_pos (one thread per position) DECIDES the previous sweep's move -- every block for itself, from the
-// candidates k_exh left and the positions of their pairs beside them (sweep_decide, two_opt_step.hpp: pos is not read) --,
-// carries it out of place (as k_move_recs does)
-// and writes, in position order and padded: rec[p] = the record of u_p (exh_arith.hpp: -2x, -2y and the norm of its
-// coordinates relative to node 0, and e[p - 1]; position n repeats position 0; further pads lie far outside the instance),
-// pid[p] = u_p.
+// candidates k_exh left and the positions of their pairs beside them (sweep_load + sweep_reduce, two_opt_step.hpp: pos is not
+// read; the candidates are asked for together with the control block, one wait) --, carries it out of place (as k_move_recs
+// does) and writes, in position order and padded: rec[p] = the record of u_p (exh_arith.hpp: -2x, -2y and the norm of its
+// coordinates relative to node 0, e[p - 1], and u_p itself; position n repeats position 0; further pads lie far outside the
+// instance and carry the id -1), pid[p] = u_p once more, as the array k_exh reads its pairs' ids from.
+// Records by permutation.  A 2-opt move only permutes positions: but for the two cut points, the record of the new position k is
+// bit for bit an old record and its e is an old e (exh_perm, exh_arith.hpp; tests/test_cpu_exh_permute.py).  A tour has two
+// record buffers; k_move_pos<HOT> reads one and writes the other, the k_exh behind it reads what it wrote, the host flips
+// them with the pair of launches.  The chain of a hot launch is kernel arguments -> {control block, candidates} -> arg-min ->
+// old records -> stores: order, pos and coord are not read (order and pos are still written, for every other reader).  The
+// first sweep of a run call is cold (built from order and coord): only inside a run call does the host know that the old buffer
+// describes the tour (tsp_dev_tours::exh_hot).
 // Hand-off.  k_exh ends at its block's candidate and, from the lane that owns the winning key, (pos[i], pos[j]) of that pair in
-// an array parallel to the candidates: no counter, no last block.  No word is read and written by different blocks
+// an array parallel to the candidates: no counter, no last block.  (Measured and not kept: the ids of a lane's pair taken from
+// the records and kept in registers, so that k_exh ends without the loads of pid[bp] and pid[bq] -- four more VGPRs and their
+// moves at every strip start cost more than the round trip behind the last row saves: -1.5 %)
+// No word is read and written by different blocks
 // of one launch: a tour has two control blocks, k_move_pos reads slot s and its block 0 writes the advanced block to slot
 // s ^ 1; k_exh reads `done` there and one thread of it sets `open` there ("candidates written, not decided"), which nobody
 // else in that launch reads.  The host flips s per pair of launches; before it looks at a control block k_exh_close (one
@@ -116,14 +126,19 @@ __device__ __forceinline__ void exh_dist_row(const double (&cx)[RJ], const doubl
 }
 
 // (1) the move: the open sweep's, decided here by every block for itself, or a pending one (decided by k_exh_close); (2) that move,
-// out of place; (3) the tour AFTER it in position order: records and ids.  Reads the control block `states`, which no block of
+// out of place; (3) the tour AFTER it in position order: records (ids in them) and ids.  Reads the control block `states`, which no block of
 // this launch writes; block 0 writes the advanced one to `states_next` (the tour's other slot), which no block of this launch reads.
-template <int WT, bool INT>
+// HOT: `rec_old` holds the records of the tour BEFORE the move (the previous sweep's, written by the previous k_move_pos of the
+// same run call: the host knows, tsp_dev_tours::exh_hot) and the new ones are a permutation of them (exh_perm, exh_arith.hpp):
+// order, pos and coord are not read, no root is taken but at the move's two cut points, and the chain of the launch is
+// kernel arguments -> {control block, candidates} -> arg-min -> old records -> stores.  Otherwise (the first sweep of a run
+// call) the records are built from order and coord, two round trips more.
+template <int WT, bool INT, bool HOT>
 __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__restrict__ coord, int *orders, int *poss, int *orders2,
                                                            int *poss2, const TourState *__restrict__ states,
                                                            TourState *__restrict__ states_next, const Partial *__restrict__ partials,
                                                            const int2 *__restrict__ wpos, size_t partial_per_tour, int flat_slots,
-                                                           ExhRec *__restrict__ rec,
+                                                           const ExhRec *__restrict__ rec_old, ExhRec *__restrict__ rec,
                                                            int *__restrict__ pid, int n) {
     static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only (integer costs: the tour cost needs no staging)");
     __shared__ double s_d[kScanThreads / 64];
@@ -131,17 +146,29 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__rest
     const int tour = blockIdx.y;
     const TourState *st = states + tour;
     const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-    if (st->done) {   // a finished tour stays finished in both slots
+    // The candidates' addresses do not depend on the control block: both are asked for before either is used -- one wait.
+    // (A finished tour, or one without an open sweep, has loaded candidates it does not look at.)
+    const Partial *part = partials + (size_t)tour * partial_per_tour;
+    const int2 *wp = wpos + (size_t)tour * partial_per_tour;
+    const SweepLoads cand = sweep_load<true>(part, wp, flat_slots, threadIdx.x);
+    int done = st->done, is_open = st->open, parity = st->parity, pending = st->pending, mv_pa = st->mv_pa, mv_pb = st->mv_pb;
+    __builtin_amdgcn_sched_barrier(0);
+    // (and every kernel argument fetched by the entry's one batch of loads, not by batches of their own further down; the
+    // pointers only as a comparison, as at the head of k_exh)
+    const int args_null = (int)(coord == nullptr) | (int)(orders == nullptr) | (int)(poss == nullptr) | (int)(orders2 == nullptr) |
+                          (int)(poss2 == nullptr) | (int)(states_next == nullptr) | (int)(rec_old == nullptr) | (int)(rec == nullptr);
+    asm volatile("" : "+s"(done), "+s"(is_open), "+s"(parity), "+s"(pending), "+s"(mv_pa), "+s"(mv_pb) : "s"(n), "s"(args_null));
+    sweep_pin(cand);
+    if (done) {   // a finished tour stays finished in both slots
         if (writer) states_next[tour] = *st;
         return;
     }
     const size_t base = (size_t)tour * n, pbase = (size_t)tour * (n + kExhPad);
-    MoveView mv = move_view(st, orders + base, poss + base, orders2 + base, poss2 + base, n);
-    const bool open = st->open != 0;   // (then nothing is pending: mv.L == 0)
+    MoveView mv = move_view(parity, pending, mv_pa, mv_pb, orders + base, poss + base, orders2 + base, poss2 + base, n);
+    const bool open = is_open != 0;   // (then nothing is pending: mv.L == 0)
     SweepDecision dec;
     if (open) {
-        dec = sweep_decide(partials + (size_t)tour * partial_per_tour, wpos + (size_t)tour * partial_per_tour, flat_slots, mv.pos, n,
-                           s_d, s_k);   // the winner's positions came with its candidate: pos is not read
+        dec = sweep_reduce<true>(cand, part, wp, flat_slots, mv.pos, n, s_d, s_k);   // the winner's positions came with its candidate: pos is not read
         if (!dec.found) {   // the local optimum: block 0 recomputes the cost (tabusearch.c:168-172), nobody has records to build
             if (blockIdx.x != 0) return;
             const double cost = tour_cost_block<WT, INT>(coord, mv.order, mv.pos, n, s_d, nullptr);
@@ -157,23 +184,39 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__rest
     }
     const int k = blockIdx.x * kScanThreads + threadIdx.x;
     if (k >= n + kExhPad) return;
-    // every load of the current copy (which this kernel never writes) comes before the first store
-    const int u = k < n ? mv.node_at(k) : (k == n ? mv.node_at(0) : -1);
-    const int v = k >= 1 && k <= n ? mv.node_at(k - 1) : -1;   // the position before
-    const double2 c0 = coord[0];
-    double2 cu = make_double2(c0.x - 6.0e6, c0.y - 6.0e6);   // pads: farther from every node than any tour edge is long
-    int len = 0;
-    if (u >= 0) cu = coord[u];
-    if (v >= 0) { const double2 cv = coord[v]; len = (int)dist_xy<WT, INT>(cv.x, cv.y, cu.x, cu.y); }
+    int u;
+    ExhRec r;
+    if constexpr (HOT) {
+        // old records a and b and old record n's eprev (the closing edge): three loads whose addresses the move decides, in
+        // flight together; no thread, the two at the cut points included, waits a second time
+        const ExhRec *__restrict__ old = rec_old + pbase;
+        const ExhPerm pm = exh_perm(k, n, mv.pa1, mv.L);
+        const ExhRec ra = old[pm.a], rb = old[pm.b];
+        const int wrap = old[n].eprev;
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" : : "v"(ra.m2x), "v"(ra.m2y), "v"(ra.nrm), "v"(ra.eprev), "v"(rb.m2x), "v"(rb.m2y), "v"(rb.nrm),
+                     "v"(rb.eprev), "v"(rb.id), "v"(wrap));
+        r = exh_perm_rec<exh_mode<WT>()>(pm, ra, rb, wrap, [](double v) { return __builtin_amdgcn_sqrt(v); });
+        u = r.id;
+    } else {
+        // every load of the current copy (which this kernel never writes) comes before the first store
+        u = k < n ? mv.node_at(k) : (k == n ? mv.node_at(0) : -1);
+        const int v = k >= 1 && k <= n ? mv.node_at(k - 1) : -1;   // the position before
+        const double2 c0 = coord[0];
+        double2 cu = make_double2(c0.x - 6.0e6, c0.y - 6.0e6);   // pads: farther from every node than any tour edge is long
+        int len = 0;
+        if (u >= 0) cu = coord[u];
+        if (v >= 0) { const double2 cv = coord[v]; len = (int)dist_xy<WT, INT>(cv.x, cv.y, cu.x, cu.y); }
+        exh_rec_xy(cu.x - c0.x, cu.y - c0.y, r);   // exact: integers whose difference is below 2^21 (the pads: 6e6)
+        r.eprev = len;
+        r.id = u;
+    }
+    // order and pos stay current for every other reader (these stores are on nobody's path)
     if (mv.L > 0 && k < n) {
-        int *o_new = (st->parity ? orders : orders2) + base, *p_new = (st->parity ? poss : poss2) + base;
+        int *o_new = (parity ? orders : orders2) + base, *p_new = (parity ? poss : poss2) + base;
         o_new[k] = u;
         p_new[u] = k;
     }
-    ExhRec r;
-    exh_rec_xy(cu.x - c0.x, cu.y - c0.y, r);   // exact: integers whose difference is below 2^21 (the pads: 6e6)
-    r.eprev = len;
-    r.pad_ = 0;
     rec[pbase + k] = r;
     pid[pbase + k] = u;
     if (writer) {   // the next control block: the sweep counted, the move carried out (the other copy is the current one now)
@@ -203,8 +246,9 @@ __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__res
     const size_t base = (size_t)tour * n;
     const bool second = st->parity != 0;
     const int *order = (second ? orders2 : orders) + base, *pos = (second ? poss2 : poss) + base;
-    const SweepDecision dec = sweep_decide(partials + (size_t)tour * partial_per_tour, wpos + (size_t)tour * partial_per_tour,
-                                           flat_slots, pos, n, s_d, s_k);
+    const Partial *part = partials + (size_t)tour * partial_per_tour;
+    const int2 *wp = wpos + (size_t)tour * partial_per_tour;
+    const SweepDecision dec = sweep_reduce<true>(sweep_load<true>(part, wp, flat_slots, threadIdx.x), part, wp, flat_slots, pos, n, s_d, s_k);
     double cost = 0.0;
     if (!dec.found) cost = tour_cost_block<WT, INT>(coord, order, pos, n, s_d, nullptr);
     if (threadIdx.x == 0) {

@@ -255,7 +255,7 @@ bool sorted_run(const tsp_dev_tours *t, int mode, const tsp_dev_tabu *tabu) {
 
 // BEST sweeps of this handle execute every delta expression through k_move_pos + k_exh (bounds off, integer-coordinate metric)
 bool exh_run(const tsp_dev_tours *t, int mode, const tsp_dev_tabu *tabu) {
-    return mode == TSP_2OPT_BEST && !tabu && t->exh_blocks > 0 && t->d_prec && t->inst->filter_margin > 1e299 &&
+    return mode == TSP_2OPT_BEST && !tabu && t->exh_blocks > 0 && t->d_prec[0] && t->inst->filter_margin > 1e299 &&
            (t->inst->wtype == WT_EUC_2D_ICOORD || t->inst->wtype == WT_CEIL_2D_ICOORD || t->inst->wtype == WT_ATT_ICOORD);
 }
 
@@ -295,8 +295,19 @@ int tabu_list_prepare(tsp_dev_tours *t, tsp_dev_tabu *tb, bool *usable, long lon
     return TSP_OK;
 }
 
+// Whoever queues exhaustive pairs (launch_step) holds one of these for as long as it does: the records of the last pair describe
+// the tour only until the caller stops -- false on entry, false again on every way out (tsp_dev_tours::exh_hot).
+struct ExhHotScope {
+    tsp_dev_tours *t;
+    explicit ExhHotScope(tsp_dev_tours *t_) : t(t_) { t->exh_hot = false; }
+    ~ExhHotScope() { t->exh_hot = false; }
+    ExhHotScope(const ExhHotScope &) = delete;
+    ExhHotScope &operator=(const ExhHotScope &) = delete;
+};
+
 // After sorted sweeps: pending move carried out, tour back in the first copy of order/pos.
 void launch_flush(tsp_dev_tours *t) {
+    t->exh_hot = false;   // a pending move is carried out in order / pos: the exhaustive sweep's records no longer describe the tour
     if (!t->d_order2) return;
     hipStream_t s = t->inst->ctx->stream;
     const dim3 g((t->n + 255) / 256, t->B);
@@ -367,14 +378,25 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
             TourState *cur = t->d_state;
             t->slot ^= 1;
             t->d_state = t->d_state_base + (size_t)t->slot * t->B;
-            hipLaunchKernelGGL((k_move_pos<WT, INT>), dim3((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B), dim3(kScanThreads), 0, s,
-                               t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2, cur, t->d_state, t->d_partial,
-                               t->d_exh_wpos, t->partial_per_tour, t->exh_blocks, t->d_prec, t->d_pid, t->n);
+            // the records likewise: read from one buffer (when it holds the records of the tour as it stands), written to the other
+            const ExhRec *rec_old = t->exh_hot ? t->d_prec[t->exh_buf] : nullptr;
+            t->exh_buf ^= 1;
+            ExhRec *rec_new = t->d_prec[t->exh_buf];
+            const dim3 gm((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B);
+            if (rec_old)
+                hipLaunchKernelGGL((k_move_pos<WT, INT, true>), gm, dim3(kScanThreads), 0, s, t->inst->d_coord, t->d_order, t->d_pos,
+                                   t->d_order2, t->d_pos2, cur, t->d_state, t->d_partial, t->d_exh_wpos, t->partial_per_tour,
+                                   t->exh_blocks, rec_old, rec_new, t->d_pid, t->n);
+            else
+                hipLaunchKernelGGL((k_move_pos<WT, INT, false>), gm, dim3(kScanThreads), 0, s, t->inst->d_coord, t->d_order, t->d_pos,
+                                   t->d_order2, t->d_pos2, cur, t->d_state, t->d_partial, t->d_exh_wpos, t->partial_per_tour,
+                                   t->exh_blocks, rec_old, rec_new, t->d_pid, t->n);
+            t->exh_hot = true;   // (tsp_grid_run takes it back when the call returns)
             a.states = t->d_state;
             a.flat_slots = t->exh_blocks;
             const dim3 g(t->exh_blocks, 1, t->B);
-            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, t->d_prec, t->d_pid,
-                               t->d_exh_deal, t->d_exh_wpos);
+            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, rec_new, t->d_pid, t->d_exh_deal,
+                               t->d_exh_wpos);
             return TSP_OK;
         }
     }
@@ -461,6 +483,10 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
                  double time_limit_s, int sync, int *all_done) {
     if (!t || (mode != TSP_2OPT_FIRST && mode != TSP_2OPT_BEST)) return TSP_DEV_E_ARG;
     if (!sync && max_steps < 0) return TSP_DEV_E_ARG;   // "until done" needs the polls of a synchronous run: it would queue launches forever
+    // The exhaustive sweep's records by permutation: the first pair of this call builds them from the coordinates, the later
+    // ones from their predecessor's; when the call returns nobody knows them any more (the flush may carry out a pending move).
+    // A poll inside the run keeps them: k_exh_close only records a pending move, which the next k_move_pos applies.
+    ExhHotScope exh_hot_scope(t);
     hipStream_t s = t->inst->ctx->stream;
     const double t0 = wall_s();
     if (tabu && (iter < 0 || tenure < 0)) tabu = nullptr;   // check_tenure answers 0 before it reads anything (tabusearch.c:84)
@@ -978,7 +1004,8 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
             t->exh_lds = std::min(65536, inst->ctx->lds_bytes / waves) - 1024;
         t->partial_per_tour = std::max(t->partial_per_tour, (size_t)t->exh_blocks);
         const size_t pn = (size_t)B * (inst->n + kExhPad);
-        TSP_HIP_TRY(hipMalloc(&t->d_prec, pn * sizeof(ExhRec)));
+        TSP_HIP_TRY(hipMalloc(&t->d_prec[0], pn * sizeof(ExhRec)));
+        TSP_HIP_TRY(hipMalloc(&t->d_prec[1], pn * sizeof(ExhRec)));
         TSP_HIP_TRY(hipMalloc(&t->d_pid, pn * sizeof(int)));
         {   // rows per wave for each of the `waves` equal parts of the grid (k_exh: the older a workgroup, the larger its share);
             // TSP_EXH_SHARES = per-cent figures (or "0": equal shares), the default measured on MI355X
@@ -1041,7 +1068,7 @@ void tsp_dev_tours_destroy(tsp_dev_tours *t) {
     (void)hipFree(t->d_state_base); (void)hipFree(t->d_partial); (void)hipFree(t->d_slot_evals); (void)hipFree(t->d_ticket); (void)hipFree(t->d_rec);
     (void)hipFree(t->d_gmax); (void)hipFree(t->d_order2); (void)hipFree(t->d_pos2); (void)hipFree(t->d_pairtab); (void)hipFree(t->d_cl_ticket);
     (void)hipFree(t->d_row_ticket); (void)hipFree(t->d_row_evals); (void)hipFree(t->d_row_slot);
-    (void)hipFree(t->d_prec); (void)hipFree(t->d_pid); (void)hipFree(t->d_exh_deal); (void)hipFree(t->d_exh_wpos);
+    (void)hipFree(t->d_prec[0]); (void)hipFree(t->d_prec[1]); (void)hipFree(t->d_pid); (void)hipFree(t->d_exh_deal); (void)hipFree(t->d_exh_wpos);
     (void)hipFree(t->d_cl_slots); (void)hipFree(t->d_cl_pairtab); (void)hipFree(t->d_cl_stats);
     (void)hipFree(t->d_chain); (void)hipHostFree(t->h_chain); (void)hipFree(t->d_order_snap); (void)hipFree(t->d_kick_result); (void)hipHostFree(t->h_kick_result); (void)hipHostFree(t->h_cl_err);
     (void)hipHostFree(t->h_state);
@@ -1147,6 +1174,7 @@ int tsp_dev_tours_run(tsp_dev_tours *t, int mode, int64_t max_steps, double time
 
 int tsp_dev_tours_time_scan(tsp_dev_tours *t, int reps, float *mean_ms, int64_t *evals_per_launch) {
     if (!t || reps < 1) return TSP_DEV_E_ARG;
+    ExhHotScope exh_hot_scope(t);   // (it queues exhaustive pairs itself, not through tsp_grid_run)
     TSP_HIP_TRY(hipSetDevice(t->inst->ctx->device));
     hipStream_t s = t->inst->ctx->stream;
     const int n = t->n;

@@ -4,6 +4,7 @@
 // Part of the GRID engine; included by two_opt_grid.hip only (one translation unit).
 #pragma once
 #include "two_opt_common.hpp"
+#include "exh_arith.hpp"
 
 #pragma clang fp contract(off)
 
@@ -83,27 +84,27 @@ __global__ __launch_bounds__(kApplyThreads) void k_tour_cost(const double2 *__re
 struct MoveView {
     const int *order, *pos;   // the current copy
     int n, pa1, L;            // pending reversal: positions pa1 .. pa1 + L - 1 (cyclic); L == 0: none
-    __device__ __forceinline__ int mirror(int p) const {
-        int t = p - pa1; if (t < 0) t += n;
-        if (t >= L) return p;
-        int q = pa1 + (L - 1 - t); if (q >= n) q -= n;
-        return q;
-    }
+    __device__ __forceinline__ int mirror(int p) const { return exh_mirror(p, n, pa1, L); }   // (exh_arith.hpp: the CPU tests it)
     __device__ __forceinline__ int node_at(int p) const { return order[mirror(p)]; }   // node at new position p
     __device__ __forceinline__ int pos_of(int v) const { return mirror(pos[v]); }       // the mirror is an involution
 };
 
-__device__ __forceinline__ MoveView move_view(const TourState *st, const int *o1, const int *p1, const int *o2,
-                                              const int *p2, int n) {
+// (from the control block's words, for a caller that has loaded them itself)
+__device__ __forceinline__ MoveView move_view(int parity, int pending, int mv_pa, int mv_pb, const int *o1, const int *p1,
+                                              const int *o2, const int *p2, int n) {
     MoveView m;
-    const bool second = st->parity != 0;
+    const bool second = parity != 0;
     m.order = second ? o2 : o1; m.pos = second ? p2 : p1; m.n = n;
     m.L = 0; m.pa1 = 0;
-    if (st->pending) {
-        int L = st->mv_pb - st->mv_pa; if (L < 0) L += n;
-        m.L = L; m.pa1 = st->mv_pa + 1 == n ? 0 : st->mv_pa + 1;
+    if (pending) {
+        int L = mv_pb - mv_pa; if (L < 0) L += n;
+        m.L = L; m.pa1 = mv_pa + 1 == n ? 0 : mv_pa + 1;
     }
     return m;
+}
+__device__ __forceinline__ MoveView move_view(const TourState *st, const int *o1, const int *p1, const int *o2,
+                                              const int *p2, int n) {
+    return move_view(st->parity, st->pending, st->mv_pa, st->mv_pb, o1, p1, o2, p2, n);
 }
 
 // ---- the decision of a sweep whose block candidates a FINISHED launch has left in memory ----------------------
@@ -116,45 +117,68 @@ __device__ __forceinline__ MoveView move_view(const TourState *st, const int *o1
 // The reduction order differs from apply_step's; the arg-min with a strict tie-break does not depend on it.  Two slots may
 // hold the same pair (k_exh: strip 0 overlaps strip 1): they hold the same positions.  s_d, s_k: >= kScanThreads / 64
 // entries each.
+// Two halves.  The candidates' addresses depend on the thread alone, so a caller with loads of its own to wait for (k_move_pos:
+// the control block) issues sweep_load first and lets both travel together; sweep_reduce is everything behind the wait.
 struct SweepDecision {
     int found = 0, i = -1, j = -1;   // found == 0: local optimum (i = j = -1)
     int pa = 0, pb = 0, L = 0;       // pos[i], pos[j]; reverse positions pa + 1 .. pb (cyclic), L = (pb - pa) mod n of them
 };
 
-__device__ __forceinline__ SweepDecision sweep_decide(const Partial *__restrict__ part, const int2 *__restrict__ wpos, int nslots,
-                                                      const int *__restrict__ pos, int n, double *s_d, u64 *s_k) {
+constexpr int kDecidePU = 8;   // 2 048 candidates = 8 per thread: one round
+struct SweepLoads { Partial p[kDecidePU]; int2 w[kDecidePU]; };
+
+// one round of a thread's loads: slots s0, s0 + kScanThreads, ... (s0 = threadIdx.x for the first round).
+// WPOS: the caller always has the array of positions (the exhaustive sweep) -- no test per load, no path through pos.
+template <bool WPOS = false>
+__device__ __forceinline__ SweepLoads sweep_load(const Partial *__restrict__ part, const int2 *__restrict__ wpos, int nslots, int s0) {
+    SweepLoads l;
+#pragma unroll
+    for (int k = 0; k < kDecidePU; ++k) {
+        const int s = s0 + k * kScanThreads;
+        l.p[k].delta = 0.0; l.p[k].i = -1; l.p[k].j = -1;
+        l.w[k] = make_int2(0, 0);
+        if (s < nslots) {
+            l.p[k] = part[s];
+            if (WPOS || wpos) l.w[k] = wpos[s];
+        }
+    }
+    return l;
+}
+
+// keeps the loads of a round where they were issued: to be called behind the caller's own loads and a scheduling barrier,
+// before the first use of any of them (the device k_exh starts its strips with)
+__device__ __forceinline__ void sweep_pin(const SweepLoads &l) {
+#pragma unroll
+    for (int k = 0; k < kDecidePU; ++k)
+        asm volatile("" : : "v"(l.p[k].delta), "v"(l.p[k].i), "v"(l.p[k].j), "v"(l.w[k].x), "v"(l.w[k].y));
+}
+
+// `first`: the round sweep_load(part, wpos, nslots, threadIdx.x) fetched; further rounds (nslots > 2 048) are fetched here
+template <bool WPOS = false>
+__device__ __forceinline__ SweepDecision sweep_reduce(const SweepLoads &first, const Partial *__restrict__ part,
+                                                      const int2 *__restrict__ wpos, int nslots, const int *__restrict__ pos, int n,
+                                                      double *s_d, u64 *s_k) {
     __shared__ int2 s_wpos;
     const int tid = threadIdx.x;
     double bd = 0.0;
     u64 key = kNoKey;
     int2 bw = make_int2(0, 0);
-    constexpr int PU = 8;   // 2 048 candidates = 8 per thread: one round
-    for (int s0 = tid; s0 < nslots; s0 += PU * kScanThreads) {
-        Partial p[PU];
-        int2 w[PU];
+    auto fold = [&](const SweepLoads &l) {
 #pragma unroll
-        for (int k = 0; k < PU; ++k) {
-            const int s = s0 + k * kScanThreads;
-            p[k].delta = 0.0; p[k].i = -1; p[k].j = -1;
-            w[k] = make_int2(0, 0);
-            if (s < nslots) {
-                p[k] = part[s];
-                if (wpos) w[k] = wpos[s];
-            }
+        for (int k = 0; k < kDecidePU; ++k) {
+            const u64 kk = make_key(l.p[k].i, l.p[k].j);
+            if (better(l.p[k].delta, kk, bd, key)) { bd = l.p[k].delta; key = kk; bw = l.w[k]; }
         }
-#pragma unroll
-        for (int k = 0; k < PU; ++k) {
-            const u64 kk = make_key(p[k].i, p[k].j);
-            if (better(p[k].delta, kk, bd, key)) { bd = p[k].delta; key = kk; bw = w[k]; }
-        }
-    }
+    };
+    fold(first);
+    for (int s0 = tid + kDecidePU * kScanThreads; s0 < nslots; s0 += kDecidePU * kScanThreads) fold(sweep_load<WPOS>(part, wpos, nslots, s0));
     const u64 mine = key;
     block_argmin<true>(bd, key, s_d, s_k);
     SweepDecision d;
     d.found = key != kNoKey && bd < 0;   // (block-uniform)
     if (d.found) {
         d.i = key_i(key); d.j = key_j(key);
-        if (wpos) {
+        if (WPOS || wpos) {
             if (mine == key) s_wpos = bw;   // every owner of the key holds the same pair of positions
             __syncthreads();
             d.pa = s_wpos.x; d.pb = s_wpos.y;
@@ -164,6 +188,12 @@ __device__ __forceinline__ SweepDecision sweep_decide(const Partial *__restrict_
         d.L = d.pb - d.pa; if (d.L < 0) d.L += n;
     }
     return d;
+}
+
+// the two halves back to back
+__device__ __forceinline__ SweepDecision sweep_decide(const Partial *__restrict__ part, const int2 *__restrict__ wpos, int nslots,
+                                                      const int *__restrict__ pos, int n, double *s_d, u64 *s_k) {
+    return sweep_reduce(sweep_load(part, wpos, nslots, threadIdx.x), part, wpos, nslots, pos, n, s_d, s_k);
 }
 
 // What apply_step's thread 0 adds to the control block for one exhaustive sweep, at the moment the sweep is decided; without a
