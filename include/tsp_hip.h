@@ -143,6 +143,11 @@ int tsp_dev_selftest_raw_sqrt(tsp_dev_ctx *ctx, const double *in, int count, dou
 int tsp_dev_construct(tsp_dev_inst *inst, int kind, int B, const int *starts, const double *urand,
                       int *succ, int succ_stride, int64_t tour_stride, double *obj, int *status_out);
 
+/* One line of text in buf naming the kernel (and its variant) that tsp_dev_construct launches for this instance and kind under the
+ * switches the instance was created with: "k_construct_nn<float2, packed>", "k_construct_nn_big<double2, generic>",
+ * "k_construct_lds", "k_construct" (tests check that an input reached the path they mean to test). */
+int tsp_dev_construct_describe(tsp_dev_inst *inst, int kind, char *buf, int cap);
+
 /* HEU_extramileage (src/heuristics.c:208-314): farthest pair, then cheapest insertion of every other
  * node; writes the successor list and the reference's obj (2*d(A,B) + the sum of the extra mileages). */
 int tsp_dev_extramileage(tsp_dev_inst *inst, int *succ, int succ_stride, double *obj);

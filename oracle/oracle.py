@@ -57,6 +57,7 @@ def lib():
         L.orc_greedy_iter.argtypes = [dp, C.c_int, C.c_int, C.c_int, ip, dp]
         L.orc_grasp_iter_prefix.argtypes = [dp, C.c_int, C.c_int, C.c_int, C.c_longlong, ip, dp, C.POINTER(C.c_longlong)]
         L.orc_extramileage.argtypes = [dp, C.c_int, C.c_int, C.c_int, ip, dp]
+        L.orc_extramileage_fast.argtypes = [dp, C.c_int, C.c_int, C.c_int, ip, dp]
         L.orc_two_opt_first.argtypes = [dp, C.c_int, C.c_int, C.c_int, ip, dp, C.c_double, C.c_int,
                                         C.POINTER(Stats), C.POINTER(Move), C.c_longlong]
         L.orc_two_opt_first_moves.argtypes = [dp, C.c_int, C.c_int, C.c_int, ip, dp, C.c_longlong, C.POINTER(Stats)]
@@ -174,6 +175,16 @@ def extramileage(xy, wtype, integer_cost=1):
     succ = np.zeros(n, dtype=np.int32)
     obj = C.c_double(0)
     st = lib().orc_extramileage(_d(xy), n, wtype, integer_cost, _i(succ), C.byref(obj))
+    return st, succ, obj.value
+
+
+def extramileage_fast(xy, wtype, integer_cost=1):
+    """extramileage() bit for bit, without its O(n^3) loop"""
+    xy = _xy(xy)
+    n = len(xy)
+    succ = np.zeros(n, dtype=np.int32)
+    obj = C.c_double(0)
+    st = lib().orc_extramileage_fast(_d(xy), n, wtype, integer_cost, _i(succ), C.byref(obj))
     return st, succ, obj.value
 
 

@@ -235,6 +235,65 @@ int orc_extramileage(const double *xy, int n, int wtype, int integer_cost, int *
     return ORC_OK;
 }
 
+/* orc_extramileage with the same decisions in O(n^2) plus the rescans: every node outside the tour keeps its cheapest
+ * (extra, slot), the first slot among equals as the strict '<' of the slot loop leaves it (src/heuristics.c:262-280).  An
+ * insertion changes two slots: the replaced one, j, and the appended one.  A node whose cheapest slot was j is scanned again over
+ * every slot; any other node keeps its value over the unchanged slots and is compared with the two new ones -- j wins an exact
+ * tie only when it lies before the node's slot, the appended slot (the last) needs strictly less.  The node picked is the first
+ * among the cheapest (the node loop is the outer one).  Every extra is the same expression on the same operands as in
+ * orc_extramileage, so tours and costs are equal bit for bit; tests/test_cpu_construct_ref.py holds the two against each other. */
+int orc_extramileage_fast(const double *xy, int n, int wtype, int integer_cost, int *succ, double *obj) {
+    char *in_tour = calloc((size_t)n, 1);
+    int *from = calloc((size_t)n, sizeof(int)), *to = calloc((size_t)n, sizeof(int)), *best_slot = calloc((size_t)n, sizeof(int));
+    double *best_extra = calloc((size_t)n, sizeof(double));
+    memset(succ, 0, sizeof(int) * (size_t)n);
+    int far_a = 0, far_b = 1;
+    double far_d = 0.0;
+    for (int i = 0; i < n; i++)
+        for (int j = i + 1; j < n; j++) {
+            double d = orc_dist(xy, i, j, wtype, integer_cost);
+            if (d > far_d) { far_a = i; far_b = j; far_d = d; }
+        }
+    int m = 0;
+    from[m] = far_a; to[m] = far_b; m++;
+    from[m] = far_b; to[m] = far_a; m++;
+    succ[far_a] = far_b; succ[far_b] = far_a;
+    in_tour[far_a] = in_tour[far_b] = 1;
+    double total = 2 * orc_dist(xy, far_a, far_b, wtype, integer_cost);
+#define ORC_EXTRA(c, s) (orc_dist(xy, from[s], (c), wtype, integer_cost) + orc_dist(xy, (c), to[s], wtype, integer_cost) \
+                         - orc_dist(xy, from[s], to[s], wtype, integer_cost))
+#define ORC_RESCAN(c) do { best_extra[c] = DBL_MAX; best_slot[c] = -1;                                   \
+        for (int s_ = 0; s_ < m; s_++) { const double e_ = ORC_EXTRA(c, s_);                              \
+            if (e_ < best_extra[c]) { best_extra[c] = e_; best_slot[c] = s_; } } } while (0)
+    for (int c = 0; c < n; c++) if (!in_tour[c]) ORC_RESCAN(c);
+    while (m < n) {
+        double low = DBL_MAX;
+        int pick_node = -1;
+        for (int c = 0; c < n; c++)
+            if (!in_tour[c] && best_slot[c] >= 0 && best_extra[c] < low) { low = best_extra[c]; pick_node = c; }
+        if (pick_node < 0) break;
+        const int j = best_slot[pick_node], a = from[j], b = to[j];
+        succ[a] = pick_node; succ[pick_node] = b;
+        to[j] = pick_node;
+        from[m] = pick_node; to[m] = b; m++;
+        in_tour[pick_node] = 1;
+        total += low;
+        for (int c = 0; c < n; c++) {
+            if (in_tour[c]) continue;
+            if (best_slot[c] == j) { ORC_RESCAN(c); continue; }
+            const double ej = ORC_EXTRA(c, j);
+            if (ej < best_extra[c] || (ej == best_extra[c] && j < best_slot[c])) { best_extra[c] = ej; best_slot[c] = j; }
+            const double em = ORC_EXTRA(c, m - 1);
+            if (em < best_extra[c]) { best_extra[c] = em; best_slot[c] = m - 1; }
+        }
+    }
+#undef ORC_RESCAN
+#undef ORC_EXTRA
+    *obj = total;
+    free(in_tour); free(from); free(to); free(best_slot); free(best_extra);
+    return ORC_OK;
+}
+
 /* ---- 2-opt ----------------------------------------------------------------------------- */
 
 static void rebuild_prev(int n, const int *succ, int *prev) {

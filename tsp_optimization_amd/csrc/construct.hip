@@ -630,6 +630,45 @@ __global__ __launch_bounds__(256) void k_dist_matrix(const double2 *__restrict__
     }
 }
 
+// ---- which kernel a construction runs ------------------------------------------------------------------------------
+// Decided in one place, for tsp_dev_construct and for tsp_dev_construct_describe (tests assert the path they mean to cover).
+enum ConsPath { CONS_NN, CONS_NN_BIG, CONS_LDS, CONS_GLOBAL };
+struct ConstructPlan {
+    ConsPath path;
+    bool float_xy;      // spatial kernels: float2 coordinates relative to the instance's corner (bounded integers), else double2
+    bool pack;          // spatial kernels: one 64-bit (distance, id, slot) key per candidate
+    size_t lds_bytes;   // dynamic LDS of the launch (0 for k_construct)
+};
+
+static ConstructPlan construct_plan(const tsp_dev_inst *inst, int kind) {
+    ConstructPlan p;
+    // greedy on a sqrt metric with the Hilbert groups at hand: the spatial kernel, one wave per start
+    const bool nn_off = TSP_SW(inst, CONSTRUCT_NN, 1) == 0;
+    const bool icoord = inst->wtype == WT_EUC_2D_ICOORD || inst->wtype == WT_CEIL_2D_ICOORD || inst->wtype == WT_ATT_ICOORD;
+    const size_t need = icoord ? nn_lds_bytes<float2>(inst->n_slots, inst->ng) : nn_lds_bytes<double2>(inst->n_slots, inst->ng);
+    const bool small = inst->ng <= 64 * kNnMaxRounds && need <= (size_t)158 * 1024;
+    // larger instances: coordinates stay in HBM/L2, LDS holds the alive masks and float boxes (k_construct_nn_big)
+    const size_t need_big = (sizeof(float4) + sizeof(unsigned long long)) * (size_t)inst->ng + 64;
+    const bool big = !small && inst->ng <= 4096 && need_big <= (size_t)158 * 1024;
+    // greedy: both kernels; grasp (its runner-up is one more query with an id limit): the LDS-resident one
+    const bool use_nn = inst->d_sperm && !nn_off && (small || (big && kind == TSP_CONSTRUCT_GREEDY));
+    // one 64-bit key per candidate when the costs are integers and ids/slots fit their fields
+    const bool pack = inst->integer_cost && (small ? (inst->n_slots <= 32768 && inst->cost_bound < 2147483647.0)
+                                                   : (inst->n_slots <= 262144 && inst->cost_bound < 268435455.0));
+    p.float_xy = icoord;
+    p.pack = pack;
+    if (use_nn) {
+        p.path = small ? CONS_NN : CONS_NN_BIG;
+        p.lds_bytes = small ? need : need_big;
+        return p;
+    }
+    const size_t lds_bytes = 4 * (kConsLdsThreads / 64) * sizeof(ConsSlot) + sizeof(double2) * (size_t)inst->n;
+    const bool use_lds = TSP_SW(inst, CONSTRUCT_GLOBAL, 0) != 1 && inst->n <= kConsLdsMaxN && lds_bytes <= (size_t)160 * 1024;
+    p.path = use_lds ? CONS_LDS : CONS_GLOBAL;
+    p.lds_bytes = use_lds ? lds_bytes : 0;
+    return p;
+}
+
 }  // namespace tsp
 
 using namespace tsp;
@@ -668,21 +707,10 @@ int tsp_dev_construct(tsp_dev_inst *inst, int kind, int B, const int *starts, co
     TSP_HIP_TRY(hipMemsetAsync(d_succ, 0, sizeof(int) * bn, s));  // CALLOC'd edges, solver.c:270
     if (grasp_call)
         TSP_HIP_TRY(hipMemcpyAsync(d_urand.p, urand, sizeof(double) * bn, hipMemcpyHostToDevice, s));
-    // greedy on a sqrt metric with the Hilbert groups at hand: the spatial kernel, one wave per start
-    bool use_nn = false;
+    const ConstructPlan plan = construct_plan(inst, kind);
+    const bool use_nn = plan.path == CONS_NN || plan.path == CONS_NN_BIG;
     {
-        const bool nn_off = TSP_SW(inst, CONSTRUCT_NN, 1) == 0;
-        const bool icoord = inst->wtype == tsp::WT_EUC_2D_ICOORD || inst->wtype == tsp::WT_CEIL_2D_ICOORD || inst->wtype == tsp::WT_ATT_ICOORD;
-        const size_t need = icoord ? nn_lds_bytes<float2>(inst->n_slots, inst->ng) : nn_lds_bytes<double2>(inst->n_slots, inst->ng);
-        const bool small = inst->ng <= 64 * kNnMaxRounds && need <= (size_t)158 * 1024;
-        // larger instances: coordinates stay in HBM/L2, LDS holds the alive masks and float boxes (k_construct_nn_big)
-        const size_t need_big = (sizeof(float4) + sizeof(unsigned long long)) * (size_t)inst->ng + 64;
-        const bool big = !small && inst->ng <= 4096 && need_big <= (size_t)158 * 1024;
-        // greedy: both kernels; grasp (its runner-up is one more query with an id limit): the LDS-resident one
-        use_nn = inst->d_sperm && !nn_off && (small || (big && kind == TSP_CONSTRUCT_GREEDY));
-        // one 64-bit key per candidate when the costs are integers and ids/slots fit their fields
-        const bool pack = inst->integer_cost && (small ? (inst->n_slots <= 32768 && inst->cost_bound < 2147483647.0)
-                                                       : (inst->n_slots <= 262144 && inst->cost_bound < 268435455.0));
+        const bool small = plan.path == CONS_NN, pack = plan.pack;
         if (use_nn) {
             std::vector<int> slots((size_t)B, 0);
             for (int b = 0; b < B; ++b) if (starts[b] >= 0 && starts[b] < n) slots[b] = inst->h_sinv[starts[b]];
@@ -698,8 +726,8 @@ int tsp_dev_construct(tsp_dev_inst *inst, int kind, int B, const int *starts, co
                         const bool grasp = kind == TSP_CONSTRUCT_GRASP;
                         auto kf = grasp ? (pack ? k_construct_nn<WTC, INTC, CT, true, true> : k_construct_nn<WTC, INTC, CT, false, true>)
                                         : (pack ? k_construct_nn<WTC, INTC, CT, true, false> : k_construct_nn<WTC, INTC, CT, false, false>);
-                        e_nn = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-                        hipLaunchKernelGGL(kf, dim3(B), dim3(64), need, s, inst->d_coord, inst->d_sperm, inst->d_gbox, n, inst->ng,
+                        e_nn = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+                        hipLaunchKernelGGL(kf, dim3(B), dim3(64), plan.lds_bytes, s, inst->d_coord, inst->d_sperm, inst->d_gbox, n, inst->ng,
                                            inst->n_slots, ox, oy, d_starts, d_slots, (const double *)d_urand.p, d_succ, d_obj, d_status);
                     } else {
                         if (!inst->d_sxy) {   // rank-ordered coordinates, once per instance
@@ -710,8 +738,8 @@ int tsp_dev_construct(tsp_dev_inst *inst, int kind, int B, const int *starts, co
                         }
                         if (e_nn == hipSuccess) {
                             auto kf = pack ? k_construct_nn_big<WTC, INTC, CT, true> : k_construct_nn_big<WTC, INTC, CT, false>;
-                            e_nn = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need_big);
-                            hipLaunchKernelGGL(kf, dim3(B), dim3(64), need_big, s, (const CT *)inst->d_sxy, inst->d_sperm, inst->d_gbox, n,
+                            e_nn = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+                            hipLaunchKernelGGL(kf, dim3(B), dim3(64), plan.lds_bytes, s, (const CT *)inst->d_sxy, inst->d_sperm, inst->d_gbox, n,
                                                inst->ng, ox, oy, d_starts, d_slots, d_succ, d_obj, d_status);
                         }
                     }
@@ -720,20 +748,19 @@ int tsp_dev_construct(tsp_dev_inst *inst, int kind, int B, const int *starts, co
             TSP_HIP_TRY(e_nn);
         }
     }
-    const size_t lds_bytes = 4 * (kConsLdsThreads / 64) * sizeof(ConsSlot) + sizeof(double2) * (size_t)n;
-    const bool use_lds = TSP_SW(inst, CONSTRUCT_GLOBAL, 0) != 1 && n <= kConsLdsMaxN && lds_bytes <= (size_t)160 * 1024;
+    const bool use_lds = plan.path == CONS_LDS;
     hipError_t attr_err = hipSuccess;
     if (!use_nn) TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         if (use_lds) {
             if (kind == TSP_CONSTRUCT_GRASP) {
                 auto kf = k_construct_lds<WTC, INTC, true>;
-                attr_err = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                hipLaunchKernelGGL(kf, dim3(B), dim3(kConsLdsThreads), lds_bytes, s, inst->d_coord, n, d_starts, d_urand.p,
+                attr_err = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+                hipLaunchKernelGGL(kf, dim3(B), dim3(kConsLdsThreads), plan.lds_bytes, s, inst->d_coord, n, d_starts, d_urand.p,
                                    d_succ, d_obj, d_status);
             } else {
                 auto kf = k_construct_lds<WTC, INTC, false>;
-                attr_err = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                hipLaunchKernelGGL(kf, dim3(B), dim3(kConsLdsThreads), lds_bytes, s, inst->d_coord, n, d_starts,
+                attr_err = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+                hipLaunchKernelGGL(kf, dim3(B), dim3(kConsLdsThreads), plan.lds_bytes, s, inst->d_coord, n, d_starts,
                                    (const double *)nullptr, d_succ, d_obj, d_status);
             }
         } else if (kind == TSP_CONSTRUCT_GRASP)
@@ -758,6 +785,17 @@ int tsp_dev_construct(tsp_dev_inst *inst, int kind, int B, const int *starts, co
         for (int v = 0; v < n; ++v) sp[(size_t)v * succ_stride] = h_succ[(size_t)b * n + v];
     }
     return (B == 1) ? worst : TSP_OK;
+}
+
+int tsp_dev_construct_describe(tsp_dev_inst *inst, int kind, char *buf, int cap) {
+    if (!inst || !buf || cap < 1 || (kind != TSP_CONSTRUCT_GREEDY && kind != TSP_CONSTRUCT_GRASP)) return TSP_DEV_E_ARG;
+    const ConstructPlan p = construct_plan(inst, kind);
+    if (p.path == CONS_NN || p.path == CONS_NN_BIG)
+        snprintf(buf, (size_t)cap, "%s<%s, %s>", p.path == CONS_NN ? "k_construct_nn" : "k_construct_nn_big",
+                 p.float_xy ? "float2" : "double2", p.pack ? "packed" : "generic");
+    else
+        snprintf(buf, (size_t)cap, "%s", p.path == CONS_LDS ? "k_construct_lds" : "k_construct");
+    return TSP_OK;
 }
 
 int tsp_dev_dist_matrix(tsp_dev_inst *inst, void *out_host, int as_int32, float *kernel_ms) {
