@@ -590,6 +590,31 @@ int tsp_dev_inst_alpha_build(tsp_dev_inst *inst, int K, const double *pi, double
  * index out of range or a penalty that is not finite: TSP_DEV_E_ARG as above.  The handle's lists are left alone. */
 int tsp_dev_alpha_rows(tsp_dev_inst *inst, const double *pi, int m, const int *rows, double *out);
 
+/* ---- greedy-edge construction (extension; Bentley, Johnson & McGeoch: the customary start of 2-opt, 3-opt and LK codes) --------
+ * (DESIGN.md 4.17 has the kernels.)  d(i,j) is the value tsp_dev_dist_pairs returns, taken with the lower node id first.
+ * Edge order: lexicographic on (d, lo, hi), lo = min, hi = max -- the Held-Karp section's order with pi = 0, a strict total order.
+ * Greedy edge, n >= 3: all n(n-1)/2 edges are walked in that order; {u,v} is accepted iff both nodes have degree < 2 and they are
+ * not the two ends of one fragment (the accepted edges always form paths).  After n - 1 accepted edges the one Hamiltonian path
+ * is closed by the edge between its two ends.
+ * Output.  edges: the n - 1 accepted edges as pairs (lo, hi), sorted by (lo, hi); the closing edge is not among them.  The tour:
+ * a successor list oriented so that succ[0] is the smaller-id one of node 0's two tour neighbours.  obj: the recomputed cost,
+ * the sum over nodes in node order of d(v, succ v) as in every section above.  No floating-point atomics: two runs return the
+ * same bits.  The device builds the same edge set in rounds (each fragment joins along its smallest valid edge when the fragment
+ * at the other end agrees), not by sorting. */
+typedef struct {
+    int64_t rounds;             /* rounds carried out (at most n - 1: every round accepts an edge)                          */
+    int64_t edges;              /* accepted edges: n - 1                                                                    */
+    int64_t rows_scanned;       /* rows (free nodes) whose smallest valid edge was looked for, over all rounds: only rows
+                                   whose cached edge had become invalid are scanned again                                   */
+    int64_t dists_executed;     /* distances the scans evaluated (lanes of the waves that scanned x n columns)              */
+    int64_t max_edges_in_round; /* most edges accepted by one round                                                         */
+    double seconds;             /* wall time of the call, host clock                                                        */
+    double device_ms;           /* device time of the call, HIP events on the engine's stream                               */
+} tsp_greedy_edge_stats;
+/* succ: n ints, succ_stride ints apart; edges: 2(n - 1) ints; each output may be NULL.  No instance, n < 3 or a stride below 1:
+ * TSP_DEV_E_ARG, and the outputs are untouched.  There is no CPU fallback. */
+int tsp_dev_greedy_edge(tsp_dev_inst *inst, int *succ, int succ_stride, double *obj, int *edges, tsp_greedy_edge_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,14 @@ int tsp_host_set_dlb(int mode);
  * TSP_HK_DEFAULT_ITERS, time_lim <= 0 = unlimited.  Returns the bound (valid also when the time limit ended the ascent). */
 double tsp_host_lower_bound(instance *inst, double ub, int max_iters, double time_lim);
 
+/* ---- greedy-edge construction (extension; include/tsp_hip.h, tsp_dev_greedy_edge).  Library entry points only: no
+ * solver_type, no -method row. */
+int HEU_greedy_edge(instance *inst);       /* the greedy-edge tour into inst->solution, its recomputed cost into obj_best, as
+                                              HEU_extramileage leaves its tour                                               */
+int HEU_2opt_greedy_edge(instance *inst);  /* HEU_greedy_edge + alg_2opt   */
+int HEU_nl_greedy_edge(instance *inst);    /* HEU_greedy_edge + alg_nl_opt */
+int HEU_ils_greedy_edge(instance *inst);   /* HEU_greedy_edge + alg_ils    */
+
 /* ---- src/tabusearch.c (externally linked there, not in its header) --------------------------- */
 int alg_2opt_tabu(instance *inst, int *skip_edge, int *stored_prev, const int iter, const int tenure); /* :107 */
 
@@ -284,6 +292,8 @@ void tsp_host_last_ils_stats(tsp_ils_stats *out);
 void tsp_host_last_dlb_stats(int64_t *active_nodes, int64_t *closing_scans);
 /* Counters of the last tsp_host_lower_bound call of this thread. */
 void tsp_host_last_lb_stats(tsp_lb_stats *out);
+/* Counters of the last HEU_greedy_edge call of this thread (also through HEU_2opt_ / HEU_nl_ / HEU_ils_greedy_edge). */
+void tsp_host_last_greedy_edge_stats(tsp_greedy_edge_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */
 void tsp_host_shutdown(void);
 

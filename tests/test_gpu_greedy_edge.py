@@ -1,0 +1,231 @@
+"""GPU: the greedy-edge construction on the device (tsp_dev_greedy_edge, HEU_greedy_edge and the descents behind it) against the
+CPU references of the definition (tests/greedy_edge_ref.py).  The construction is decision-exact: the accepted edges, the
+successor list and its orientation equal the sort-and-walk reference's; the cost equals the reference cost exactly for integer
+costs and to 1e-12 relative otherwise (summation order)."""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import greedy_edge_ref as G
+import held_karp_ref as HK
+from helpers import INSTANCES, Instance, HostInstance, rand_instance
+from oracle import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from tsp_optimization_amd import engine as E
+    assert E.device_count() >= 1
+    return E
+
+
+@pytest.fixture(scope="module")
+def ctx(eng):
+    c = eng.Context(0)
+    yield c
+    c.close()
+
+
+@functools.lru_cache(maxsize=None)
+def load(name):
+    made = {"grid30": lambda: G.tie_grid(30, 4), "grid400": lambda: G.tie_grid(400, 20), "collinear200": lambda: G.collinear(200),
+            "coincident64": lambda: G.coincident(64), "n3": lambda: G.small(3), "n4": lambda: G.small(4), "n5": lambda: G.small(5),
+            "rand257": lambda: rand_instance(257), "rand4097": lambda: rand_instance(4097)}
+    if name in made:
+        return made[name](), O.EUC_2D
+    return O.parse_tsplib(os.path.join(INSTANCES, name + ".tsp"))
+
+
+# the six metrics x both integer_cost settings; MAX_2D and MAN_2D (which no fixture names) on berlin52's coordinates.  rand257 is
+# one past a workgroup; rand4097 is one past the size at which the scan's 32 chunks are 128 columns each: odd chunks of 129, a short
+# last one, and more than one workgroup of rows.
+CASES = [("burma14", None), ("ulysses22", None), ("att48", None), ("berlin52", None), ("berlin52", O.MAX_2D), ("berlin52", O.MAN_2D),
+         ("dsj1000", None), ("pr1002", None), ("grid30", None), ("grid400", None), ("collinear200", None), ("coincident64", None),
+         ("n3", None), ("n4", None), ("n5", None), ("rand257", None), ("rand4097", None)]
+UNIFORM = ("rand257", "rand4097")
+
+
+def check_stats(st, n, uniform, what):
+    print("%s: %d rounds, %.2f n rows scanned, %.3g distances, at most %d edges in a round, %.2f ms on the device"
+          % (what, st["rounds"], st["rows_scanned"] / n, st["dists_executed"], st["max_edges_in_round"], st["device_ms"]))
+    assert st["edges"] == n - 1, what
+    assert 1 <= st["rounds"] <= n - 1, what
+    assert st["rows_scanned"] >= n, what
+    assert st["dists_executed"] >= st["rows_scanned"] * (n - 2), what
+    assert 1 <= st["max_edges_in_round"] <= n - 1, what
+    if uniform:
+        assert st["rows_scanned"] <= 6 * n, what   # the stale-only rule (the CPU simulation: 2.7 - 2.8 n); a rescan of every row per round is rounds x n
+
+
+def check_result(got, ref, integer_cost, what):
+    succ, obj, edges = got[:3]
+    re_, rs, rc = ref[:3]
+    print("%s: cost %.6f (reference %.6f)" % (what, obj, rc))
+    assert edges.shape == re_.shape and (edges == re_).all(), what
+    assert (succ == rs).all(), what
+    pred0 = int(np.flatnonzero(succ == 0)[0])
+    assert succ[0] <= pred0, what
+    if integer_cost:
+        assert obj == rc, (what, obj, rc)
+    else:
+        assert abs(obj - rc) <= 1e-12 * abs(rc), (what, obj, rc)
+
+
+@pytest.mark.parametrize("integer_cost", [1, 0])
+@pytest.mark.parametrize("name,wt_as", CASES)
+def test_greedy_edge_is_decision_exact(eng, ctx, name, wt_as, integer_cost):
+    xy, wt = load(name)
+    wt = wt if wt_as is None else wt_as
+    n = len(xy)
+    inst = eng.Instance(ctx, xy, wt, integer_cost)
+    # GEO is the tolerance tier (cos / acos differ in the last ulp between libraries): compared on the device's own distances
+    D = inst.dist_matrix()[0] if wt == O.GEO else O.dist_matrix(xy, wt, integer_cost)
+    what = "%s wt %d int %d" % (name, wt, integer_cost)
+    got = inst.greedy_edge(want_edges=True, want_stats=True)
+    inst.close()
+    check_result(got, G.sort_and_walk(D), integer_cost, what)
+    check_stats(got[3], n, name in UNIFORM, what)
+    if name == "collinear200":
+        assert got[3]["rounds"] == n - 1 and got[3]["max_edges_in_round"] == 1 and got[3]["rows_scanned"] <= 4 * n
+
+
+def test_metric_coverage_of_the_cases():
+    seen = {(load(n)[1] if w is None else w) for n, w in CASES}
+    assert seen == {O.EUC_2D, O.MAX_2D, O.MAN_2D, O.CEIL_2D, O.GEO, O.ATT}
+
+
+def test_greedy_edge_at_scale(eng, ctx):
+    """n = 20 011 against the round-rule reference over row scans (about 12 s of numpy for it; the distance matrix would not
+    fit a sort)."""
+    n = 20011
+    xy = rand_instance(n)
+    inst = eng.Instance(ctx, xy, O.EUC_2D, 1)
+    got = inst.greedy_edge(want_edges=True, want_stats=True)
+    inst.close()
+    ref = G.round_rule(HK.Euc2DRows(xy))
+    check_result(got, ref, 1, "rand%d" % n)
+    check_stats(got[3], n, True, "rand%d" % n)
+    assert got[3]["rounds"] == ref[3]["rounds"] and got[3]["rows_scanned"] == ref[3]["rows_scanned"]
+    assert got[3]["max_edges_in_round"] == max(ref[3]["edges_per_round"])
+
+
+def test_rounds_and_rows_equal_the_round_rule_reference(eng, ctx):
+    """The device follows the round rule round for round: its counters equal the CPU rounds' (pr1002, fractional costs)."""
+    xy, wt = load("pr1002")
+    inst = eng.Instance(ctx, xy, wt, 0)
+    st = inst.greedy_edge(want_stats=True)[2]
+    inst.close()
+    info = G.round_rule(O.dist_matrix(xy, wt, 0))[3]
+    assert (st["rounds"], st["rows_scanned"], st["max_edges_in_round"]) == (info["rounds"], info["rows_scanned"],
+                                                                             max(info["edges_per_round"]))
+
+
+def test_two_runs_return_the_same_bits(eng, ctx):
+    xy, wt = load("pr1002")
+    inst = eng.Instance(ctx, xy, wt, 0)
+    a = inst.greedy_edge(want_edges=True, want_stats=True)
+    b = inst.greedy_edge(want_edges=True, want_stats=True)
+    assert a[0].tobytes() == b[0].tobytes() and np.float64(a[1]).tobytes() == np.float64(b[1]).tobytes()
+    assert a[2].tobytes() == b[2].tobytes()
+    for k in ("rounds", "edges", "rows_scanned", "dists_executed", "max_edges_in_round"):
+        assert a[3][k] == b[3][k], k
+    # every output may be NULL, and the tour does not depend on which are asked for
+    L = eng.lib()
+    assert L.tsp_dev_greedy_edge(inst._h, None, 1, None, None, None) == 0
+    obj = C.c_double(0)
+    assert L.tsp_dev_greedy_edge(inst._h, None, 0, C.byref(obj), None, None) == 0 and obj.value == a[1]
+    # a strided successor list (the host's edge array)
+    wide = np.full((inst.n, 2), -7, dtype=np.int32)
+    assert L.tsp_dev_greedy_edge(inst._h, wide[:, 1:].ctypes.data_as(C.POINTER(C.c_int)), 2, None, None, None) == 0
+    assert (wide[:, 1] == a[0]).all() and (wide[:, 0] == -7).all()
+    inst.close()
+
+
+def test_bad_arguments_leave_the_outputs_untouched(eng, ctx):
+    L = eng.lib()
+    succ = np.full(52, -7, dtype=np.int32)
+    edges = np.full((51, 2), -7, dtype=np.int32)
+    obj = C.c_double(-7.0)
+    st = eng.GreedyEdgeStats()
+    st.rounds = -7
+    ip = C.POINTER(C.c_int)
+    assert L.tsp_dev_greedy_edge(None, succ.ctypes.data_as(ip), 1, C.byref(obj), edges.ctypes.data_as(ip), C.byref(st)) == eng.E_ARG
+    assert b"tsp_dev_greedy_edge" in L.tsp_dev_last_error()
+    xy, wt = load("berlin52")
+    inst = eng.Instance(ctx, xy, wt, 1)
+    for stride in (0, -1):
+        assert L.tsp_dev_greedy_edge(inst._h, succ.ctypes.data_as(ip), stride, C.byref(obj), edges.ctypes.data_as(ip),
+                                     C.byref(st)) == eng.E_ARG
+    assert (succ == -7).all() and (edges == -7).all() and obj.value == -7.0 and st.rounds == -7
+    with pytest.raises(eng.TspDeviceError, match="-3"):
+        eng.Instance(ctx, np.array([[0.0, 0.0], [1.0, 1.0]]), O.EUC_2D, 1)   # n = 2: no handle to ask with
+    s, o = inst.greedy_edge()   # the handle still works
+    assert O.is_tour(s) and o == O.succ_cost(xy, wt, s)
+    inst.close()
+
+
+# ---- the C host mirror --------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def host(eng):
+    from tsp_optimization_amd.build import lib_path
+    L = C.CDLL(lib_path("libtsp_host.so"))
+    for f in ["HEU_greedy_edge", "HEU_2opt_greedy_edge", "HEU_nl_greedy_edge", "HEU_ils_greedy_edge", "alg_2opt", "alg_nl_opt"]:
+        getattr(L, f).argtypes = [C.POINTER(Instance)]
+    L.tsp_host_last_greedy_edge_stats.argtypes = [C.POINTER(eng.GreedyEdgeStats)]
+    L.tsp_host_set_ils.argtypes = [C.c_int, C.c_int, C.c_int]
+    yield L
+    L.tsp_host_set_ils(100, 50, 1)
+    L.tsp_host_shutdown()
+
+
+@pytest.fixture(scope="module")
+def pr299_start(eng, ctx):
+    xy, wt = load("pr299")
+    inst = eng.Instance(ctx, xy, wt, 1)
+    out = inst.greedy_edge(want_stats=True)
+    inst.close()
+    return out
+
+
+def test_heu_greedy_edge_reproduces_the_python_result(eng, host, pr299_start):
+    succ, obj, st = pr299_start
+    h = HostInstance("pr299")
+    assert host.HEU_greedy_edge(C.byref(h.c)) == 0
+    assert (h.succ == succ).all() and h.obj == obj == O.succ_cost(h.xy, h.wt, succ)
+    assert (h.edges[:, 0] == np.arange(h.n)).all()
+    hs = eng.GreedyEdgeStats()
+    host.tsp_host_last_greedy_edge_stats(C.byref(hs))
+    for k in ("rounds", "edges", "rows_scanned", "dists_executed", "max_edges_in_round"):
+        assert getattr(hs, k) == st[k], k
+
+
+def test_heu_2opt_greedy_edge_ends_in_a_tour_alg_2opt_leaves_alone(eng, host, pr299_start):
+    h = HostInstance("pr299")
+    assert host.HEU_2opt_greedy_edge(C.byref(h.c)) == 0
+    s, o = h.succ, h.obj
+    assert O.is_tour(s) and o == O.succ_cost(h.xy, h.wt, s) and o < pr299_start[1]
+    assert host.alg_2opt(C.byref(h.c)) == 0
+    assert (h.succ == s).all() and h.obj == o
+
+
+def test_heu_nl_greedy_edge_is_the_start_plus_alg_nl_opt(eng, host, pr299_start):
+    h = HostInstance("pr299")
+    assert host.HEU_nl_greedy_edge(C.byref(h.c)) == 0
+    g = HostInstance("pr299")
+    g.set_tour(pr299_start[0], pr299_start[1])
+    assert host.alg_nl_opt(C.byref(g.c)) == 0
+    assert (h.succ == g.succ).all() and h.obj == g.obj == O.succ_cost(h.xy, h.wt, h.succ) and h.obj < pr299_start[1]
+
+
+def test_heu_ils_greedy_edge_is_no_dearer_than_its_start(eng, host, pr299_start):
+    assert host.tsp_host_set_ils(20, 50, 1) == 0
+    h = HostInstance("pr299")
+    assert host.HEU_ils_greedy_edge(C.byref(h.c)) == 0
+    assert O.is_tour(h.succ) and h.obj == O.succ_cost(h.xy, h.wt, h.succ)
+    assert h.obj <= pr299_start[1]

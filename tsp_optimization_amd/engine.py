@@ -80,6 +80,11 @@ class AlphaStats(_Stats):
                 ("seconds", C.c_double), ("device_ms", C.c_double)]
 
 
+class GreedyEdgeStats(_Stats):
+    _fields_ = [("rounds", C.c_int64), ("edges", C.c_int64), ("rows_scanned", C.c_int64), ("dists_executed", C.c_int64),
+                ("max_edges_in_round", C.c_int64), ("seconds", C.c_double), ("device_ms", C.c_double)]
+
+
 _lib = None
 
 
@@ -178,6 +183,7 @@ def lib():
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
         L.tsp_dev_inst_alpha_build.argtypes = [vp, C.c_int, dp, dp, C.POINTER(AlphaStats)]
         L.tsp_dev_alpha_rows.argtypes = [vp, dp, C.c_int, ip, dp]
+        L.tsp_dev_greedy_edge.argtypes = [vp, ip, C.c_int, dp, ip, C.POINTER(GreedyEdgeStats)]
         _lib = L
     return _lib
 
@@ -201,6 +207,7 @@ EXPORTED = [
     "tsp_dev_ils", "tsp_dev_ils_kick", "tsp_dev_nl_3opt_dlb", "tsp_dev_ils_dlb",
     "tsp_dev_one_tree", "tsp_dev_held_karp",
     "tsp_dev_inst_alpha_build", "tsp_dev_alpha_rows",
+    "tsp_dev_greedy_edge",
 ]
 
 COMM_ID_BYTES = 128
@@ -530,6 +537,22 @@ class Instance:
         rows = np.ascontiguousarray(np.atleast_1d(rows), dtype=np.int32)
         out = np.zeros((len(rows), self.n), dtype=np.float64)
         _check(lib().tsp_dev_alpha_rows(self._h, _d(pi) if pi is not None else None, len(rows), _i(rows), _d(out)))
+        return out
+
+    # -- greedy-edge construction (extension) -------------------------------------------------
+    def greedy_edge(self, want_edges=False, want_stats=False):
+        """The greedy-edge tour (tsp_dev_greedy_edge) -> (succ [n] int32 with succ[0] the smaller of node 0's two neighbours, obj
+        (recomputed cost)) (+ the n - 1 accepted edges [n-1,2] sorted (lo, hi) with want_edges, + a stats dict with want_stats)"""
+        succ = np.zeros(self.n, dtype=np.int32)
+        edges = np.zeros((self.n - 1, 2), dtype=np.int32) if want_edges else None
+        obj = C.c_double(0)
+        st = GreedyEdgeStats()
+        _check(lib().tsp_dev_greedy_edge(self._h, _i(succ), 1, C.byref(obj), _i(edges) if want_edges else None, C.byref(st)))
+        out = (succ, obj.value)
+        if want_edges:
+            out += (edges,)
+        if want_stats:
+            out += (st.as_dict(),)
         return out
 
     def perm_cost(self, perms):

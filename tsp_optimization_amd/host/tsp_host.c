@@ -696,6 +696,33 @@ int HEU_nl_greedy(instance *inst) { (void)HEU_greedy(inst); return alg_nl_opt(in
 int HEU_nl_grasp(instance *inst) { (void)HEU_Grasp(inst); return alg_nl_opt(inst); }
 int HEU_nl_extramileage(instance *inst) { (void)HEU_extramileage(inst); return alg_nl_opt(inst); }
 
+/* ---- greedy-edge construction (extension) ------------------------------------------------------------------ */
+
+static __thread tsp_greedy_edge_stats t_ge_stats;
+
+void tsp_host_last_greedy_edge_stats(tsp_greedy_edge_stats *out) {
+    if (out) *out = t_ge_stats;
+}
+
+int HEU_greedy_edge(instance *inst) {
+    tsp_greedy_edge_stats st;
+    memset(&st, 0, sizeof st);
+    double obj = 0.0;
+    pthread_mutex_lock(&g_lock);
+    int rc = tsp_dev_greedy_edge(dev_inst_locked(inst), &inst->solution.edges[0].j, 2, &obj, NULL, &st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_greedy_edge", rc);
+    stamp_edge_sources(inst);
+    inst->solution.obj_best = obj;
+    t_ge_stats = st;
+    return 0;
+}
+
+/* construction + descent: the constructive status is overwritten */
+int HEU_2opt_greedy_edge(instance *inst) { (void)HEU_greedy_edge(inst); return alg_2opt(inst); }
+int HEU_nl_greedy_edge(instance *inst) { (void)HEU_greedy_edge(inst); return alg_nl_opt(inst); }
+int HEU_ils_greedy_edge(instance *inst) { (void)HEU_greedy_edge(inst); return alg_ils(inst); }
+
 /* ---- Held-Karp lower bound (extension) -------------------------------------------------------------------- */
 
 static __thread tsp_lb_stats t_lb_stats;
