@@ -9,8 +9,10 @@ import os
 import numpy as np
 import pytest
 
+import alpha_ref as AR
 import greedy_edge_ref as G
 import held_karp_ref as HK
+import nl_opt_ref as NL
 from helpers import INSTANCES, Instance, HostInstance, rand_instance
 from oracle import oracle as O
 
@@ -144,6 +146,56 @@ def test_two_runs_return_the_same_bits(eng, ctx):
     assert L.tsp_dev_greedy_edge(inst._h, wide[:, 1:].ctypes.data_as(C.POINTER(C.c_int)), 2, None, None, None) == 0
     assert (wide[:, 1] == a[0]).all() and (wide[:, 0] == -7).all()
     inst.close()
+
+
+@pytest.mark.parametrize("n,wt,integer_cost", [(257, O.EUC_2D, 1), (1500, O.ATT, 0)])
+def test_the_row_scans_share_one_instance_without_disturbing_each_other(eng, ctx, n, wt, integer_cost):
+    """The 1-tree keeps a block of its own, greedy edge carves the instance's pooled block, the alpha and KNN builds allocate per
+    call: every result of the sequence equals its CPU reference as the per-feature tests compare them, and a call repeated at
+    the end returns the bits of its first run.  257: one past a workgroup, 9 tree chunks of 32 columns, 8 greedy-edge chunks;
+    1500: several workgroups of rows, a short last chunk in every scan, several alpha chunks, fractional costs."""
+    xy = rand_instance(n)
+    inst = eng.Instance(ctx, xy, wt, integer_cost)
+    D = O.dist_matrix(xy, wt, integer_cost)
+    pi = np.random.default_rng(n).uniform(-0.5, 0.5, n) * D[np.triu_indices(n, 1)].mean()
+    ref_tree = HK.one_tree(D, pi)
+    ref_ge = G.sort_and_walk(D)
+    A, Wt, _ = AR.alpha_rows(D, pi)
+    what = "rand%d wt %d" % (n, wt)
+
+    def tree():
+        edges, deg, value = inst.one_tree(pi)
+        assert (edges == ref_tree[0]).all() and (deg == ref_tree[1]).all() and deg.sum() == 2 * n, what
+        assert abs(value - ref_tree[2]) <= 1e-12 * abs(ref_tree[2]), what
+        return edges, deg, value
+
+    def greedy_edge():
+        got = inst.greedy_edge(want_edges=True, want_stats=True)
+        check_result(got, ref_ge, integer_cost, what)
+        check_stats(got[3], n, True, what)
+        return got
+
+    t1 = tree()
+    g1 = greedy_edge()
+    nbr, al = inst.alpha_build(5, pi, want_alpha=True)
+    rn, ra = AR.lists(A, Wt, np.arange(n), 5)
+    assert (nbr == rn).all() and al.tobytes() == ra.tobytes(), what
+    inst.knn_build(10)
+    assert (inst.knn() == NL.knn(D, 10)).all(), what
+    bound, pi_best, st = inst.held_karp(g1[1], max_iters=20)
+    rv = HK.one_tree(D, pi_best)[2]
+    assert abs(rv - bound) <= 1e-9 * abs(bound) and bound <= g1[1] and st["iterations"] == 20, what
+    rows = np.array([0, 1, n - 1], dtype=np.int32)
+    assert inst.alpha_rows(rows, pi).tobytes() == np.ascontiguousarray(A[rows]).tobytes(), what
+    g2 = greedy_edge()
+    t2 = tree()
+    inst.close()
+    assert t1[0].tobytes() == t2[0].tobytes() and t1[1].tobytes() == t2[1].tobytes(), what
+    assert np.float64(t1[2]).tobytes() == np.float64(t2[2]).tobytes(), what
+    assert g1[0].tobytes() == g2[0].tobytes() and g1[2].tobytes() == g2[2].tobytes(), what
+    assert np.float64(g1[1]).tobytes() == np.float64(g2[1]).tobytes(), what
+    deg = np.bincount(g1[2].ravel(), minlength=n)
+    assert (deg == np.bincount(g2[2].ravel(), minlength=n)).all() and deg.max() == 2 and (deg == 1).sum() == 2, what
 
 
 def test_bad_arguments_leave_the_outputs_untouched(eng, ctx):

@@ -2,22 +2,18 @@
 // (tsp_dev_alpha_rows).  The definitions are in include/tsp_hip.h.
 //
 // Tree     tsp_hk_tree (held_karp.hip) leaves the 1-tree's edge slots and the penalties on the device.
-// Order    host, O(n log n): the n - 2 spanning-tree edges in ascending (w, lo, hi) order merge components Kruskal-style; a
-//          component keeps its nodes as a sequence, a merge concatenates two sequences and writes the edge's weight at the
-//          junction: h[k] sits between positions k and k + 1 of the final sequence.  Components are intervals of it, and the
-//          junctions strictly between positions p < q all come from merges no later than the one that united p and q, whose own
-//          junction lies between them: beta(node at p, node at q) = max(h[p .. q-1]), bit for bit a tree weight.  Node 0 takes
-//          the last position, n - 1; every pair with it uses w0, the larger of its two tree edges.
+// Order    host, O(n log n): the spanning-tree edges in ascending (w, lo, hi) order merge components Kruskal-style; a merge
+//          concatenates two node sequences and writes the edge's weight at the junction, h[k] between positions k and k + 1 of
+//          the final sequence, so that beta(node at p, node at q) = max(h[p .. q-1]), bit for bit a tree weight.
+//          Node 0 takes the last position, n - 1; every pair with it uses w0, the larger of its two tree edges.
 // Columns  k_alpha_cols: the records {x, y, pi, node} in position order.  k_alpha_bounds: per column chunk and position the
-//          running maximum a lane starts the chunk with (positions left of the chunk: up to its first column; right of it: down
-//          to its last).
-// Scan     k_alpha_scan (one lane = one row position, the column is wave-uniform: record and junction come from scalar loads;
-//          columns right of the lane ascend, columns left of it descend, m = max(m, h) in a register; alpha = w - m; LISTS: the
-//          lane's 16 best (alpha, w, node) sorted in registers; ROWS: alpha stored per column) -> k_alpha_merge (LISTS: the
-//          chunks' lists merged, the first K stored per node).
+//          running maximum a lane starts the chunk with (left of the chunk: up to its first column; right of it: down to its last).
+// Scan     k_alpha_scan (a row scan, row_scan.hpp, over positions; columns right of the lane ascend, columns left of it descend,
+//          m = max(m, h) in a register; alpha = w - m; LISTS: the lane's 16 best (alpha, w, node); ROWS: alpha stored per
+//          column) -> k_alpha_merge (LISTS: the first K stored per node).
 // Nothing is accumulated in floating point and no atomic is used: two runs return the same bits.
 #include "tsp_internal.hpp"
-
+#include "row_scan.hpp"
 #include <math.h>
 #include <algorithm>
 #include <numeric>
@@ -32,11 +28,7 @@ constexpr int kK = TSP_NL_MAX_K;     // k_alpha_scan keeps this many per row wha
 constexpr int kAlChunks = 16;        // most column chunks
 constexpr int kAlWaves = 4096;       // ... chosen so that about this many waves exist
 
-struct alignas(32) AlCol {
-    double x, y, pi;
-    int id, pad;
-};
-static_assert(sizeof(AlCol) == 32, "AlCol is one 32-byte scalar load");
+typedef ScanCol AlCol;               // tag = the node at this position
 
 // the strict order of list entries: (alpha, w, node)
 __device__ __forceinline__ bool al_less(double a, double w, int id, double a2, double w2, int id2) {
@@ -66,7 +58,7 @@ __global__ __launch_bounds__(256) void k_alpha_cols(const double2 *__restrict__ 
     const int v = ids[p];
     const double2 c = coord[v];
     AlCol r;
-    r.x = c.x; r.y = c.y; r.pi = pi[v]; r.id = v; r.pad = 0;
+    r.x = c.x; r.y = c.y; r.pi = pi[v]; r.tag = v; r.pad = 0;
     col[p] = r;
 }
 
@@ -117,8 +109,8 @@ struct AlLane {
     double *out;   // ROWS: this lane's row
 
     __device__ __forceinline__ void visit(int q, const AlCol &cc, double beta) {
-        const bool vlo = me.id < cc.id;
-        double d;
+        const bool vlo = me.tag < cc.tag;
+        double d;   // pair_dist and pair_weight (row_scan.hpp), written out: through them the GEO scans are allocated other registers
         if constexpr (WT == WT_GEO) {
             const double ax = vlo ? me.x : cc.x, ay = vlo ? me.y : cc.y, bx = vlo ? cc.x : me.x, by = vlo ? cc.y : me.y;
             d = dist_xy<WT, INT>(ax, ay, bx, by);
@@ -128,11 +120,11 @@ struct AlLane {
         const double w = (d + (vlo ? me.pi : cc.pi)) + (vlo ? cc.pi : me.pi);
         const bool zero = p == n - 1 || q == n - 1;
         double a = w - (zero ? w0 : beta);
-        if (zero && (me.id | cc.id) == c1) a = 0.0;   // one of the two ids is 0
+        if (zero && (me.tag | cc.tag) == c1) a = 0.0;   // one of the two ids is 0
         if constexpr (ROWS) {
-            if (live) out[cc.id] = a;
+            if (live) out[cc.tag] = a;
         } else {
-            if (al_less(a, w, cc.id, ka[kK - 1], kw[kK - 1], ki[kK - 1])) al_insert(ka, kw, ki, a, w, cc.id);
+            if (al_less(a, w, cc.tag, ka[kK - 1], kw[kK - 1], ki[kK - 1])) al_insert(ka, kw, ki, a, w, cc.tag);
         }
     }
 };
@@ -219,13 +211,6 @@ __global__ __launch_bounds__(256) void k_alpha_merge(int n, int Cc, int K, const
         if (s < K) { nbr[(size_t)v * K + s] = ki[s]; alpha[(size_t)v * K + s] = ka[s]; }
 }
 
-bool pi_finite(const double *pi, int n) {
-    if (pi)
-        for (int v = 0; v < n; ++v)
-            if (!std::isfinite(pi[v])) return false;
-    return true;
-}
-
 // The dendrogram order of the spanning tree in the edge slots: ids[p] = node at position p (node 0 last), h[p] = junction
 // between p and p + 1 (-inf from n - 2 on), pos = the inverse of ids.  False: the slots do not hold a tree.
 bool dendrogram(int n, const std::vector<int> &lo, const std::vector<int> &hi, const std::vector<double> &w, std::vector<int> &ids,
@@ -272,7 +257,8 @@ bool dendrogram(int n, const std::vector<int> &lo, const std::vector<int> &hi, c
 
 // Everything the scans need, built for one pi.
 struct AlPrep {
-    int n = 0, CH = 0, Cc = 0, c1 = 0;
+    int n = 0, c1 = 0;
+    ScanChunks g = {0, 0};
     double w0 = 0.0, W = 0.0;
     long long rounds = 0;
     float tree_ms = 0.f;
@@ -299,20 +285,17 @@ int prepare(tsp_dev_inst *inst, const double *pi, AlPrep *P) {
         return TSP_DEV_E_HIP;
     }
     P->n = n; P->c1 = hi[0]; P->w0 = w[n]; P->W = tr.W; P->rounds = tr.rounds; P->tree_ms = tr.device_ms;
-    const int waves = (n + 63) / 64;
-    const int Cc0 = std::max(1, std::min(kAlChunks, (kAlWaves + waves - 1) / waves));
-    P->CH = (n + Cc0 - 1) / Cc0;
-    P->Cc = (n + P->CH - 1) / P->CH;
+    P->g = scan_chunks(n, kAlWaves, kAlChunks, 1);
     TSP_HIP_TRY(P->col.alloc((size_t)n));
     TSP_HIP_TRY(P->h.alloc((size_t)n));
-    TSP_HIP_TRY(P->T.alloc((size_t)P->Cc * n));
+    TSP_HIP_TRY(P->T.alloc((size_t)P->g.Cc * n));
     TSP_HIP_TRY(P->ids.alloc((size_t)n));
     TSP_HIP_TRY(hipMemcpy(P->ids.p, ids.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     TSP_HIP_TRY(hipMemcpy(P->h.p, h.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     if (int e = tsp_inst_events(inst)) return e;
     TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
     hipLaunchKernelGGL(k_alpha_cols, dim3((n + 255) / 256), dim3(256), 0, s, inst->d_coord, tr.d_pi, P->ids.p, n, P->col.p);
-    hipLaunchKernelGGL(k_alpha_bounds, dim3(P->Cc), dim3(256), 0, s, P->h.p, n, P->CH, P->T.p);
+    hipLaunchKernelGGL(k_alpha_bounds, dim3(P->g.Cc), dim3(256), 0, s, P->h.p, n, P->g.CH, P->T.p);
     return TSP_OK;
 }
 
@@ -337,7 +320,7 @@ int tsp_dev_inst_alpha_build(tsp_dev_inst *inst, int K, const double *pi, double
     hipStream_t s = inst->ctx->stream;
     DevBuf<double> pa, pw, d_alpha;
     DevBuf<int> pid, nbr;
-    const size_t part = (size_t)P.Cc * kK * n;
+    const size_t part = (size_t)P.g.Cc * kK * n;
     TSP_HIP_TRY(pa.alloc(part));
     TSP_HIP_TRY(pw.alloc(part));
     TSP_HIP_TRY(pid.alloc(part));
@@ -345,10 +328,10 @@ int tsp_dev_inst_alpha_build(tsp_dev_inst *inst, int K, const double *pi, double
     TSP_HIP_TRY(d_alpha.alloc((size_t)n * K));
     const int gn = (n + 255) / 256;
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-        hipLaunchKernelGGL((k_alpha_scan<WTC, INTC, false>), dim3(gn, P.Cc), dim3(256), 0, s, P.col.p, P.h.p, P.T.p, (const int *)nullptr, n,
-                           n, P.CH, P.w0, P.c1, pa.p, pw.p, pid.p, (double *)nullptr);
+        hipLaunchKernelGGL((k_alpha_scan<WTC, INTC, false>), dim3(gn, P.g.Cc), dim3(256), 0, s, P.col.p, P.h.p, P.T.p, (const int *)nullptr, n,
+                           n, P.g.CH, P.w0, P.c1, pa.p, pw.p, pid.p, (double *)nullptr);
     });
-    hipLaunchKernelGGL(k_alpha_merge, dim3(gn), dim3(256), 0, s, n, P.Cc, K, P.ids.p, pa.p, pw.p, pid.p, nbr.p, d_alpha.p);
+    hipLaunchKernelGGL(k_alpha_merge, dim3(gn), dim3(256), 0, s, n, P.g.Cc, K, P.ids.p, pa.p, pw.p, pid.p, nbr.p, d_alpha.p);
     TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
     TSP_HIP_TRY(hipEventSynchronize(inst->ev1));
     TSP_HIP_TRY(hipGetLastError());
@@ -386,8 +369,8 @@ int tsp_dev_alpha_rows(tsp_dev_inst *inst, const double *pi, int m, const int *r
     TSP_HIP_TRY(hipMemcpyAsync(d_rp.p, rp.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, s));
     TSP_HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * (size_t)m * n, s));   // out[r][rows[r]] = 0
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-        hipLaunchKernelGGL((k_alpha_scan<WTC, INTC, true>), dim3((m + 255) / 256, P.Cc), dim3(256), 0, s, P.col.p, P.h.p, P.T.p, d_rp.p, m,
-                           n, P.CH, P.w0, P.c1, (double *)nullptr, (double *)nullptr, (int *)nullptr, d_out.p);
+        hipLaunchKernelGGL((k_alpha_scan<WTC, INTC, true>), dim3((m + 255) / 256, P.g.Cc), dim3(256), 0, s, P.col.p, P.h.p, P.T.p, d_rp.p, m,
+                           n, P.g.CH, P.w0, P.c1, (double *)nullptr, (double *)nullptr, (int *)nullptr, d_out.p);
     });
     TSP_HIP_TRY(hipStreamSynchronize(s));
     TSP_HIP_TRY(hipGetLastError());

@@ -3,21 +3,17 @@
 // State per node: the column record {x, y, deg}, other[v] (the other end of v's fragment; v itself at degree 0), the cached
 // smallest valid edge best[v] = (bw[v], bo[v]) and two adjacency slots.  A partner c is valid for a free node u (deg < 2) iff
 // deg[c] < 2, c != u and c != other[u].
-// Round r  k_ge_scan (the rows of the stale list x all columns in chunks: one lane = one row, the column is wave-uniform and
-//          its record comes from scalar loads; each lane keeps its smallest valid edge) -> k_ge_merge (the chunks of a row merged
-//          in column order into best[u]) -> k_ge_decide (edge {u, v} joins iff it is the best of both ends and smaller than the
-//          best of the other end of either fragment: best(F_u) = e = best(F_v); every node writes its own verdict) ->
-//          k_ge_apply (the verdicts carried out: degrees, adjacency, the two new ends point at each other) -> k_ge_stale (the
-//          free nodes whose cached best is no longer valid, compacted into the next round's list).
+// Round r  k_ge_scan (a row scan, row_scan.hpp, over the rows of the stale list: each lane keeps its smallest valid edge) ->
+//          k_ge_merge (a row's chunks into best[u]) -> k_ge_decide (edge {u, v} joins iff best(F_u) = e = best(F_v); every node
+//          writes its own verdict) -> k_ge_apply (the verdicts carried out) -> k_ge_stale (the free nodes whose cached best is
+//          no longer valid, compacted into the next round's list).
 // Validity only shrinks, so a cached best that is still valid is still the minimum and is not rescanned: about 3 n rows are
-// scanned in all, not rounds x n.  Within a row (lo, hi) grows with the column, so `d < best` on ascending columns and
-// ascending chunks IS the order (d, lo, hi).  A fragment's two ends know each other through other[], so the fragment minimum is
-// one comparison and needs no atomics; each fragment takes part in at most one join per round, so no two joins touch the same
-// state.  The only atomics are integer adds (edge count, list cursor); the order of the stale list does not reach any result.
-// Rounds are queued in batches without a wait: ecnt[r & 3] is the edge count at the start of round r, round r adds to
-// ecnt[(r + 1) & 3]; once it holds n - 1 every kernel of the rounds behind returns at once (held_karp.hip's pattern).
+// scanned in all, not rounds x n.  A fragment's two ends know each other through other[], so the fragment minimum is one
+// comparison; a fragment takes part in at most one join per round, so no two joins touch the same state.  The only atomics are
+// integer adds (edge count, list cursor); the order of the stale list does not reach any result.  Rounds are queued in batches
+// without a wait: round r reads ecnt[r & 3] and adds to ecnt[(r + 1) & 3]; at n - 1 the rounds behind return at once.
 #include "tsp_internal.hpp"
-
+#include "row_scan.hpp"
 #include <math.h>
 #include <algorithm>
 
@@ -32,12 +28,7 @@ constexpr int kGeMinChunk = 32;      // ... of at least this many columns
 constexpr int kGeFirstBatch = 16, kGeMaxBatch = 64;   // rounds queued between two looks at the control block
 constexpr int kCostThreads = 1024;
 
-struct alignas(32) GeCol {
-    double x, y;
-    int deg, pad0;
-    long long pad1;
-};
-static_assert(sizeof(GeCol) == 32, "GeCol is one 32-byte scalar load");
+typedef ScanColDeg GeCol;
 
 struct alignas(16) GeCtl {
     long long rounds, rows_scanned, dists, max_edges;
@@ -67,8 +58,7 @@ __global__ __launch_bounds__(256) void k_ge_init(const double2 *__restrict__ coo
 }
 
 // Slot i of the stale list = one lane, columns [chunk * CH, chunk * CH + CH): pw / po [chunk * n + i] = the smallest valid edge
-// (d, partner) of row list[i] (+inf, -1: none).  The distance is taken with the row first: every metric but GEO is symmetric to
-// the bit; GEO orders its operands (lower id first).  The grid covers n slots; the workgroups past the list return at once.
+// (d, partner) of row list[i] (+inf, -1: none).  The grid covers n slots; the workgroups past the list return at once.
 template <int WT, bool INT>
 __global__ __launch_bounds__(256) void k_ge_scan(const GeCol *__restrict__ col, const int *__restrict__ other,
                                                  const int *__restrict__ list, const GeCtl *__restrict__ ctl, int r, int n, int CH,
@@ -87,14 +77,7 @@ __global__ __launch_bounds__(256) void k_ge_scan(const GeCol *__restrict__ col, 
 #pragma unroll 4
     for (int c = c0; c < c1; ++c) {   // (unrolled: four columns' scalar loads in flight)
         const GeCol cc = col[c];
-        double d;
-        if constexpr (WT == WT_GEO) {
-            const bool ulo = u < c;
-            const double ax = ulo ? me.x : cc.x, ay = ulo ? me.y : cc.y, bx = ulo ? cc.x : me.x, by = ulo ? cc.y : me.y;
-            d = dist_xy<WT, INT>(ax, ay, bx, by);
-        } else {
-            d = dist_xy<WT, INT>(me.x, me.y, cc.x, cc.y);
-        }
+        const double d = pair_dist<WT, INT>(u, me.x, me.y, c, cc.x, cc.y);
         if (cc.deg < 2 && c != u && c != ou && d < bw) { bw = d; bo = c; }
     }
     if (i < ns) {
@@ -245,35 +228,19 @@ struct GeBufs {
     int4 *jn;
     double *bw, *pw;
     int *other, *bo, *adj, *list, *po, *succ;
-    int Cc, CH;
+    ScanChunks g;
 };
 
 int ge_carve(tsp_dev_inst *inst, GeBufs *b) {
-    const int n = inst->n;
-    const int want = std::max(1, std::min(kGeMaxChunks, n / kGeMinChunk));
-    b->CH = (n + want - 1) / want;
-    b->Cc = (n + b->CH - 1) / b->CH;
-    const size_t N = (size_t)n, P = (size_t)b->Cc * N;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t a_ctl = take(sizeof(GeCtl)), a_cost = take(sizeof(double)), a_col = take(sizeof(GeCol) * N),
-                 a_jn = take(sizeof(int4) * N), a_bw = take(sizeof(double) * N), a_pw = take(sizeof(double) * P),
-                 a_other = take(sizeof(int) * N), a_bo = take(sizeof(int) * N), a_adj = take(sizeof(int) * 2 * N),
-                 a_list = take(sizeof(int) * N), a_po = take(sizeof(int) * P), a_succ = take(sizeof(int) * N);
-    char *pool = static_cast<char *>(tsp_io_pool(inst, off));
+    b->g = scan_chunks_few_rows(inst->n, kGeMaxChunks, kGeMinChunk);
+    const size_t N = (size_t)inst->n, P = (size_t)b->g.Cc * N;
+    auto lay = [&](Carver &c) {
+        c(b->ctl, 1); c(b->cost, 1); c(b->col, N); c(b->jn, N); c(b->bw, N); c(b->pw, P);
+        c(b->other, N); c(b->bo, N); c(b->adj, 2 * N); c(b->list, N); c(b->po, P); c(b->succ, N);
+    };
+    void *pool = tsp_io_pool(inst, carve_bytes(lay));
     if (!pool) return TSP_DEV_E_NOMEM;
-    b->ctl = reinterpret_cast<GeCtl *>(pool + a_ctl);
-    b->cost = reinterpret_cast<double *>(pool + a_cost);
-    b->col = reinterpret_cast<GeCol *>(pool + a_col);
-    b->jn = reinterpret_cast<int4 *>(pool + a_jn);
-    b->bw = reinterpret_cast<double *>(pool + a_bw);
-    b->pw = reinterpret_cast<double *>(pool + a_pw);
-    b->other = reinterpret_cast<int *>(pool + a_other);
-    b->bo = reinterpret_cast<int *>(pool + a_bo);
-    b->adj = reinterpret_cast<int *>(pool + a_adj);
-    b->list = reinterpret_cast<int *>(pool + a_list);
-    b->po = reinterpret_cast<int *>(pool + a_po);
-    b->succ = reinterpret_cast<int *>(pool + a_succ);
+    carve(pool, lay);
     return TSP_OK;
 }
 
@@ -284,9 +251,9 @@ void queue_rounds(tsp_dev_inst *inst, const GeBufs &b, int r0, int count) {
     const int gn = (n + 255) / 256;
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         for (int r = r0; r < r0 + count; ++r) {
-            hipLaunchKernelGGL((k_ge_scan<WTC, INTC>), dim3(gn, b.Cc), dim3(256), 0, s, b.col, b.other, b.list, b.ctl, r, n, b.CH,
+            hipLaunchKernelGGL((k_ge_scan<WTC, INTC>), dim3(gn, b.g.Cc), dim3(256), 0, s, b.col, b.other, b.list, b.ctl, r, n, b.g.CH,
                                b.pw, b.po);
-            hipLaunchKernelGGL(k_ge_merge, dim3(gn), dim3(256), 0, s, b.ctl, r, n, b.Cc, b.list, b.pw, b.po, b.bw, b.bo);
+            hipLaunchKernelGGL(k_ge_merge, dim3(gn), dim3(256), 0, s, b.ctl, r, n, b.g.Cc, b.list, b.pw, b.po, b.bw, b.bo);
             hipLaunchKernelGGL(k_ge_decide, dim3(gn), dim3(256), 0, s, b.col, b.other, b.bw, b.bo, b.ctl, r, n, b.jn);
             hipLaunchKernelGGL(k_ge_apply, dim3(gn), dim3(256), 0, s, b.col, b.other, b.adj, b.jn, b.ctl, r, n);
             hipLaunchKernelGGL(k_ge_stale, dim3(gn), dim3(256), 0, s, b.col, b.other, b.bo, b.ctl, r, n, n, b.list);
@@ -323,9 +290,8 @@ int tsp_dev_greedy_edge(tsp_dev_inst *inst, int *succ, int succ_stride, double *
     for (;;) {
         queue_rounds(inst, b, queued, batch);
         queued += batch;
-        TSP_HIP_TRY(hipMemcpyAsync(&c, b.ctl, sizeof c, hipMemcpyDeviceToHost, s));
-        TSP_HIP_TRY(hipStreamSynchronize(s));
-        TSP_HIP_TRY(hipGetLastError());
+        rc = poll_ctl(s, &c, b.ctl);
+        if (rc) return rc;
         if (c.ecnt[queued & 3] >= n - 1) break;
         if (c.rounds != queued || queued >= n - 1) {   // every round adds an edge: n - 1 rounds always suffice
             tsp::set_last_error_text("tsp_dev_greedy_edge: the rounds did not end in one path");
@@ -345,7 +311,7 @@ int tsp_dev_greedy_edge(tsp_dev_inst *inst, int *succ, int succ_stride, double *
         for (int k = 0; k < 2; ++k) {
             const int w = adj[2 * (size_t)v + k];
             if (w < -1 || w >= n || w == v) good = false;
-            else if (w > v) el.push_back(((long long)v << 32) | (long long)w);
+            else if (w > v) el.push_back(edge_key(v, w));
         }
         if (adj[2 * (size_t)v] < 0) good = false;
         else if (adj[2 * (size_t)v + 1] < 0) {
@@ -381,10 +347,7 @@ int tsp_dev_greedy_edge(tsp_dev_inst *inst, int *succ, int succ_stride, double *
     if (succ)
         for (int v = 0; v < n; ++v) succ[(size_t)v * succ_stride] = sc[(size_t)v];
     if (obj) *obj = cost;
-    if (edges) {
-        std::sort(el.begin(), el.end());
-        for (int k = 0; k < n - 1; ++k) { edges[2 * k] = (int)(el[k] >> 32); edges[2 * k + 1] = (int)(el[k] & 0xffffffffll); }
-    }
+    if (edges) write_sorted_keys(el, edges);
     if (stats) {
         memset(stats, 0, sizeof *stats);
         stats->rounds = c.rounds; stats->edges = c.ecnt[queued & 3]; stats->rows_scanned = c.rows_scanned;

@@ -1,22 +1,20 @@
 // held_karp.hip -- Held-Karp lower bound: minimum 1-trees under node penalties (tsp_dev_one_tree) and the subgradient ascent
 // over them (tsp_dev_held_karp).  The definitions are in include/tsp_hip.h.
 //
-// Tree     k_hk_init (column records {x, y, pi, component}, every node its own component) -> R Boruvka rounds over nodes
+// Tree     k_hk_init (column records {x, y, pi, tag = component}, every node its own component) -> R Boruvka rounds over nodes
 //          1 .. n-1 -> k_hk_finish (one workgroup: the two smallest edges at node 0, W, |g|^2 and, in the ascent, the step).
-// Round r  k_hk_scan (one lane = one row node, the column is wave-uniform: its record comes from scalar loads; columns in
-//          chunks; each lane keeps its smallest edge into another component) -> k_hk_min1 (the chunks merged per node; per
-//          component the smallest weight) -> k_hk_min2 (among the nodes that hold that weight the smallest (lo, hi)) ->
-//          k_hk_hook (per root: its component's edge; two components that chose the same edge keep the lower root; the root that
-//          is hooked stores the edge in ITS slot, so no slot is written twice and no list is appended to) -> k_hk_relabel.
-// The edge order (w, lo, hi) is strict, so the chosen edges never close a cycle and every algorithm returns this tree.  Within a
-// row (lo, hi) grows with the column, so `w < best` on ascending columns and ascending chunks IS the order.  Across nodes the
-// minimum goes through 64-bit INTEGER atomic minima (of the ordered bit pattern of w, then of lo << 32 | hi): their result does
-// not depend on arrival order.  No floating-point atomic anywhere; every sum is a fixed tree in one workgroup.
+// Round r  k_hk_scan (a row scan, row_scan.hpp: each lane keeps its smallest edge into another component) -> k_hk_min1 (the
+//          chunks merged per node; per component the smallest weight) -> k_hk_min2 (among the nodes that hold it the smallest
+//          (lo, hi)) -> k_hk_hook (per root: its component's edge; two components that chose the same edge keep the lower root;
+//          the hooked root stores the edge in ITS slot, so no slot is written twice) -> k_hk_relabel.
+// The edge order (w, lo, hi) is strict, so the chosen edges never close a cycle and every algorithm returns this tree.  Across
+// nodes the minimum goes through 64-bit INTEGER atomic minima (of the ordered bits of w, then of lo << 32 | hi), whose result
+// does not depend on arrival order.  No floating-point atomic anywhere; every sum is a fixed tree in one workgroup.
 // A tree of R rounds is queued without a wait: round r reads ncomp[r] and adds to ncomp[r + 1], rounds behind the last one
 // return at once.  The ascent queues R = (rounds of the last tree) + 1; a tree that is not finished after them raises `stop`,
 // which turns everything queued behind it into no-ops, and the host repeats that iteration with the full ceil(log2(n - 1)).
 #include "tsp_internal.hpp"
-
+#include "row_scan.hpp"
 #include <math.h>
 #include <algorithm>
 
@@ -35,11 +33,7 @@ constexpr int kHkMinChunk = 32;       // ... of at least this many columns
 constexpr int kFinThreads = 1024;
 constexpr hk_u64 kNone = ~0ull;
 
-struct alignas(32) HkCol {
-    double x, y, pi;
-    int comp, pad;
-};
-static_assert(sizeof(HkCol) == 32, "HkCol is one 32-byte scalar load");
+typedef ScanCol HkCol;   // tag = the node's component
 
 struct alignas(16) HkCtl {
     double ub, lambda, best, W;
@@ -93,14 +87,13 @@ __global__ __launch_bounds__(256) void k_hk_init(const double2 *__restrict__ coo
     if (v == n) return;
     const double2 c = coord[v];
     HkCol r;
-    r.x = c.x; r.y = c.y; r.pi = pi[v]; r.comp = v; r.pad = 0;
+    r.x = c.x; r.y = c.y; r.pi = pi[v]; r.tag = v; r.pad = 0;
     col[v] = r;
     compw[v] = kNone; compe[v] = kNone; deg[v] = 0;
 }
 
 // Row node v = one lane, columns [max(1, chunk * CH), chunk * CH + CH): pw / po [chunk * n + v] = the smallest edge (w, other
-// end) from v into another component (+inf, -1: none).  The distance is taken with the row first: every metric but GEO is
-// symmetric to the bit (a - b = -(b - a) exactly, and only squares and absolute values of it are used); GEO orders its operands.
+// end) from v into another component (+inf, -1: none).
 template <int WT, bool INT>
 __global__ __launch_bounds__(256) void k_hk_scan(const HkCol *__restrict__ col, const HkCtl *__restrict__ ctl, int r, int n, int CH,
                                                  double *__restrict__ pw, int *__restrict__ po) {
@@ -114,16 +107,8 @@ __global__ __launch_bounds__(256) void k_hk_scan(const HkCol *__restrict__ col, 
 #pragma unroll 4
     for (int c = c0; c < c1; ++c) {   // (unrolled: four columns' scalar loads in flight)
         const HkCol cc = col[c];
-        const bool vlo = v < c;
-        double d;
-        if constexpr (WT == WT_GEO) {
-            const double ax = vlo ? me.x : cc.x, ay = vlo ? me.y : cc.y, bx = vlo ? cc.x : me.x, by = vlo ? cc.y : me.y;
-            d = dist_xy<WT, INT>(ax, ay, bx, by);
-        } else {
-            d = dist_xy<WT, INT>(me.x, me.y, cc.x, cc.y);
-        }
-        const double w = (d + (vlo ? me.pi : cc.pi)) + (vlo ? cc.pi : me.pi);
-        if (cc.comp != me.comp && w < bw) { bw = w; bo = c; }
+        const double w = pair_weight<WT, INT>(v, me.x, me.y, me.pi, c, cc.x, cc.y, cc.pi);
+        if (cc.tag != me.tag && w < bw) { bw = w; bo = c; }
     }
     if (v >= n) return;
     const size_t at = (size_t)chunk * n + v;
@@ -147,7 +132,7 @@ __global__ __launch_bounds__(256) void k_hk_min1(const HkCol *__restrict__ col, 
         candw[v] = bw; cando[v] = bo;
     }
     const bool valid = bo >= 0;
-    comp_atomic_min(compw, valid ? col[v].comp : 0, valid ? ord_of(bw) : kNone, valid);
+    comp_atomic_min(compw, valid ? col[v].tag : 0, valid ? ord_of(bw) : kNone, valid);
 }
 
 // Among the nodes that hold their component's smallest weight: the smallest (lo, hi).
@@ -162,7 +147,7 @@ __global__ __launch_bounds__(256) void k_hk_min2(const HkCol *__restrict__ col, 
     if (v >= 1 && v < n) {
         const int o = cando[v];
         if (o >= 0) {
-            comp = col[v].comp;
+            comp = col[v].tag;
             valid = ord_of(candw[v]) == compw[comp];
             key = ((hk_u64)(unsigned)min(v, o) << 32) | (hk_u64)(unsigned)max(v, o);
         }
@@ -184,12 +169,12 @@ __global__ __launch_bounds__(256) void k_hk_hook(const HkCol *__restrict__ col, 
         return;
     }
     bool hooked = false;
-    if (v >= 1 && v < n && col[v].comp == v) {
+    if (v >= 1 && v < n && col[v].tag == v) {
         const hk_u64 e = compe[v];
         int p = v;
         if (e != kNone) {
             const int lo = (int)(e >> 32), hi = (int)(e & 0xffffffffu);
-            const int other = col[lo].comp == v ? col[hi].comp : col[lo].comp;
+            const int other = col[lo].tag == v ? col[hi].tag : col[lo].tag;
             if (!(compe[other] == e && v < other)) {
                 p = other; hooked = true;
                 elo[v] = lo; ehi[v] = hi; ew[v] = ord_back(compw[v]);
@@ -213,13 +198,13 @@ __global__ __launch_bounds__(256) void k_hk_relabel(HkCol *__restrict__ col, con
     if (hk_idle(ctl) || ctl->ncomp[r] <= 1) return;
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v < 1 || v >= n) return;
-    int root = col[v].comp;
+    int root = col[v].tag;
     for (int hop = 0; hop < n; ++hop) {   // bounded whatever the arrays hold
         const int p = parent[root];
         if (p == root) break;
         root = p;
     }
-    col[v].comp = root;
+    col[v].tag = root;
     compw[v] = kNone; compe[v] = kNone;
 }
 
@@ -268,7 +253,7 @@ __global__ __launch_bounds__(kFinThreads) void k_hk_finish(const HkCol *__restri
     int c1 = -1, c2 = -1;
     for (int c = 1 + tid; c < n; c += kFinThreads) {
         const HkCol cc = col[c];
-        const double w = (dist_xy<WT, INT>(z.x, z.y, cc.x, cc.y) + z.pi) + cc.pi;
+        const double w = pair_weight<WT, INT>(0, z.x, z.y, z.pi, c, cc.x, cc.y, cc.pi);
         top2_offer(w, c, w1, c1, w2, c2);
     }
     sw1[tid] = w1; sc1[tid] = c1; sw2[tid] = w2; sc2[tid] = c2;
@@ -336,48 +321,33 @@ __global__ __launch_bounds__(kFinThreads) void k_hk_finish(const HkCol *__restri
     }
 }
 
-// Scratch of one instance.
+// Scratch of one instance: one device block of its own (the tree's outputs outlive the call that built it) and the pinned h_ctl.
 struct HkData {
-    int n = 0, Cc = 0, CH = 0, Rmax = 0;
+    int n = 0, Rmax = 0;
+    ScanChunks g = {0, 0};
+    void *block = nullptr;
     HkCol *d_col = nullptr;
     HkCtl *d_ctl = nullptr, *h_ctl = nullptr;   // h_ctl pinned
     double *d_pi = nullptr, *d_pi_best = nullptr, *d_candw = nullptr, *d_pw = nullptr, *d_ew = nullptr;
     int *d_gprev = nullptr, *d_deg = nullptr, *d_parent = nullptr, *d_cando = nullptr, *d_po = nullptr, *d_elo = nullptr,
         *d_ehi = nullptr;
     hk_u64 *d_compw = nullptr, *d_compe = nullptr;
-    ~HkData() {
-        (void)hipFree(d_col); (void)hipFree(d_ctl); (void)hipHostFree(h_ctl); (void)hipFree(d_pi); (void)hipFree(d_pi_best);
-        (void)hipFree(d_candw); (void)hipFree(d_pw); (void)hipFree(d_ew); (void)hipFree(d_gprev); (void)hipFree(d_deg);
-        (void)hipFree(d_parent); (void)hipFree(d_cando); (void)hipFree(d_po); (void)hipFree(d_elo); (void)hipFree(d_ehi);
-        (void)hipFree(d_compw); (void)hipFree(d_compe);
-    }
+    ~HkData() { (void)hipFree(block); (void)hipHostFree(h_ctl); }
 };
 
 int hk_alloc_arrays(HkData *x, int n) {
     x->n = n;
-    const int waves = (n + 63) / 64;
-    const int want = std::max(1, std::min(kHkMaxChunks, (kHkWaves + waves - 1) / waves));
-    x->CH = std::max(kHkMinChunk, (n + want - 1) / want);
-    x->Cc = (n + x->CH - 1) / x->CH;
+    x->g = scan_chunks(n, kHkWaves, kHkMaxChunks, kHkMinChunk);
     while ((1ll << x->Rmax) < n - 1) x->Rmax += 1;
-    const size_t N = (size_t)n, P = (size_t)x->Cc * N;
-    TSP_HIP_TRY(hipMalloc(&x->d_col, sizeof(HkCol) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_ctl, sizeof(HkCtl)));
+    const size_t N = (size_t)n, P = (size_t)x->g.Cc * N;
+    auto lay = [&](Carver &c) {
+        c(x->d_col, N); c(x->d_ctl, 1); c(x->d_pi, N); c(x->d_pi_best, N); c(x->d_candw, N); c(x->d_pw, P); c(x->d_ew, N + 1);
+        c(x->d_gprev, N); c(x->d_deg, N); c(x->d_parent, N); c(x->d_cando, N); c(x->d_po, P); c(x->d_elo, N + 1);
+        c(x->d_ehi, N + 1); c(x->d_compw, N); c(x->d_compe, N);
+    };
+    TSP_HIP_TRY(hipMalloc(&x->block, carve_bytes(lay)));
+    carve(x->block, lay);
     TSP_HIP_TRY(hipHostMalloc(&x->h_ctl, sizeof(HkCtl), hipHostMallocDefault));
-    TSP_HIP_TRY(hipMalloc(&x->d_pi, sizeof(double) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_pi_best, sizeof(double) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_candw, sizeof(double) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_pw, sizeof(double) * P));
-    TSP_HIP_TRY(hipMalloc(&x->d_ew, sizeof(double) * (N + 1)));
-    TSP_HIP_TRY(hipMalloc(&x->d_gprev, sizeof(int) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_deg, sizeof(int) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_parent, sizeof(int) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_cando, sizeof(int) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_po, sizeof(int) * P));
-    TSP_HIP_TRY(hipMalloc(&x->d_elo, sizeof(int) * (N + 1)));
-    TSP_HIP_TRY(hipMalloc(&x->d_ehi, sizeof(int) * (N + 1)));
-    TSP_HIP_TRY(hipMalloc(&x->d_compw, sizeof(hk_u64) * N));
-    TSP_HIP_TRY(hipMalloc(&x->d_compe, sizeof(hk_u64) * N));
     return TSP_OK;
 }
 
@@ -402,8 +372,8 @@ void queue_tree(tsp_dev_inst *inst, HkData *x, int R, int ascent) {
                        x->d_deg, x->d_elo, x->d_ew);
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         for (int r = 0; r < R; ++r) {
-            hipLaunchKernelGGL((k_hk_scan<WTC, INTC>), dim3(gn, x->Cc), dim3(256), 0, s, x->d_col, x->d_ctl, r, n, x->CH, x->d_pw, x->d_po);
-            hipLaunchKernelGGL(k_hk_min1, dim3(gn), dim3(256), 0, s, x->d_col, x->d_ctl, r, n, x->Cc, x->d_pw, x->d_po, x->d_candw,
+            hipLaunchKernelGGL((k_hk_scan<WTC, INTC>), dim3(gn, x->g.Cc), dim3(256), 0, s, x->d_col, x->d_ctl, r, n, x->g.CH, x->d_pw, x->d_po);
+            hipLaunchKernelGGL(k_hk_min1, dim3(gn), dim3(256), 0, s, x->d_col, x->d_ctl, r, n, x->g.Cc, x->d_pw, x->d_po, x->d_candw,
                                x->d_cando, x->d_compw);
             hipLaunchKernelGGL(k_hk_min2, dim3(gn), dim3(256), 0, s, x->d_col, x->d_ctl, r, n, x->d_candw, x->d_cando, x->d_compw,
                                x->d_compe);
@@ -414,14 +384,6 @@ void queue_tree(tsp_dev_inst *inst, HkData *x, int R, int ascent) {
         hipLaunchKernelGGL((k_hk_finish<WTC, INTC>), dim3(1), dim3(kFinThreads), 0, s, x->d_col, x->d_ctl, R, n, ascent, x->d_pi,
                            x->d_pi_best, x->d_gprev, x->d_deg, x->d_elo, x->d_ehi, x->d_ew);
     });
-}
-
-int hk_poll(tsp_dev_inst *inst, HkData *x) {
-    hipStream_t s = inst->ctx->stream;
-    TSP_HIP_TRY(hipMemcpyAsync(x->h_ctl, x->d_ctl, sizeof(HkCtl), hipMemcpyDeviceToHost, s));
-    TSP_HIP_TRY(hipStreamSynchronize(s));
-    TSP_HIP_TRY(hipGetLastError());
-    return TSP_OK;
 }
 
 // pi (NULL = zeros) and a fresh control block onto the device
@@ -435,13 +397,6 @@ int hk_begin(tsp_dev_inst *inst, HkData *x, const double *pi, const HkCtl &c0) {
     TSP_HIP_TRY(hipMemcpyAsync(x->d_ctl, x->h_ctl, sizeof(HkCtl), hipMemcpyHostToDevice, s));
     TSP_HIP_TRY(hipStreamSynchronize(s));   // h_ctl is polled into from here on; a pageable pi has been consumed
     return TSP_OK;
-}
-
-bool pi_finite(const double *pi, int n) {
-    if (pi)
-        for (int v = 0; v < n; ++v)
-            if (!std::isfinite(pi[v])) return false;
-    return true;
 }
 
 void fill_stats(tsp_lb_stats *st, const HkCtl &c, double t0, float ms) {
@@ -471,7 +426,7 @@ int tsp_hk_tree(tsp_dev_inst *inst, const double *pi, tsp::HkTree *out, tsp_lb_s
     TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
     queue_tree(inst, x, x->Rmax, 0);
     TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
-    rc = hk_poll(inst, x);
+    rc = poll_ctl(s, x->h_ctl, x->d_ctl);
     if (rc) return rc;
     float ms = 0.f;
     TSP_HIP_TRY(hipEventElapsedTime(&ms, inst->ev0, inst->ev1));
@@ -503,16 +458,10 @@ int tsp_dev_one_tree(tsp_dev_inst *inst, const double *pi, int *edges, int *deg,
         std::vector<int> lo((size_t)n + 1), hi((size_t)n + 1);
         TSP_HIP_TRY(hipMemcpy(lo.data(), x->d_elo, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost));
         TSP_HIP_TRY(hipMemcpy(hi.data(), x->d_ehi, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost));
-        std::vector<long long> e;
-        e.reserve((size_t)n);
-        for (int k = 0; k <= n; ++k)
-            if (lo[k] >= 0) e.push_back(((long long)lo[k] << 32) | (long long)hi[k]);
-        if ((int)e.size() != n) {
+        if (write_sorted_edges(lo.data(), hi.data(), n + 1, edges, n) != n) {
             tsp::set_last_error_text("tsp_dev_one_tree: the 1-tree does not have n edges");
             return TSP_DEV_E_HIP;
         }
-        std::sort(e.begin(), e.end());
-        for (int k = 0; k < n; ++k) { edges[2 * k] = (int)(e[k] >> 32); edges[2 * k + 1] = (int)(e[k] & 0xffffffffll); }
     }
     return TSP_OK;
 }
@@ -549,7 +498,7 @@ int tsp_dev_held_karp(tsp_dev_inst *inst, double ub, int max_iters, double lambd
             next = (int)std::max(1.0, std::min((double)next, (time_limit_s - (wall_s() - t0)) / per));
         const double tq = wall_s();
         for (int k = 0; k < next; ++k) queue_tree(inst, x, R, 1);
-        rc = hk_poll(inst, x);
+        rc = poll_ctl(s, x->h_ctl, x->d_ctl);
         if (rc) return rc;
         const HkCtl &c = *x->h_ctl;
         per = (wall_s() - tq) / next;

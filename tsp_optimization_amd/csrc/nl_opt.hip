@@ -1,8 +1,7 @@
 // nl_opt.hip -- candidate neighbour lists: the exact KNN build (tsp_dev_inst_knn_*) and the 2-opt + Or-opt descent over the
 // list neighbourhood (tsp_dev_nl_opt).  The definitions are in include/tsp_hip.h.
 //
-// KNN      k_knn_scan (one lane = one row node, its 16 best (distance, id) sorted in registers, columns in <= 16 chunks)
-//          -> k_knn_merge (one lane = one row: the chunks' lists merged, the first K ids stored).
+// KNN      k_knn_scan (a row scan, row_scan.hpp: each lane keeps its 16 best (distance, id)) -> k_knn_merge (the first K ids stored).
 // Decision k_nl_prep (per node: length of its tour edge, rem of the three segments that start at it) -> k_nl_scan (one
 //          lane = one list entry (v, u): the 2 + 20 moves whose new / attaching edge is {v, u}; one (delta, kind, key) per
 //          workgroup) -> k_nl_pick_apply (the workgroups' candidates, then the move on order/pos; one workgroup per tour).
@@ -13,6 +12,7 @@
 // tsp_nl_write_stats fills the records of all five stats types, told by an NlStatsOut which groups a record has.
 #include "descent.hpp"
 #include "nl_common.hpp"
+#include "row_scan.hpp"
 
 #include <cstddef>
 
@@ -40,7 +40,7 @@ __device__ __forceinline__ void knn_insert(double (&kd)[kK], int (&ki)[kK], doub
 }
 
 // Row node v = one lane, columns [chunk * CH, chunk * CH + CH): pd / pi [(chunk * 16 + s) * n + v] = s-th best of the chunk
-// (+inf, -1 where the chunk has fewer).  The column is wave-uniform: its coordinates come from scalar loads.
+// (+inf, -1 where the chunk has fewer).  The column's coordinates are its record; the distance is taken row first (see pair_dist).
 template <int WT, bool INT>
 __global__ __launch_bounds__(256) void k_knn_scan(const double2 *__restrict__ coord, int n, int CH, double *__restrict__ pd,
                                                   int *__restrict__ pi) {
@@ -597,20 +597,18 @@ int tsp_dev_inst_knn_build(tsp_dev_inst *inst, int K, float *kernel_ms) {
     const int n = inst->n;
     TSP_HIP_TRY(hipSetDevice(inst->ctx->device));
     hipStream_t s = inst->ctx->stream;
-    const int waves = (n + 63) / 64;
-    const int Cc0 = std::max(1, std::min(kKnnChunks, (kKnnWaves + waves - 1) / waves));
-    const int CH = (n + Cc0 - 1) / Cc0, Cc = (n + CH - 1) / CH;
+    const ScanChunks g = scan_chunks(n, kKnnWaves, kKnnChunks, 1);
     DevBuf<double> pd;
     DevBuf<int> pi, nbr;
-    TSP_HIP_TRY(pd.alloc((size_t)Cc * kK * n));
-    TSP_HIP_TRY(pi.alloc((size_t)Cc * kK * n));
+    TSP_HIP_TRY(pd.alloc((size_t)g.Cc * kK * n));
+    TSP_HIP_TRY(pi.alloc((size_t)g.Cc * kK * n));
     TSP_HIP_TRY(nbr.alloc((size_t)n * K));
     if (int e = tsp_inst_events(inst)) return e;
     TSP_HIP_TRY(hipEventRecord(inst->ev0, s));
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-        hipLaunchKernelGGL((k_knn_scan<WTC, INTC>), dim3((n + 255) / 256, Cc), dim3(256), 0, s, inst->d_coord, n, CH, pd.p, pi.p);
+        hipLaunchKernelGGL((k_knn_scan<WTC, INTC>), dim3((n + 255) / 256, g.Cc), dim3(256), 0, s, inst->d_coord, n, g.CH, pd.p, pi.p);
     });
-    hipLaunchKernelGGL(k_knn_merge, dim3((n + 255) / 256), dim3(256), 0, s, n, Cc, K, pd.p, pi.p, nbr.p);
+    hipLaunchKernelGGL(k_knn_merge, dim3((n + 255) / 256), dim3(256), 0, s, n, g.Cc, K, pd.p, pi.p, nbr.p);
     TSP_HIP_TRY(hipEventRecord(inst->ev1, s));
     TSP_HIP_TRY(hipEventSynchronize(inst->ev1));
     TSP_HIP_TRY(hipGetLastError());

@@ -326,6 +326,17 @@ inline double wall_s() {
 }
 }  // namespace tsp
 
+// Everything queued on the stream waited for and a control block copied back: the look a host loop takes between two batches.
+namespace tsp {
+template <typename CTL>
+inline int poll_ctl(hipStream_t s, CTL *host, const CTL *dev) {
+    TSP_HIP_TRY(hipMemcpyAsync(host, dev, sizeof(CTL), hipMemcpyDeviceToHost, s));
+    TSP_HIP_TRY(hipStreamSynchronize(s));
+    TSP_HIP_TRY(hipGetLastError());
+    return TSP_OK;
+}
+}  // namespace tsp
+
 // The instance's reusable pair of timing events, created on first use.
 inline int tsp_inst_events(tsp_dev_inst *inst) {
     if (!inst->ev0) { TSP_HIP_TRY(hipEventCreate(&inst->ev0)); TSP_HIP_TRY(hipEventCreate(&inst->ev1)); }
