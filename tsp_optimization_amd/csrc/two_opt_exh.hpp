@@ -55,7 +55,11 @@
 // does the exact bookkeeping (delta, tie-break on node ids) for the few pairs that reach that bound -- about ln(pairs of the
 // wave) times per wave.  Measured and not kept: a per-lane bound (a wave's 64 RJ pairs per row step held one that beat its
 // own lane's best almost every step: 47.7 us per sweep at RJ = 4); a bound shared by all waves through one word per tour
-// (atomicMin on improvement, re-read every 16 rows: 4 096 waves on one L2 line cost more than the pruning saves, 69.6 us).
+// (atomicMin on improvement, re-read every 16 rows: 4 096 waves on one L2 line cost more than the pruning saves, 69.6 us);
+// the bound tested once per batch of kRowBatch rows instead of once per row (the rows of a batch one basic block, their hit
+// masks OR-ed, one branch; with the stage order of a row kept, with a row's integer tail free to issue among the next row's
+// first stage, and with the rows of a batch scheduled freely: k_exh 29.37 us per launch in every form, as with the branch
+// per row -- the model loop of tools/ubench/dist3.hip promised 15 % of a row step).
 #pragma once
 #include "two_opt_step.hpp"
 #include "exh_arith.hpp"

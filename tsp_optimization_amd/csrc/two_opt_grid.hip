@@ -1011,7 +1011,7 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
             // TSP_EXH_SHARES = per-cent figures (or "0": equal shares), the default measured on MI355X
             t->exh_share[0] = t->exh_share[1] = t->exh_share[2] = t->exh_share[3] = 0;
             t->exh_gens = 0;
-            int pc[4] = {48, 29, 15, 8};   // (tools/exh_shares.sh: 42.2 us per sweep against 43.7 with 52 / 28 / 13 / 7)
+            int pc[4] = {45, 29, 16, 10};   // (tools/exh_shares.sh: 35.7 us per sweep against 36.8 with 48 / 29 / 15 / 8)
             bool on = B == 1;
             const char *e = getenv("TSP_EXH_SHARES");
             if (e && *e) {
