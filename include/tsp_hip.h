@@ -521,6 +521,33 @@ int tsp_dev_ils_dlb(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_st
                     uint64_t seed, int64_t iterations, int span, int64_t max_moves_per_descent, double time_limit_s,
                     int dlb_mode, tsp_ils_dlb_stats *stats);
 
+/* ---- batched list descent (extension): many moves with disjoint arcs per decision ----------------------------------------------
+ * (DESIGN.md 4.19 has the kernels.)  A new descent rule behind a new entry point: tsp_dev_nl_3opt, the don't-look entry points
+ * and tsp_dev_ils keep their trajectories.  Moves, deltas, keys, the order (delta, kind, key), the candidates cand(v) of a node
+ * and the way a move is applied are those above.  Positions are along the successor orientation, modulo n; ahead(p, q) = p - q.
+ * Arc of a move: the cyclic range (start, len) of the positions the move rewrites, extended by the ends of its removed edges.
+ *     2-opt (i, j):        start = pos i, len = ahead(pos j, pos i) + 2                 (i .. j1)
+ *     3-opt (a, b, c, T):  start = pos a, len = ahead(pos c, pos a) + 2                 (a .. c1)
+ *     Or-opt (f, L, a, o): with m1 = ahead(pos a, pos f + L) + 1 nodes s .. a and m2 = n - L - m1 nodes b .. p:
+ *                          m1 <= m2: start = pos f - 1, len = m1 + L + 2 (p .. b);  else start = pos a, len = m2 + L + 2 (a .. s)
+ * len is clipped to n.  Two arcs are disjoint iff ahead(s2, s1) >= len1 and ahead(s1, s2) >= len2.  Both ends of every new and of
+ * every removed edge lie inside the arc and its two end positions keep their nodes, so moves with disjoint arcs commute and the
+ * delta of each, computed before the decision, stays exact.
+ * Decision.  For every node v the candidate is the best (delta, key) of the improving moves of cand(v) whose arc has
+ * len <= max_arc; the overall best move of any arc length is kept beside them.  Up to `rounds` claim rounds run over the live
+ * candidates (at first all): every live candidate claims every position of its arc, a position goes to the smallest (delta, key)
+ * that claims it, a candidate that holds all of its positions is accepted, and the live candidates whose arc meets an accepted
+ * arc die.  What is live after the last round is dropped.  With enough rounds (n at the most) that is the sequential greedy
+ * selection by (delta, key).  Without any candidate the overall best move alone is applied, and without one the descent ends:
+ * the result is a local optimum of the whole list neighbourhood.  max_moves >= 0: the accepted set is cut to its first
+ * max_moves - moves members in (delta, key) order.  `decisions` counts decisions, `moves` moves; the other counters keep their
+ * meaning.  The result does not depend on the order in which the accepted moves are carried out: two runs return the same bits. */
+#define TSP_NL_BATCH_DEFAULT_ROUNDS 2
+/* max_arc <= 0: n / 2 (more than n: n).  rounds <= 0: TSP_NL_BATCH_DEFAULT_ROUNDS (more than n: n).  Everything else, bad arguments
+ * (TSP_DEV_E_ARG, the caller's tours untouched) included, as tsp_dev_nl_3opt. */
+int tsp_dev_nl_3opt_batch(tsp_dev_inst *inst, int kinds, int max_arc, int rounds, int B, int *succ, int succ_stride,
+                          int64_t tour_stride, double *obj, int64_t max_moves, double time_limit_s, tsp_nl3_opt_stats *stats);
+
 /* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
  * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
  * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.

@@ -164,6 +164,12 @@ int HEU_ils_greedy(instance *inst);   /* HEU_greedy + alg_ils */
  * HEU_ils_greedy: TSP_DLB_OFF (the default: the full scan, as before), TSP_DLB_ON or TSP_DLB_CLOSE; else TSP_DEV_E_ARG and the
  * setting stays.  No -method row, as for the other extensions. */
 int tsp_host_set_dlb(int mode);
+/* The batched rule (include/tsp_hip.h, tsp_dev_nl_3opt_batch) for alg_nl_opt, alg_3opt and HEU_nl_*: max_arc < 0 (with rounds 0)
+ * is off, the default: one move per decision, as before.  max_arc >= 0 turns it on: max_arc = 0 is n / 2 and rounds = 0 is
+ * TSP_NL_BATCH_DEFAULT_ROUNDS.  rounds < 0, max_arc < 0 with rounds != 0, or on while tsp_host_set_dlb is not TSP_DLB_OFF:
+ * TSP_DEV_E_ARG and the setting stays; so does tsp_host_set_dlb with a mode other than TSP_DLB_OFF while the batched rule is on.
+ * alg_ils keeps the plain rule.  No -method row, as for the other extensions. */
+int tsp_host_set_batch(int max_arc, int rounds);
 
 /* ---- Held-Karp lower bound (extension; include/tsp_hip.h, tsp_dev_held_karp).  A library entry point only: no solver_type,
  * no -method row.  Runs the ascent on the instance's device handle from zero penalties with TSP_HK_DEFAULT_LAMBDA and the

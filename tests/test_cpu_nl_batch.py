@@ -1,0 +1,228 @@
+"""CPU: the rule of the batched list descent (include/tsp_hip.h, tsp_dev_nl_3opt_batch) as tests/nl_batch_ref.py states it, and the
+arc helper csrc/nl_arc.hpp as the very source text the kernels compile, built with the host compiler (tests/nl_arc_check.cpp).
+
+The reference without candidates is the plain descent move for move; n rounds are the sequential greedy selection; accepted moves
+commute and their deltas add up; every position a move rewrites and every end of a removed edge lies inside its arc."""
+import itertools
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import nl3_opt_ref as N3
+import nl_batch_ref as NB
+from helpers import load_instance, random_tour
+from oracle import oracle as O
+
+NL = N3.NL
+R = NL.R
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "tsp_optimization_amd", "csrc")
+KIND_BITS = (0, 1 << 62, 1 << 63)
+
+
+def _instance(n, seed):
+    rng = np.random.default_rng(seed)
+    xy = rng.integers(0, 1000, size=(n, 2)).astype(np.float64)
+    return xy, O.dist_matrix(xy, O.EUC_2D, 1), random_tour(n, rng)
+
+
+def _cost(D, succ):
+    return int(np.sum(D[np.arange(len(succ)), np.asarray(succ)]))
+
+
+# ---- the rule -----------------------------------------------------------------------------------------------------------------------
+
+def test_the_entry_point_is_exported_and_bound():
+    from tsp_optimization_amd import engine as E
+    assert "tsp_dev_nl_3opt_batch" in E.EXPORTED and hasattr(E.lib(), "tsp_dev_nl_3opt_batch")
+    assert hasattr(E.Instance, "nl_3opt_batch")
+    with open(os.path.join(ROOT, "include", "tsp_hip.h")) as f:
+        assert "#define TSP_NL_BATCH_DEFAULT_ROUNDS %d\n" % E.NL_BATCH_DEFAULT_ROUNDS in f.read()
+
+
+@pytest.mark.parametrize("kinds", [1, 7])
+def test_without_candidates_the_reference_is_the_plain_descent_move_for_move(kinds):
+    xy, wt = load_instance("att48")
+    D = O.dist_matrix(xy, wt, 1)
+    nbr = NL.knn(D, 6)
+    for seed in range(2):
+        start = random_tour(len(xy), np.random.default_rng(seed))
+        t0, t1 = [], []
+        ref, c = N3.descent(D, start, nbr, kinds, trace=t0)
+        got, cb = NB.descent(D, start, nbr, kinds, 0, 2, trace=t1)
+        assert (got == ref).all() and cb == c
+        assert [[m] for m in t0] == t1
+        for cap in (0, 1, 5):
+            ref, c = N3.descent(D, start, nbr, kinds, max_moves=cap)
+            got, cb = NB.descent(D, start, nbr, kinds, 0, 2, max_moves=cap)
+            assert (got == ref).all() and cb == c
+
+
+def test_n_rounds_are_the_sequential_greedy_selection():
+    fewer = 0
+    for n, seed in itertools.product((12, 30, 60), range(4)):
+        xy, D, succ = _instance(n, 100 * n + seed)
+        nbr = NL.knn(D, min(8, n - 1))
+        _, _, pos, _ = NB.tour(succ)
+        for max_arc in (4, 16, n // 2, n):
+            cand, best = NB.candidates(D, succ, nbr, 7, max_arc)
+            want = NB.greedy(cand, pos, n)
+            assert NB.select(cand, pos, n, n) == want
+            one = NB.select(cand, pos, n, 1)
+            assert set(one) <= set(want)                  # a round accepts only what the greedy selection takes
+            fewer += len(one) < len(want)
+            if cand:
+                assert want[0] == min(cand.values()) and best <= want[0]
+    assert fewer > 0                                      # ... and one round is not always enough
+
+
+def test_accepted_moves_commute_and_their_deltas_add_up():
+    batches = 0
+    rng = np.random.default_rng(7)
+    for n in range(5, 41):
+        xy, D, succ = _instance(n, n)
+        nbr = NL.knn(D, min(6, n - 1))
+        _, _, pos, _ = NB.tour(succ)
+        for max_arc, rounds in ((n, 1), (n // 2, 2), (8, n)):
+            moves = NB.decision(D, succ, nbr, 7, max_arc, rounds)
+            if not moves:
+                continue
+            arcs = [NB.arc(m, pos, n) for m in moves]
+            assert all(NB.disjoint(a, b, n) for a, b in itertools.combinations(arcs, 2))
+            batches += len(moves) > 1
+            results = []
+            for order in [list(range(len(moves))), list(range(len(moves)))[::-1]] + [list(rng.permutation(len(moves))) for _ in range(3)]:
+                s = succ
+                for q in order:
+                    s = N3.apply_decision(s, moves[q], N3.new_counters())
+                assert O.is_tour(s)
+                results.append(s)
+            assert all((r == results[0]).all() for r in results)
+            assert _cost(D, results[0]) - _cost(D, succ) == sum(m[0] for m in moves)
+    assert batches > 10
+
+
+# ---- arcs -------------------------------------------------------------------------------------------------------------------------
+
+def _all_moves(D, succ):
+    """every move of the three kinds on the tour, in or out of any list neighbourhood, with whatever delta"""
+    succ, order, pos, pred = NB.tour(succ)
+    n = len(succ)
+    out = []
+    for i in range(n):
+        for j in range(i + 1, n):
+            if j != succ[i] and succ[j] != i:
+                out.append((0.0, 0, i * n + j))
+    for f, L, a, o in itertools.product(range(n), (1, 2, 3), range(n), (0, 1)):
+        if (pos[a] - pos[f] + 1) % n > L and not (o == 1 and L == 1):
+            out.append((0.0, 1, R.key(f, L, a, o, n)))
+    a, b, c = N3.all_triples(succ)
+    for T in range(4):
+        move, _, k, _ = N3._evaluate(D, succ, pos, a, b, c, T)
+        out += [(0.0, 2, int(q)) for q in k[move]]
+    return out
+
+
+@pytest.fixture(scope="module")
+def arc_cases():
+    """(n, start tour, its pos, move) for every move of every kind at n = 5 .. 12"""
+    out = []
+    for n in range(5, 13):
+        xy, D, succ = _instance(n, 50 + n)
+        _, _, pos, _ = NB.tour(succ)
+        out += [(n, succ, pos, m) for m in _all_moves(D, succ)]
+    return out
+
+
+def test_every_rewritten_position_and_every_removed_end_lies_inside_the_arc(arc_cases):
+    kinds, clipped = set(), 0
+    for n, succ, pos, m in arc_cases:
+        _, order, _, pred = NB.tour(succ)
+        start, ln = NB.arc(m, pos, n)
+        assert 4 <= ln <= n
+        inside = set(NB.positions((start, ln), n))
+        assert all(int(pos[v]) in inside for v in NB.removed_ends(m, succ, pred, n)), m
+        new = N3.apply_decision(succ, m, N3.new_counters())
+        assert O.is_tour(new)
+        kinds.add(m[1])
+        clipped += ln == n
+        if ln == n:
+            continue
+        # the node at the arc's first position keeps it; the new tour laid out from there differs inside the arc alone, and not
+        # at its two end positions
+        v = int(order[start])
+        changed = set()
+        for q in range(n):
+            p = (start + q) % n
+            if order[p] != v:
+                changed.add(p)
+            v = int(new[v])
+        assert changed <= inside - {start, (start + ln - 1) % n}, m
+    assert kinds == {0, 1, 2} and clipped > 0
+
+
+@pytest.fixture(scope="module")
+def sources():
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    return [cxx, "-std=c++17", "-ffp-contract=off", "-I", CSRC], os.path.join(ROOT, "tests", "nl_arc_check.cpp")
+
+
+@pytest.fixture(scope="module")
+def commands(arc_cases):
+    """(command text, expected answer)"""
+    out = []
+    for n, succ, pos, m in arc_cases:
+        want = "%d %d" % NB.arc(m, pos, n)
+        out.append(("arc %d %d %s" % (n, m[2] | KIND_BITS[m[1]], " ".join(str(int(p)) for p in pos)), want))
+        if m[1] == 0:
+            out.append(("two %d %d %d" % (n, pos[m[2] // n], pos[m[2] % n]), want))
+        elif m[1] == 2:
+            a, _, c, _ = N3.decode(m[2], n)
+            out.append(("three %d %d %d" % (n, pos[a], pos[c]), want))
+        else:
+            f, L, a, _ = R.decode(m[2], n)
+            out.append(("or %d %d %d %d" % (n, pos[f], pos[a], L), want))
+    # the largest instance the 3-opt kind takes: an arc that wraps, and one clipped to n
+    n = 1 << 20
+    out.append(("two %d %d %d" % (n, n - 1, 0), "%d 3" % (n - 1)))
+    out.append(("three %d %d %d" % (n, 5, 4), "5 %d" % n))
+    rng = np.random.default_rng(11)
+    for n in (5, 6, 9, 16):
+        for _ in range(200):
+            x = (int(rng.integers(n)), int(rng.integers(1, n + 1)))
+            y = (int(rng.integers(n)), int(rng.integers(1, n + 1)))
+            d = NB.disjoint(x, y, n)
+            assert d == (not set(NB.positions(x, n)) & set(NB.positions(y, n)))
+            out.append(("disj %d %d %d %d %d" % ((n,) + x + y), "%d %d" % (d, d)))
+    return out
+
+
+@pytest.fixture(scope="module")
+def results(sources, commands, tmp_path_factory):
+    cmd, src = sources
+    exe = str(tmp_path_factory.mktemp("nl_arc") / "nl_arc_check")
+    subprocess.check_call(cmd + ["-O2", "-o", exe, src])
+    text = "".join(c[0] + "\n" for c in commands)
+    res = subprocess.run([exe], input=text, check=True, capture_output=True, text=True, timeout=300)
+    return res.stdout, text
+
+
+def test_the_arc_helper_gives_the_rules_arcs_and_disjointness(commands, results):
+    lines = results[0].split("\n")[:-1]
+    assert len(lines) == len(commands)
+    for (text, want), line in zip(commands, lines):
+        assert line == want, text
+
+
+def test_the_arc_helper_runs_clean_under_the_address_and_undefined_behaviour_sanitizers(sources, results, tmp_path):
+    """A program of its own, built with the sanitizers and run once on every case: the same answers, no report."""
+    cmd, src = sources
+    exe = str(tmp_path / "nl_arc_check_san")
+    subprocess.check_call(cmd + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
+    res = subprocess.run([exe], input=results[1], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and res.stderr == "", res.stderr[-2000:]
+    assert res.stdout == results[0]

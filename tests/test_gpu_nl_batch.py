@@ -1,0 +1,337 @@
+"""The batched list descent on the device (tsp_dev_nl_3opt_batch) against the CPU reference of the rule in include/tsp_hip.h
+(tests/nl_batch_ref.py): tour, cost and every counter the reference keeps, over arc limits, claim rounds, metrics, sizes from 5
+nodes up, batches of tours, caps that cut a batch, both kind masks; every result is a local optimum of the plain descent and two
+runs return the same bits; a property run at a size without a trajectory reference; the host library's switch."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import nl3_opt_ref as N3
+import nl_batch_ref as NB
+from helpers import HostInstance, Instance, load_instance, rand_instance, random_tour
+from oracle import oracle as O
+
+NL = N3.NL
+pytestmark = pytest.mark.gpu
+
+COUNTERS = ("decisions", "moves", "moves_2opt", "moves_oropt", "moves_by_len", "moves_reversed", "reversed", "moves_3opt",
+            "moves_by_type")
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from tsp_optimization_amd import engine as E
+    assert E.device_count() >= 1, "no HIP device visible: the product path has no CPU fallback"
+    return E
+
+
+@pytest.fixture(scope="module")
+def ctx(eng):
+    c = eng.Context(0)
+    yield c
+    c.close()
+
+
+def _run(inst, succ, **kw):
+    kw.setdefault("time_limit", 300.0)     # a descent that does not end is a failure, not a hang
+    return inst.nl_3opt_batch(succ, **kw)
+
+
+def _same(dev_succ, dev_obj, dev_st, ref_succ, ref_c, D):
+    assert O.is_tour(dev_succ)
+    assert (dev_succ == np.asarray(ref_succ)).all(), "tour differs from the reference"
+    n = len(dev_succ)
+    ref_obj = float(np.sum(D[np.arange(n), np.asarray(ref_succ)]))
+    assert dev_obj == ref_obj or abs(dev_obj - ref_obj) <= 1e-9 * abs(ref_obj), (dev_obj, ref_obj)
+    for k in COUNTERS:
+        assert dev_st[k] == ref_c[k], (k, dev_st[k], ref_c[k])
+
+
+def _follows(eng, inst, D, nbr, start, kinds, max_arc, rounds, max_moves=-1, trace=None):
+    """one device descent against the reference; an uncapped one must end where the plain descent has no move"""
+    n = len(start)
+    ma, ro = NB.normal(n, max_arc, rounds, eng.NL_BATCH_DEFAULT_ROUNDS)
+    ref, c = NB.descent(D, start, nbr, kinds, ma, ro, max_moves=max_moves, trace=trace)
+    rc, s, o, st = _run(inst, start, kinds=kinds, max_arc=max_arc, rounds=rounds, max_moves=max_moves)
+    assert rc == 0
+    _same(s, o, st, ref, c, D)
+    if max_moves < 0:
+        rc, s2, o2, st2 = inst.nl_3opt(s, kinds=kinds, time_limit=300.0)
+        assert rc == 0 and st2["moves"] == 0 and st2["decisions"] == (1 if N3.effective_kinds(kinds, n) else 0) and (s2 == s).all()
+    return st
+
+
+def _wraps(trace, start):
+    """moves of the first decision whose arc runs past position n - 1 (order / pos start at node 0)"""
+    _, _, pos, _ = NB.tour(start)
+    n = len(start)
+    return sum(1 for m in trace[0] if sum(NB.arc(m, pos, n)) > n) if trace else 0
+
+
+# ---- 1. trajectories -------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def kro(eng, ctx):
+    xy, wt = load_instance("kroA100")
+    inst = eng.Instance(ctx, xy, wt, 1)
+    yield inst, xy, wt, O.dist_matrix(xy, wt, 1)
+    inst.close()
+
+
+@pytest.mark.parametrize("arc_of", ["4", "16", "half", "n"])
+@pytest.mark.parametrize("K,start", [(5, "greedy"), (5, "random"), (8, "greedy")])
+def test_kroA100_follows_the_reference(eng, kro, K, start, arc_of):
+    inst, xy, wt, D = kro
+    n = len(xy)
+    inst.knn_build(K)
+    nbr = inst.knn()
+    assert (nbr == NL.knn(D, K)).all()
+    s0 = O.greedy(xy, wt)[1] if start == "greedy" else random_tour(n, np.random.default_rng(K))
+    max_arc = {"4": 4, "16": 16, "half": n // 2, "n": n}[arc_of]
+    batched = 0
+    for rounds in (1, 2, n):
+        for kinds in (1, 7):
+            st = _follows(eng, inst, D, nbr, s0, kinds, max_arc, rounds)
+            batched += st["moves"] > st["decisions"]
+            assert st["deltas_executed"] > 0
+    assert batched > 0
+
+
+def test_kroA100_k8_from_a_random_tour_with_the_defaults(eng, kro):
+    inst, xy, wt, D = kro
+    n = len(xy)
+    inst.knn_build(8)
+    s0 = random_tour(n, np.random.default_rng(8))
+    trace = []
+    st = _follows(eng, inst, D, inst.knn(), s0, 7, 0, 0, trace=trace)          # max_arc = n / 2, the default rounds
+    assert st["moves"] > st["decisions"] and all(st[k] > 0 for k in ("moves_2opt", "moves_oropt", "moves_3opt"))
+    ref, c = NB.descent(D, s0, inst.knn(), 7, n // 2, eng.NL_BATCH_DEFAULT_ROUNDS)
+    assert c["moves"] == st["moves"]
+
+
+@pytest.mark.parametrize("name,K", [("att48", 6), ("burma14", 5)])
+def test_att_and_geo_follow_the_reference(eng, ctx, name, K):
+    xy, wt = load_instance(name)
+    n = len(xy)
+    inst = eng.Instance(ctx, xy, wt, 1)
+    # GEO: the reference's distances are the device's own matrix, as tests/test_gpu_nl3_opt.py takes them
+    D = inst.dist_matrix()[0] if wt == O.GEO else O.dist_matrix(xy, wt, 1)
+    inst.knn_build(K)
+    nbr = inst.knn()
+    wraps = 0
+    for seed in range(3):
+        s0 = random_tour(n, np.random.default_rng(seed))
+        for max_arc, rounds in ((4, 2), (16, 1), (n // 2, n), (n, 2)):
+            for kinds in (1, 7):
+                trace = []
+                _follows(eng, inst, D, nbr, s0, kinds, max_arc, rounds, trace=trace)
+                wraps += _wraps(trace, s0)
+    inst.close()
+    assert wraps > 0
+
+
+@pytest.mark.parametrize("n", [5, 8, 12])
+def test_small_tours_with_full_lists(eng, ctx, n):
+    multi = 0
+    for seed in range(4):
+        rng = np.random.default_rng(40 * n + seed)
+        xy = np.round(rng.uniform(0, 300, size=(n, 2)), 1)
+        D = O.dist_matrix(xy, O.EUC_2D, 1)
+        inst = eng.Instance(ctx, xy, O.EUC_2D, 1)
+        inst.knn_build(n - 1)
+        nbr = inst.knn()
+        s0 = random_tour(n, rng)
+        for max_arc in (4, 16, n // 2, n):
+            for rounds in (1, 2, n):
+                for kinds in (1, 7):
+                    st = _follows(eng, inst, D, nbr, s0, kinds, max_arc, rounds)
+                    multi += st["moves"] > st["decisions"]
+        inst.close()
+    assert multi > 0 or n < 12
+
+
+@pytest.mark.parametrize("max_arc,rounds", [(0, 0), (16, 200)])
+def test_two_hundred_nodes(eng, ctx, max_arc, rounds):
+    n = 200
+    xy = rand_instance(n, seed=200, hi=10000)
+    D = O.dist_matrix(xy, O.EUC_2D, 1)
+    inst = eng.Instance(ctx, xy, O.EUC_2D, 1)
+    inst.knn_build(6)
+    trace = []
+    s0 = random_tour(n, np.random.default_rng(1))
+    st = _follows(eng, inst, D, inst.knn(), s0, 7, max_arc, rounds, trace=trace)
+    inst.close()
+    assert max(len(t) for t in trace) >= 8
+
+
+# ---- 2. batches of tours, caps, determinism ------------------------------------------------------------------------------------------
+
+def test_three_tours_that_end_at_different_decisions(eng, kro):
+    inst, xy, wt, D = kro
+    n = len(xy)
+    inst.knn_build(5)
+    nbr = inst.knn()
+    greedy = O.greedy(xy, wt)[1]
+    done = _run(inst, greedy)[1]                                  # a local optimum: a descent of one decision
+    starts = np.stack([done, greedy, random_tour(n, np.random.default_rng(2))])
+    for max_arc, rounds in ((0, 0), (16, n)):
+        ma, ro = NB.normal(n, max_arc, rounds, eng.NL_BATCH_DEFAULT_ROUNDS)
+        rc, S, Ob, St = _run(inst, starts, max_arc=max_arc, rounds=rounds)
+        assert rc == 0
+        for q in range(3):
+            ref, c = NB.descent(D, starts[q], nbr, 7, ma, ro)
+            _same(S[q], Ob[q], St[q], ref, c, D)
+        assert St[0]["decisions"] == 1 < St[1]["decisions"] < St[2]["decisions"] and St[0]["moves"] == 0
+
+
+def test_max_moves_cuts_a_batch_in_the_middle(eng, kro):
+    inst, xy, wt, D = kro
+    n = len(xy)
+    inst.knn_build(5)
+    nbr = inst.knn()
+    s0 = random_tour(n, np.random.default_rng(5))
+    trace = []
+    NB.descent(D, s0, nbr, 7, n // 2, 2, trace=trace)
+    cut = 0
+    for q, moves in enumerate(trace[:12]):
+        if len(moves) < 3:
+            continue
+        before = sum(len(t) for t in trace[:q])
+        for cap in (before + 1, before + len(moves) - 1):         # the batch loses all but its best move / its worst move
+            st = _follows(eng, inst, D, nbr, s0, 7, n // 2, 2, max_moves=cap)
+            assert st["moves"] == cap and st["decisions"] == q + 1
+            cut += 1
+    assert cut >= 4
+    for cap in (0, 1):
+        _follows(eng, inst, D, nbr, s0, 7, n // 2, 2, max_moves=cap)
+    # three tours under one cap
+    starts = np.stack([random_tour(n, np.random.default_rng(q)) for q in range(3)])
+    rc, S, Ob, St = _run(inst, starts, max_arc=n // 2, rounds=2, max_moves=9)
+    assert rc == 0
+    for q in range(3):
+        ref, c = NB.descent(D, starts[q], nbr, 7, n // 2, 2, max_moves=9)
+        _same(S[q], Ob[q], St[q], ref, c, D)
+
+
+def test_two_runs_return_the_same_bits(eng, ctx):
+    xy, wt = load_instance("pr299")
+    succ = random_tour(len(xy), np.random.default_rng(5))
+    for ic in (1, 0):
+        inst = eng.Instance(ctx, xy, wt, ic)
+        inst.knn_build(8)
+        r1 = _run(inst, succ, max_moves=150)
+        r2 = _run(inst, succ, max_moves=150)
+        assert r1[0] == r2[0] == 0 and r1[3]["moves"] == 150 > r1[3]["decisions"]
+        assert (r1[1] == r2[1]).all() and np.float64(r1[2]).tobytes() == np.float64(r2[2]).tobytes()
+        assert all(r1[3][k] == r2[3][k] for k in COUNTERS + ("deltas_executed",))
+        inst.close()
+
+
+def test_bad_arguments(eng, ctx):
+    n = 50
+    xy = rand_instance(n, seed=50)
+    inst = eng.Instance(ctx, xy, O.EUC_2D, 1)
+    succ = random_tour(n, np.random.default_rng(0))
+    for kinds in (0, 8, -1):
+        with pytest.raises(eng.TspDeviceError, match="-3"):
+            inst.nl_3opt_batch(succ, kinds=kinds)
+    bad = succ.copy()
+    bad[0] = bad[1]
+    with pytest.raises(eng.TspDeviceError, match="-4"):
+        inst.nl_3opt_batch(bad)
+    L = eng.lib()
+    o = np.zeros(1)
+    args = (7, 0, 0, 1, succ.ctypes.data_as(C.POINTER(C.c_int)), 1, n, o.ctypes.data_as(C.POINTER(C.c_double)), -1, -1.0, None)
+    assert L.tsp_dev_nl_3opt_batch(None, *args) == eng.E_ARG
+    assert L.tsp_dev_nl_3opt_batch(inst._h, *(args[:3] + (0,) + args[4:])) == eng.E_ARG          # B = 0
+    assert L.tsp_dev_nl_3opt_batch(inst._h, *(args[:5] + (0,) + args[6:])) == eng.E_ARG          # succ_stride = 0
+    assert L.tsp_dev_nl_3opt_batch(inst._h, *(args[:4] + (None,) + args[5:])) == eng.E_ARG       # no tours
+    # max_arc and rounds beyond n are n; the default lists are built on first use
+    D = O.dist_matrix(xy, O.EUC_2D, 1)
+    rc, s, o2, st = _run(inst, succ, max_arc=10 * n, rounds=10 * n)
+    ref, c = NB.descent(D, succ, inst.knn(), 7, n, n)
+    _same(s, o2, st, ref, c, D)
+    inst.close()
+
+
+# ---- 3. a size without a trajectory reference ---------------------------------------------------------------------------------------
+
+def test_large_property_run(eng, ctx):
+    n, K = 16400, 16
+    xy = rand_instance(n)
+    inst = eng.Instance(ctx, xy, O.EUC_2D, 1)
+    inst.knn_build(K)
+    s0, o0 = inst.greedy_edge()
+    r1 = _run(inst, s0)
+    r2 = _run(inst, s0)
+    rc, s, o, st = r1
+    assert rc == 0 and O.is_tour(s)
+    assert o == O.succ_cost(xy, O.EUC_2D, s) and o < o0
+    assert st["moves"] >= st["decisions"] - 1 and st["moves"] > st["decisions"]
+    assert (r2[1] == s).all() and np.float64(r2[2]).tobytes() == np.float64(o).tobytes()
+    assert all(r2[3][k] == st[k] for k in COUNTERS + ("deltas_executed",))
+    rc, s2, o2, st2 = inst.nl_3opt(s, time_limit=300.0)
+    assert rc == 0 and st2["moves"] == 0 and (s2 == s).all()
+    inst.close()
+
+
+# ---- 4. the host library ------------------------------------------------------------------------------------------------------------
+
+def test_host_library_switch(eng, ctx):
+    from tsp_optimization_amd.build import lib_path
+    L = C.CDLL(lib_path("libtsp_host.so"))
+    for f in ("alg_3opt", "alg_nl_opt", "HEU_greedy"):
+        getattr(L, f).argtypes = [C.POINTER(Instance)]
+    L.tsp_host_set_knn.argtypes = [C.c_int]
+    L.tsp_host_set_dlb.argtypes = [C.c_int]
+    L.tsp_host_set_batch.argtypes = [C.c_int, C.c_int]
+    L.tsp_host_last_nl3_stats.argtypes = [C.POINTER(eng.Nl3OptStats)]
+    L.tsp_host_last_nl_stats.argtypes = [C.POINTER(eng.NlOptStats)]
+    try:
+        h = HostInstance("kroA100")
+        n = h.n
+        D = O.dist_matrix(h.xy, h.wt, 1)
+        assert L.tsp_host_set_knn(6) == 0
+        inst = eng.Instance(ctx, h.xy, h.wt, 1)
+        inst.knn_build(6)
+        greedy = O.greedy(h.xy, h.wt)[1]
+        # off (the default): today's alg_3opt
+        assert L.HEU_greedy(C.byref(h.c)) == 0 and L.alg_3opt(C.byref(h.c)) == 0
+        rc, s, o, st = inst.nl_3opt(greedy, time_limit=300.0)
+        assert (h.succ == s).all() and h.obj == o
+        ref, c = N3.descent(D, greedy, NL.knn(D, 6), 7)
+        assert (h.succ == ref).all()
+        # on: the Python path's tour and counters
+        for max_arc, rounds in ((0, 0), (16, 3)):
+            assert L.tsp_host_set_batch(max_arc, rounds) == 0
+            assert L.HEU_greedy(C.byref(h.c)) == 0 and L.alg_3opt(C.byref(h.c)) == 0
+            rc, s, o, st = _run(inst, greedy, max_arc=max_arc, rounds=rounds)
+            assert rc == 0 and (h.succ == s).all() and h.obj == o
+            hs = eng.Nl3OptStats()
+            L.tsp_host_last_nl3_stats(C.byref(hs))
+            assert all(hs.as_dict()[k] == st[k] for k in COUNTERS) and st["moves"] > st["decisions"]
+            assert L.HEU_greedy(C.byref(h.c)) == 0 and L.alg_nl_opt(C.byref(h.c)) == 0
+            rc, s, o, st = _run(inst, greedy, kinds=3, max_arc=max_arc, rounds=rounds)
+            assert rc == 0 and (h.succ == s).all() and h.obj == o
+            hn = eng.NlOptStats()
+            L.tsp_host_last_nl_stats(C.byref(hn))
+            assert all(hn.as_dict()[k] == st[k] for k in COUNTERS[:7])
+        # the argument errors: negative rounds, rounds with off, don't-look bits with the batched rule either way round
+        assert L.tsp_host_set_batch(0, -1) == eng.E_ARG and L.tsp_host_set_batch(-1, 2) == eng.E_ARG
+        assert L.tsp_host_set_dlb(eng.DLB_ON) == eng.E_ARG and L.tsp_host_set_dlb(eng.DLB_CLOSE) == eng.E_ARG
+        assert L.tsp_host_set_dlb(eng.DLB_OFF) == 0
+        assert L.tsp_host_set_batch(-1, 0) == 0
+        assert L.tsp_host_set_dlb(eng.DLB_ON) == 0
+        assert L.tsp_host_set_batch(0, 0) == eng.E_ARG and L.tsp_host_set_batch(16, 2) == eng.E_ARG
+        assert L.tsp_host_set_batch(-1, 0) == 0                     # off stays allowed
+        assert L.tsp_host_set_dlb(eng.DLB_OFF) == 0
+        # off again: the plain trajectory
+        assert L.HEU_greedy(C.byref(h.c)) == 0 and L.alg_3opt(C.byref(h.c)) == 0
+        assert (h.succ == ref).all()
+        inst.close()
+    finally:
+        L.tsp_host_set_dlb(0)
+        L.tsp_host_set_batch(-1, 0)
+        L.tsp_host_set_knn(eng.NL_DEFAULT_K)
+        L.tsp_host_shutdown()

@@ -28,12 +28,14 @@ __device__ __forceinline__ unsigned pair_slots(int s, int t) { return ((unsigned
 __device__ __forceinline__ bool same_edge(int x, int y, int p, int u) { return (x == p && y == u) || (x == u && y == p); }
 
 // One lane per list entry (p, k1), u = nbr[p][k1], q = succ p: the moves that remove (p, q) and add {p, u} and {q, w}, w in N(q).
-// DLB: the lanes of the active nodes alone, as k_nl_scan<.., true> of nl_opt.hip maps and reports them.
-template <int WT, bool INT, bool DLB>
+// DLB: the lanes of the active nodes alone, as k_nl_scan<.., true> of nl_opt.hip maps and reports them.  PN: the per-node form,
+// as k_nl_scan<.., false, true> (the owner of a lane is p).
+template <int WT, bool INT, bool DLB, bool PN = false>
 __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ coord, const int *__restrict__ orders,
                                                   const int *__restrict__ poss, NlState *__restrict__ st, int n, int K,
                                                   const int *__restrict__ nbr, const double *__restrict__ Es,
-                                                  NlBest *__restrict__ parts, NlDlb dlb) {
+                                                  NlBest *__restrict__ parts, NlDlb dlb, NlPn pn) {
+    static_assert(!(DLB && PN), "the per-node form has no active sets");
     const int bt = blockIdx.y;
     if (st[bt].done) return;
     long long lanes = (long long)n * K;
@@ -48,10 +50,14 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
     double bd = INFINITY;
     u64 bk = kNoKey;
     unsigned cnt = 0;
+    double cd = INFINITY;   // PN: the lane's best move of a short arc
+    u64 ck = kNoKey;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < lanes) {
-        int p = (int)(t / K);
-        long long e = t;
+    bool on = t < lanes;
+    int p = (int)(t / K);
+    long long e = t;
+    if constexpr (PN) on = nl_pn_lane(n, K, &p, &e);
+    if (on) {
         if constexpr (DLB) {
             e = t - (long long)p * K;
             p = dlb.list[(size_t)bt * n + p];
@@ -119,12 +125,19 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
                         const double delta = ((e1 + e2) + e3) - old;
                         cnt += 1;
                         offer(delta, kNl3Bit | (key0 + (u64)Tq), bd, bk);
+                        if constexpr (PN)   // a .. c1: positions pA .. pA + oc + 1
+                            if (arc_make(pA, oc + 2, n).len <= pn.max_arc) offer(delta, kNl3Bit | (key0 + (u64)Tq), cd, ck);
                     }
                 }
             }
         }
         if constexpr (DLB)
             if (bk != kNoKey) dlb.hit[(size_t)bt * n + p] = 1;
+    }
+    if constexpr (PN) {
+        __shared__ double pd[256];
+        __shared__ u64 pk[256];
+        nl_pn_reduce(cd, ck, on, K, p, pn.cand + (size_t)bt * n, pn.merge, pd, pk);
     }
     block_argmin<true>(bd, bk, sd, sk);
     if (threadIdx.x == 0) parts[(size_t)bt * gridDim.x + blockIdx.x] = NlBest{bd, bk};
@@ -140,8 +153,16 @@ void tsp_nl3_launch_scan(tsp_dev_tours *t, NlData *x, NlBest *parts3, int dlb_mo
     TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
         TSP_DISPATCH_DLB(dlb_mode, {
             hipLaunchKernelGGL((k_nl3_scan<WTC, INTC, DLBC>), dim3(x->nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord,
-                               t->d_order, t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3, x->dlb(dlb_mode));
+                               t->d_order, t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3, x->dlb(dlb_mode), NlPn{});
         });
+    });
+}
+
+void tsp_nl3_launch_scan_pn(tsp_dev_tours *t, NlData *x, int nparts, NlBest *parts3, const NlPn &pn) {
+    tsp_dev_inst *inst = t->inst;
+    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
+        hipLaunchKernelGGL((k_nl3_scan<WTC, INTC, false, true>), dim3(nparts, t->B), dim3(256), 0, inst->ctx->stream, inst->d_coord,
+                           t->d_order, t->d_pos, x->d_st, t->n, x->K, x->d_nbr, x->d_E, parts3, x->dlb(0), pn);
     });
 }
 

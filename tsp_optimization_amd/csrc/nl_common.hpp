@@ -1,9 +1,11 @@
 // nl_common.hpp -- what the list descents share: nl_opt.hip (2-opt + Or-opt, tsp_dev_nl_opt) and nl3_opt.hip (those two and the
 // 3-opt kind, tsp_dev_nl_3opt).  The decision word, the per-tour state, the symmetric distance, the reversal of a forward path on
 // order/pos, the lists and scratch of an instance, where a call's stats records go (NlStatsOut), the hooks and the DLB dispatch of
-// the launches, and the host functions the files call in each other (ils.hip too).
+// the launches, the move itself (nl_apply_move), the per-node scan form and the scratch of the batched descent (nl_batch.hip), and
+// the host functions the files call in each other (ils.hip too).
 #pragma once
 #include "descent.hpp"
+#include "nl_arc.hpp"
 #include "or_opt_shift.hpp"
 
 #pragma clang fp contract(off)
@@ -40,6 +42,23 @@ struct NlDlb {
     int mode;             // TSP_DLB_ON or TSP_DLB_CLOSE
 };
 
+// The per-node form of the scans (batched descent): cand[b n + v] = the best (delta, key) that the K lanes of
+// node v offer over the moves whose arc (nl_arc.hpp) has at most max_arc positions, (+inf, kNoKey) when there is none.  merge:
+// the slot already holds the candidate of the scan before this one.
+struct NlPn {
+    NlBest *cand;
+    int max_arc;
+    int merge;
+};
+
+// Per-tour control words of a batched decision (nl_batch.hip).
+struct NlbCtl {
+    int nacc;     // accepted moves appended by the claim rounds of this decision
+    int napply;   // entries of the tour's row of the accepted list that k_nlb_apply carries out
+    int keep;     // >= 0: only the `keep` smallest of them by (delta, key) (max_moves cuts the batch)
+    int pad;
+};
+
 // Per-chain state of the iterated local search (ils.hip), written by thread 0 of k_ils_step.
 struct alignas(16) IlsState {
     long long it;              // iterations completed; -1 until the first descent has ended
@@ -73,6 +92,92 @@ __device__ __forceinline__ void nl_reverse_path(int *__restrict__ order, int *__
     }
 }
 
+// The move `bk` of whichever kind on order/pos and in the counters.  Called by every thread of the one workgroup (NT threads) that
+// owns the tour, with nothing of the tour written since the last barrier.
+template <int NT>
+__device__ __forceinline__ void nl_apply_move(int *__restrict__ order, int *__restrict__ pos, NlState &S, int n, u64 bk) {
+    const int tid = threadIdx.x;
+    if (bk & kNl3Bit) {
+        const u64 key = bk & (kNl3Bit - 1);
+        const int T = (int)(key & 3);
+        const u64 abc = key >> 2;
+        const int c = (int)(abc % (u64)n), b = (int)((abc / (u64)n) % (u64)n), a = (int)(abc / ((u64)n * (u64)n));
+        const int pa = pos[a];
+        const int s1 = ahead(pos[b], pa, n), s2 = ahead(pos[c], pa, n) - s1;
+        const int at1 = or_wrap(pa + 1, n), at2 = or_wrap(at1 + s1, n);   // where S1 = a1 .. b and S2 = b1 .. c start
+        __syncthreads();   // every thread has read the tour before anything moves
+        if (tid == 0) {
+            S.moves += 1; S.moves_3opt += 1; S.moves_type[T] += 1;
+            if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
+        }
+        if (T <= 1) {          // S1 and S2 each reversed; type 0: then the two together, which leaves S2 S1
+            nl_reverse_path<NT>(order, pos, n, at1, s1);
+            nl_reverse_path<NT>(order, pos, n, at2, s2);
+            if (T == 0) {
+                __syncthreads();
+                nl_reverse_path<NT>(order, pos, n, at1, s1 + s2);
+            }
+        } else {               // the two together (S2' S1'), then its second part (type 2: S2' S1) or its first (type 3: S2 S1')
+            nl_reverse_path<NT>(order, pos, n, at1, s1 + s2);
+            __syncthreads();
+            if (T == 2) nl_reverse_path<NT>(order, pos, n, or_wrap(at1 + s2, n), s1);
+            else nl_reverse_path<NT>(order, pos, n, at1, s2);
+        }
+        return;
+    }
+    if (!(bk & kNlOrBit)) {
+        // 2-opt: the forward path i1 .. j (positions pi + 1 .. pi + len) is reversed in place
+        const int i = (int)(bk / (u64)n), j = (int)(bk % (u64)n);
+        const int pi = pos[i];
+        const int len = ahead(pos[j], pi, n);
+        __syncthreads();
+        if (tid == 0) {
+            S.moves += 1; S.moves_2opt += 1; S.reversed += len - 1;   // the successors rewritten: all of the path but i1's
+            if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
+        }
+        nl_reverse_path<NT>(order, pos, n, or_wrap(pi + 1, n), len);
+        return;
+    }
+    const OrMove mv = or_unkey(bk & (kNlOrBit - 1), n);
+    const int L = mv.L, o = mv.o;
+    const int i = pos[mv.f], ja = pos[mv.a];
+    int x[3] = {0, 0, 0};
+    for (int q = 0; q < L; ++q) x[q] = order[or_wrap(i + q, n)];
+    __syncthreads();   // every thread has read the tour before anything moves
+    if (tid == 0) {
+        S.moves += 1; S.moves_oropt += 1; S.moves_len[L - 1] += 1; S.moves_rev += o;
+        if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
+    }
+    or_shift_apply<NT>(order, pos, n, i, ja, L, o, x);
+}
+
+// The lanes of the per-node scan forms: thread tid of workgroup wg is lane tid % K of node wg * (256 / K) + tid / K; the threads
+// behind the workgroup's last whole node, and the nodes behind n - 1, have no lane.
+__device__ __forceinline__ bool nl_pn_lane(int n, int K, int *v, long long *e) {
+    const int npw = 256 / K, loc = (int)threadIdx.x / K;
+    *v = (int)blockIdx.x * npw + loc;
+    *e = (long long)*v * K + ((int)threadIdx.x - loc * K);
+    return loc < npw && *v < n;
+}
+
+// ... and their reduction to one candidate per node: every thread of the workgroup calls it with its lane's best short-arc move
+// ((+inf, kNoKey) without one, or without a lane); the node's first lane folds the K of them and writes or merges the slot.
+__device__ __forceinline__ void nl_pn_reduce(double cd, u64 ck, bool on, int K, int v, NlBest *__restrict__ cand, int merge,
+                                             double *pd, u64 *pk) {
+    const int tid = threadIdx.x;
+    pd[tid] = cd; pk[tid] = ck;
+    __syncthreads();
+    if (on && tid % K == 0) {
+        for (int k = 1; k < K; ++k)
+            if (pk[tid + k] != kNoKey && better(pd[tid + k], pk[tid + k], cd, ck)) { cd = pd[tid + k]; ck = pk[tid + k]; }
+        if (merge) {
+            const NlBest q = cand[v];
+            if (q.k != kNoKey && better(q.d, q.k, cd, ck)) { cd = q.d; ck = q.k; }
+        }
+        cand[v] = NlBest{cd, ck};
+    }
+}
+
 // Lists and scratch of one instance.
 struct NlData {
     int K = 0;                 // 0: no lists
@@ -90,6 +195,14 @@ struct NlData {
     unsigned char *d_act = nullptr, *d_hit = nullptr;
     int *d_alist = nullptr;
     NlDlb dlb(int mode) const { return NlDlb{d_act, d_hit, d_alist, mode}; }
+    // batched descent (nl_batch.hip), allocated by the first batched call at this B: the per-node candidates and the accepted
+    // list (B x n each), the claim words (B x n images of delta, then B x n keys), the taken map (B x n), the control words
+    // and the overall candidates of the per-node scans (B x bparts of k_nl_scan, then of k_nl3_scan)
+    NlBest *d_cand = nullptr, *d_acc = nullptr, *d_bpart = nullptr;
+    u64 *d_clm = nullptr;
+    int *d_taken = nullptr;
+    NlbCtl *d_bctl = nullptr;
+    int bparts = 0;
     void free_scratch() {
         (void)hipFree(d_st); (void)hipHostFree(h_st); (void)hipFree(d_E); (void)hipFree(d_rem); (void)hipFree(d_cost);
         (void)hipFree(d_part); (void)hipFree(d_inc); (void)hipFree(d_ils); (void)hipHostFree(h_ils);
@@ -97,6 +210,9 @@ struct NlData {
         d_inc = nullptr; d_ils = nullptr; h_ils = nullptr;
         (void)hipFree(d_act); (void)hipFree(d_hit); (void)hipFree(d_alist);
         d_act = d_hit = nullptr; d_alist = nullptr;
+        (void)hipFree(d_cand); (void)hipFree(d_acc); (void)hipFree(d_bpart); (void)hipFree(d_clm); (void)hipFree(d_taken);
+        (void)hipFree(d_bctl);
+        d_cand = d_acc = d_bpart = nullptr; d_clm = nullptr; d_taken = nullptr; d_bctl = nullptr; bparts = 0;
     }
     ~NlData() { free_scratch(); (void)hipFree(d_nbr); }
 };
@@ -137,6 +253,10 @@ void tsp_nl_write_stats(const tsp::NlStatsOut &out, int b, const tsp::NlState &z
 // nl3_opt.hip: k_nl3_scan of every tour that is not done, one candidate per workgroup in parts3 (B x nparts); dlb_mode != 0: over
 // the lanes of the active nodes alone
 void tsp_nl3_launch_scan(tsp_dev_tours *t, tsp::NlData *x, tsp::NlBest *parts3, int dlb_mode);
+// nl_opt.hip, nl3_opt.hip: the per-node forms (NlPn) of k_nl_prep + k_nl_scan and of k_nl3_scan for the batched descent: a workgroup
+// owns 256 / K whole nodes, grid x = nparts workgroups a tour, one overall candidate per workgroup in parts (B x nparts)
+void tsp_nl_launch_scan_pn(tsp_dev_tours *t, tsp::NlData *x, int kinds, int nparts, tsp::NlBest *parts, const tsp::NlPn &pn);
+void tsp_nl3_launch_scan_pn(tsp_dev_tours *t, tsp::NlData *x, int nparts, tsp::NlBest *parts3, const tsp::NlPn &pn);
 // nl_opt.hip: the argument checks of a list descent; *kinds loses the kinds without a move at the instance's size
 int tsp_nl_check(const tsp_dev_inst *inst, int *kinds, int allowed, int B, const int *succ, int succ_stride, int64_t tour_stride,
                  const double *obj);

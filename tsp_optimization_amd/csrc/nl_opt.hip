@@ -109,8 +109,8 @@ __global__ void k_nl_prep(const double2 *__restrict__ coord, const int *__restri
     rem[2 * n + v] = (dpf + dsym<WT, INT>(coord, v2, v3)) - dsym<WT, INT>(coord, pm, v3);
 }
 
-// What a lane of k_nl_scan reads the tour through.
-template <int WT, bool INT>
+// What a lane of k_nl_scan reads the tour through.  PN: the lane also keeps its best move of an arc of at most max_arc positions.
+template <int WT, bool INT, bool PN = false>
 struct NlView {
     const double2 *coord;
     const int *order, *pos;
@@ -119,6 +119,9 @@ struct NlView {
     double bd;
     u64 bk;
     unsigned cnt;
+    int max_arc;
+    double cd;
+    u64 ck;
 
     __device__ __forceinline__ int at(int p) const { return order[or_wrap(p, n)]; }
     __device__ __forceinline__ double d(int u, int v) const { return dsym<WT, INT>(coord, u, v); }
@@ -132,6 +135,8 @@ struct NlView {
         const double delta = ((dij + d11) - E[x]) - E[y];
         cnt += 1;
         offer(delta, (u64)x * (u64)n + (u64)y, bd, bk);
+        if constexpr (PN)
+            if (nl_arc_two(px, py, n).len <= max_arc) offer(delta, (u64)x * (u64)n + (u64)y, cd, ck);
     }
 
     // Or-opt move (f, L, a, o); `known` says which attaching edge has the length dk: 0 = the one at a, 1 = the one at b
@@ -146,6 +151,8 @@ struct NlView {
         const double delta = ((d1 + d2) - E[a]) - rem[(size_t)(L - 1) * n + f];
         cnt += 1;
         offer(delta, kNlOrBit | or_key(f, L, a, o, n), bd, bk);
+        if constexpr (PN)
+            if (nl_arc_or(pf, pa, L, n).len <= max_arc) offer(delta, kNlOrBit | or_key(f, L, a, o, n), cd, ck);
     }
 
     // the ten Or-opt moves that attach the segment with the edge x -> y (x ahead of y in the new tour)
@@ -169,11 +176,15 @@ struct NlView {
 // DLB: the same lanes of the active nodes alone, lane t = (slot t / K of the tour's list, k = t % K), on the same grid: a
 // workgroup whose first lane lies beyond |A| K returns (and writes no candidate), and a lane that holds an improving move
 // says so in hit[v].
-template <int WT, bool INT, bool DLB>
+// PN (without DLB): the per-node form of the batched descent, lanes as nl_pn_lane deals them, and behind the lane loop one
+// candidate per node over the moves of a short arc (NlPn); the workgroup's overall candidate is written all the same.
+template <int WT, bool INT, bool DLB, bool PN = false>
 __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coord, const int *__restrict__ orders,
                                                  const int *__restrict__ poss, NlState *__restrict__ st, int n, int K, int kinds,
                                                  const int *__restrict__ nbr, const double *__restrict__ Es,
-                                                 const double *__restrict__ rems, NlBest *__restrict__ parts, NlDlb dlb) {
+                                                 const double *__restrict__ rems, NlBest *__restrict__ parts, NlDlb dlb,
+                                                 NlPn pn) {
+    static_assert(!(DLB && PN), "the per-node form has no active sets");
     const int b = blockIdx.y;
     if (st[b].done) return;
     long long lanes = (long long)n * K;
@@ -183,14 +194,17 @@ __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coo
     }
     __shared__ double sd[4];
     __shared__ u64 sk[4];
-    NlView<WT, INT> w;
+    NlView<WT, INT, PN> w;
     w.coord = coord; w.order = orders + (size_t)b * n; w.pos = poss + (size_t)b * n;
     w.E = Es + (size_t)b * n; w.rem = rems + (size_t)b * 3 * n; w.n = n;
     w.bd = INFINITY; w.bk = kNoKey; w.cnt = 0;
+    w.max_arc = pn.max_arc; w.cd = INFINITY; w.ck = kNoKey;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < lanes) {
-        int v = (int)(t / K);
-        long long e = t;
+    bool on = t < lanes;
+    int v = (int)(t / K);
+    long long e = t;
+    if constexpr (PN) on = nl_pn_lane(n, K, &v, &e);
+    if (on) {
         if constexpr (DLB) {
             e = t - (long long)v * K;
             v = dlb.list[(size_t)b * n + v];
@@ -213,6 +227,11 @@ __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coo
         if constexpr (DLB)
             if (w.bk != kNoKey) dlb.hit[(size_t)b * n + v] = 1;
     }
+    if constexpr (PN) {
+        __shared__ double pd[256];
+        __shared__ u64 pk[256];
+        nl_pn_reduce(w.cd, w.ck, on, K, v, pn.cand + (size_t)b * n, pn.merge, pd, pk);
+    }
     double bd = w.bd;
     u64 bk = w.bk;
     block_argmin<true>(bd, bk, sd, sk);
@@ -220,65 +239,6 @@ __global__ __launch_bounds__(256) void k_nl_scan(const double2 *__restrict__ coo
     unsigned long long cnt = w.cnt;
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd((unsigned long long *)&st[b].deltas, cnt);
-}
-
-// The move `bk` of whichever kind on order/pos and in the counters.  Called by every thread of the one workgroup (NT threads) that
-// owns the tour, with nothing of the tour written since the last barrier.
-template <int NT>
-__device__ __forceinline__ void nl_apply_move(int *__restrict__ order, int *__restrict__ pos, NlState &S, int n, u64 bk) {
-    const int tid = threadIdx.x;
-    if (bk & kNl3Bit) {
-        const u64 key = bk & (kNl3Bit - 1);
-        const int T = (int)(key & 3);
-        const u64 abc = key >> 2;
-        const int c = (int)(abc % (u64)n), b = (int)((abc / (u64)n) % (u64)n), a = (int)(abc / ((u64)n * (u64)n));
-        const int pa = pos[a];
-        const int s1 = ahead(pos[b], pa, n), s2 = ahead(pos[c], pa, n) - s1;
-        const int at1 = or_wrap(pa + 1, n), at2 = or_wrap(at1 + s1, n);   // where S1 = a1 .. b and S2 = b1 .. c start
-        __syncthreads();   // every thread has read the tour before anything moves
-        if (tid == 0) {
-            S.moves += 1; S.moves_3opt += 1; S.moves_type[T] += 1;
-            if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
-        }
-        if (T <= 1) {          // S1 and S2 each reversed; type 0: then the two together, which leaves S2 S1
-            nl_reverse_path<NT>(order, pos, n, at1, s1);
-            nl_reverse_path<NT>(order, pos, n, at2, s2);
-            if (T == 0) {
-                __syncthreads();
-                nl_reverse_path<NT>(order, pos, n, at1, s1 + s2);
-            }
-        } else {               // the two together (S2' S1'), then its second part (type 2: S2' S1) or its first (type 3: S2 S1')
-            nl_reverse_path<NT>(order, pos, n, at1, s1 + s2);
-            __syncthreads();
-            if (T == 2) nl_reverse_path<NT>(order, pos, n, or_wrap(at1 + s2, n), s1);
-            else nl_reverse_path<NT>(order, pos, n, at1, s2);
-        }
-        return;
-    }
-    if (!(bk & kNlOrBit)) {
-        // 2-opt: the forward path i1 .. j (positions pi + 1 .. pi + len) is reversed in place
-        const int i = (int)(bk / (u64)n), j = (int)(bk % (u64)n);
-        const int pi = pos[i];
-        const int len = ahead(pos[j], pi, n);
-        __syncthreads();
-        if (tid == 0) {
-            S.moves += 1; S.moves_2opt += 1; S.reversed += len - 1;   // the successors rewritten: all of the path but i1's
-            if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
-        }
-        nl_reverse_path<NT>(order, pos, n, or_wrap(pi + 1, n), len);
-        return;
-    }
-    const OrMove mv = or_unkey(bk & (kNlOrBit - 1), n);
-    const int L = mv.L, o = mv.o;
-    const int i = pos[mv.f], ja = pos[mv.a];
-    int x[3] = {0, 0, 0};
-    for (int q = 0; q < L; ++q) x[q] = order[or_wrap(i + q, n)];
-    __syncthreads();   // every thread has read the tour before anything moves
-    if (tid == 0) {
-        S.moves += 1; S.moves_oropt += 1; S.moves_len[L - 1] += 1; S.moves_rev += o;
-        if (S.max_moves >= 0 && S.moves >= S.max_moves) S.done = 1;
-    }
-    or_shift_apply<NT>(order, pos, n, i, ja, L, o, x);
 }
 
 // ends(m): the tails and heads of the edges that move `bk` removes, read from the tour before the move (scalars, not an array:
@@ -462,13 +422,26 @@ void tsp_nl_launch_decision(tsp_dev_tours *t, NlData *x, int kinds, int dlb_mode
         if (low)
             TSP_DISPATCH_DLB(dlb_mode, {
                 hipLaunchKernelGGL((k_nl_scan<WTC, INTC, DLBC>), dim3(x->nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order,
-                                   t->d_pos, x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part, x->dlb(dlb_mode));
+                                   t->d_pos, x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, x->d_part, x->dlb(dlb_mode), NlPn{});
             });
     });
     if (three) tsp_nl3_launch_scan(t, x, parts3, dlb_mode);
     TSP_DISPATCH_DLB(dlb_mode, {
         hipLaunchKernelGGL(k_nl_pick_apply<DLBC>, dim3(B), dim3(kNlPickThreads), 0, s, t->d_order, t->d_pos, x->d_st, n, x->nparts,
                            low ? x->d_part : nullptr, three ? parts3 : nullptr, x->K, x->dlb(dlb_mode));
+    });
+}
+
+void tsp_nl_launch_scan_pn(tsp_dev_tours *t, NlData *x, int kinds, int nparts, NlBest *parts, const NlPn &pn) {
+    tsp_dev_inst *inst = t->inst;
+    hipStream_t s = inst->ctx->stream;
+    const int n = t->n, B = t->B;
+    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
+        hipLaunchKernelGGL((k_nl_prep<WTC, INTC>), dim3((n + 255) / 256, B), dim3(256), 0, s, inst->d_coord, t->d_order, x->d_st, n,
+                           x->d_E, x->d_rem);
+        if (kinds & (TSP_NL_2OPT | TSP_NL_OROPT))
+            hipLaunchKernelGGL((k_nl_scan<WTC, INTC, false, true>), dim3(nparts, B), dim3(256), 0, s, inst->d_coord, t->d_order,
+                               t->d_pos, x->d_st, n, x->K, kinds, x->d_nbr, x->d_E, x->d_rem, parts, x->dlb(0), pn);
     });
 }
 

@@ -16,6 +16,7 @@ E_ARG = -3
 NL_2OPT, NL_OROPT = 1, 2
 NL_3OPT = 4   # tsp_dev_nl_3opt only
 DLB_OFF, DLB_ON, DLB_CLOSE = 0, 1, 2   # don't-look bits of nl_3opt and ils
+NL_BATCH_DEFAULT_ROUNDS = 2            # claim rounds of nl_3opt_batch (TSP_NL_BATCH_DEFAULT_ROUNDS)
 NL_MAX_K, NL_DEFAULT_K = 16, 10
 HK_DEFAULT_ITERS, HK_DEFAULT_LAMBDA = 300, 2.0
 ALPHA_DEFAULT_K = 5
@@ -178,6 +179,8 @@ def lib():
                                           C.c_double, C.POINTER(NlDlbStats)]
         L.tsp_dev_ils_dlb.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_uint64, C.c_int64, C.c_int, C.c_int64,
                                       C.c_double, C.c_int, C.POINTER(IlsDlbStats)]
+        L.tsp_dev_nl_3opt_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double,
+                                            C.POINTER(Nl3OptStats)]
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
@@ -208,6 +211,7 @@ EXPORTED = [
     "tsp_dev_one_tree", "tsp_dev_held_karp",
     "tsp_dev_inst_alpha_build", "tsp_dev_alpha_rows",
     "tsp_dev_greedy_edge",
+    "tsp_dev_nl_3opt_batch",
 ]
 
 COMM_ID_BYTES = 128
@@ -445,6 +449,19 @@ class Instance:
         else:
             st = (Nl3OptStats * B)()
             rc = lib().tsp_dev_nl_3opt(self._h, int(kinds), *tours, int(max_moves), time_limit, st)
+        return _result(rc, single, succ2, o, st)
+
+    def nl_3opt_batch(self, succ, obj=None, kinds=NL_2OPT | NL_OROPT | NL_3OPT, max_arc=0, rounds=0, max_moves=-1, time_limit=-1.0):
+        """The batched list descent (tsp_dev_nl_3opt_batch): every decision applies the improving moves of pairwise disjoint arcs
+        that `rounds` claim rounds accept among the per-node candidates of an arc of at most max_arc positions (max_arc <= 0: n / 2;
+        rounds <= 0: NL_BATCH_DEFAULT_ROUNDS).  succ [n] or [B,n].  -> (status, succ', obj' (recomputed cost), stats dict(s)) as
+        nl_3opt"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = _obj(obj, B)
+        st = (Nl3OptStats * B)()
+        rc = lib().tsp_dev_nl_3opt_batch(self._h, int(kinds), int(max_arc), int(rounds), B, _i(succ2), 1, n, _d(o), int(max_moves),
+                                         time_limit, st)
         return _result(rc, single, succ2, o, st)
 
     # -- iterated local search (extension) ---------------------------------------------------

@@ -144,6 +144,7 @@ static __thread tsp_ils_stats t_ils_stats;     /* the winning chain of the last 
 static __thread int64_t t_dlb_active, t_dlb_closing;   /* active_nodes, closing_scans of the last alg_3opt or alg_ils */
 static int g_ils_iters = 100, g_ils_span = 50, g_ils_chains = 1;   /* tsp_host_set_ils */
 static int g_dlb = TSP_DLB_OFF;                /* don't-look bits of alg_3opt and alg_ils (tsp_host_set_dlb) */
+static int g_batch_arc = -1, g_batch_rounds;   /* the batched rule of alg_nl_opt and alg_3opt (tsp_host_set_batch); < 0: off */
 static int g_knn_k = TSP_NL_DEFAULT_K;         /* list length of alg_nl_opt (tsp_host_set_knn) */
 static int g_alpha_k = 0, g_alpha_iters = 0;   /* alpha lists instead (tsp_host_set_alpha); 0 = nearest-neighbour lists */
 
@@ -590,9 +591,28 @@ static int lists_locked(instance *inst, tsp_dev_inst *dev, double obj) {
 int tsp_host_set_dlb(int mode) {
     if (mode != TSP_DLB_OFF && mode != TSP_DLB_ON && mode != TSP_DLB_CLOSE) return TSP_DEV_E_ARG;
     pthread_mutex_lock(&g_lock);
-    g_dlb = mode;
+    const int ok = mode == TSP_DLB_OFF || g_batch_arc < 0;   /* the batched rule has no don't-look bits */
+    if (ok) g_dlb = mode;
     pthread_mutex_unlock(&g_lock);
-    return 0;
+    return ok ? 0 : TSP_DEV_E_ARG;
+}
+
+int tsp_host_set_batch(int max_arc, int rounds) {
+    if (rounds < 0 || (max_arc < 0 && rounds != 0)) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    const int ok = max_arc < 0 || g_dlb == TSP_DLB_OFF;
+    if (ok) {
+        g_batch_arc = max_arc < 0 ? -1 : max_arc;
+        g_batch_rounds = rounds;
+    }
+    pthread_mutex_unlock(&g_lock);
+    return ok ? 0 : TSP_DEV_E_ARG;
+}
+
+/* the list descent over `kinds` under the rule tsp_host_set_batch selects; st is at least a tsp_nl3_opt_stats */
+static int batch_descent_locked(instance *inst, tsp_dev_inst *dev, int kinds, double *obj, tsp_nl3_opt_stats *st) {
+    return tsp_dev_nl_3opt_batch(dev, kinds, g_batch_arc, g_batch_rounds, 1, &inst->solution.edges[0].j, 2,
+                                 2 * (int64_t)inst->num_nodes, obj, -1, limit_of(inst), st);
 }
 
 void tsp_host_last_dlb_stats(int64_t *active_nodes, int64_t *closing_scans) {
@@ -608,7 +628,9 @@ int alg_3opt(instance *inst) {
     pthread_mutex_lock(&g_lock);
     tsp_dev_inst *dev = dev_inst_locked(inst);
     int rc = lists_locked(inst, dev, obj);
-    if (rc == 0)
+    if (rc == 0 && g_batch_arc >= 0)   /* tsp_nl_dlb_stats starts as tsp_nl3_opt_stats; its two own counters stay 0 */
+        rc = batch_descent_locked(inst, dev, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, &obj, (tsp_nl3_opt_stats *)&st);
+    else if (rc == 0)
         rc = tsp_dev_nl_3opt_dlb(dev, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, g_dlb, 1, &inst->solution.edges[0].j, 2,
                                  2 * (int64_t)inst->num_nodes, &obj, NULL, -1, limit_of(inst), &st);
     pthread_mutex_unlock(&g_lock);
@@ -680,7 +702,12 @@ int alg_nl_opt(instance *inst) {
     pthread_mutex_lock(&g_lock);
     tsp_dev_inst *dev = dev_inst_locked(inst);
     int rc = lists_locked(inst, dev, obj);
-    if (rc == 0)
+    if (rc == 0 && g_batch_arc >= 0) {   /* tsp_nl3_opt_stats starts as tsp_nl_opt_stats */
+        tsp_nl3_opt_stats st3;
+        memset(&st3, 0, sizeof st3);
+        rc = batch_descent_locked(inst, dev, TSP_NL_2OPT | TSP_NL_OROPT, &obj, &st3);
+        memcpy(&st, &st3, sizeof st);
+    } else if (rc == 0)
         rc = tsp_dev_nl_opt(dev, TSP_NL_2OPT | TSP_NL_OROPT, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)inst->num_nodes, &obj,
                             -1, limit_of(inst), &st);
     pthread_mutex_unlock(&g_lock);
