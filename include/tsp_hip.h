@@ -548,6 +548,65 @@ int tsp_dev_ils_dlb(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_st
 int tsp_dev_nl_3opt_batch(tsp_dev_inst *inst, int kinds, int max_arc, int rounds, int B, int *succ, int succ_stride,
                           int64_t tour_stride, double *obj, int64_t max_moves, double time_limit_s, tsp_nl3_opt_stats *stats);
 
+/* ---- windowed iterated local search (extension; tour segmentation, Johnson & McGeoch): one kick-repair-accept trial per tour
+ * window, all windows of an iteration at once ---------------------------------------------------------------------------------
+ * (DESIGN.md 4.20 has the kernel.)  A new rule behind a new entry point: tsp_dev_ils, tsp_dev_ils_dlb and the descents keep their
+ * trajectories.  The lists N(v), cand(v), the 2-opt and Or-opt moves, their deltas (every d with the lower node id first, in the
+ * order given above), keys, the order (delta, kind, key), ends(m) and mix are those of the sections above.
+ * Arguments.  kinds: a non-empty subset of TSP_NL_2OPT | TSP_NL_OROPT (TSP_NL_3OPT: TSP_DEV_E_ARG).  iterations I >= 0.
+ * trials T >= 1.  max_moves_per_trial < 0: no cap.
+ *     window W:  9 <= W <= min(TSP_SEG_ILS_MAX_WINDOW, n - 1);  window <= 0: min(TSP_SEG_ILS_DEFAULT_WINDOW, n - 1)
+ *     span S:    8 <= S <= W - 1;                                span <= 0: W - 1
+ * Any other window or span is TSP_DEV_E_ARG.  n < 10 has no window: the call returns the tours unchanged, iterations = 0 and
+ * obj = the tour's cost.
+ * Windows of iteration `it` of chain b.  M = n / W (rounded down).  base = mix(mix(seed ^ (b * 0x100000001B3)) + it), the base
+ * of tsp_dev_ils; the anchor is node s = mix(base) % n.  Window w, 0 <= w < M, is the path seq_w[0 .. W-1] of W nodes that starts
+ * w * W steps after s along succ; the n - M W nodes behind the last window belong to none.  (Nodes and succ only: how a caller
+ * rotates a tour does not matter.)  The window's edges are the W - 1 tour edges (seq_w[k], seq_w[k+1]); out_w = succ seq_w[W-1]
+ * is outside the window because W <= n - 1.
+ * Window move.  A 2-opt or Or-opt move of the list neighbourhood every removed edge of which is a window edge and, Or-opt, whose
+ * segment f .. l is a path of window edges (only at W = n - 1 and L = 3 can the three removed edges be window edges around a
+ * segment seq_w[W-1], out_w, seq_w[0] that is not).  Delta and key are those of tsp_dev_nl_3opt.  Applied, it gives the same
+ * undirected tour as there, written so that every node outside seq_w[1 .. W-2] keeps its successor: only the interior of the
+ * window path is permuted.  A 2-opt move reverses the window sub-path between its two removed edges, whichever of i, j comes
+ * first in the window, and `reversed` counts the nodes of that sub-path; an Or-opt move shifts inside the window.
+ * Window cost.  x[k] = d(seq[k], seq[k+1]) for k < W - 1 and +0.0 up to P, the next power of two >= W - 1; for h = P/2, P/4, .., 1:
+ * x[k] += x[k+h] for all k < h; the cost is x[0].
+ * Trial t, 0 <= t < T, of window w.  bw = mix(base + 8 + w T + t), the draws v_j = mix(bw + j), j = 0 .. 4.
+ *   1. c0 = the window cost of the incumbent window.
+ *   2. Kick.  off = v_0 % (W - S); with q[k] = seq_w[off + k] the cuts o1 .. o4 are those of Kick above with W there replaced by S
+ *      and u_1 .. u_4 by v_1 .. v_4; the window becomes seq_w[0:off] q[0:o1] q[o3:o4] q[o2:o3] q[o1:o2] q[o4:].  off + o4 <= W - 1:
+ *      the first and the last window node stay.
+ *   3. A = q[o1-1], q[o1], q[o2-1], q[o2], q[o3-1], q[o3], q[o4-1], q[o4], read before the kick.
+ *   4. The descent of mode TSP_DLB_ON from A with cand(v) cut down to window moves: per decision the best (delta, kind, key)
+ *      over v in A is applied and A becomes its nodes with an improving window move plus ends(m); it ends at the first decision
+ *      without a move or after max_moves_per_trial moves.
+ *   5. c1 = the window cost.  The kicked and repaired window becomes the incumbent iff c1 < c0; else the window is the
+ *      incumbent's again.
+ * The T trials of a window run one after the other; the windows of an iteration touch disjoint sets of successors, so the result
+ * does not depend on their order; iterations run one after the other.  There is no descent before the first iteration: the
+ * caller's tour is the incumbent (callers run tsp_dev_nl_3opt_batch first).  obj[b] is the recomputed cost of the final tour.
+ * Time limit.  Checked between launches; TSP_TIME_LIMIT_EXCEEDED, stats.iterations counts the completed iterations, and a call
+ * without a limit and with that count returns the same bits.  Chain b of a batch equals a single call with stream b.  Two runs
+ * return the same bits in the tour, the cost and every counter but the times. */
+#define TSP_SEG_ILS_MAX_WINDOW 2048     /* what the kernel's LDS layout holds within 64 KB a workgroup */
+#define TSP_SEG_ILS_DEFAULT_WINDOW 1024 /* the lowest cost at equal time at n = 100 003 */
+typedef struct {
+    int64_t decisions, moves, moves_2opt, moves_oropt, moves_by_len[3], moves_reversed, reversed, deltas_executed;
+    double seconds, device_ms; /* tsp_nl_opt_stats, in its layout: the sums over all trials                                    */
+    int64_t iterations;        /* completed iterations (launches)                                                              */
+    int64_t windows;           /* M                                                                                            */
+    int64_t trials;            /* iterations * M * T                                                                           */
+    int64_t accepted;          /* trials whose window became the incumbent                                                     */
+    int64_t active_nodes;      /* sum of |A| at the start of every decision                                                    */
+    double start_cost;         /* the recomputed cost of the caller's tour                                                     */
+} tsp_seg_ils_stats;
+/* B chains, chain b from tour b with stream b.  Lists and the default lists as tsp_dev_nl_3opt.  Bad arguments: TSP_DEV_E_ARG,
+ * and the caller's tours are untouched. */
+int tsp_dev_seg_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                    uint64_t seed, int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial,
+                    double time_limit_s, tsp_seg_ils_stats *stats);
+
 /* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
  * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
  * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.

@@ -8,6 +8,7 @@
 // nothing to the host, which queues decisions and polls both control blocks as it does for a single descent.  The records are
 // written by tsp_nl_write_stats (nl_opt.hip) from both control blocks; below eight nodes the call is tsp_nl_run.
 #include "descent.hpp"
+#include "ils_common.hpp"
 #include "nl_common.hpp"
 
 #pragma clang fp contract(off)
@@ -16,29 +17,13 @@ using namespace tsp;
 
 namespace {
 
-__host__ __device__ __forceinline__ u64 ils_mix(u64 x) {
-    x += 0x9E3779B97F4A7C15ull;
-    u64 z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // The kick of iteration `it` of chain b on order/pos (n >= 8, W >= 8), by every thread of the one workgroup (NT threads) that
 // owns the tour, behind a barrier that follows the last write of the tour.  Positions pos[s] + o1 .. pos[s] + o4 - 1 hold
 // Bk Ck Dk; reversed as one path they hold Dk' Ck' Bk', and each block reversed again leaves Dk Ck Bk.
-struct IlsCuts {
-    int s, o1, o2, o3, o4;
-};
 __device__ __forceinline__ IlsCuts ils_cuts(int n, int W, u64 seed, int b, long long it) {
-    const u64 base = ils_mix(ils_mix(seed ^ ((u64)b * 0x100000001B3ull)) + (u64)it);
-    IlsCuts c;
-    c.s = (int)(ils_mix(base) % (u64)n);
-    c.o1 = 1 + (int)(ils_mix(base + 1) % (u64)(W - 3));
-    c.o2 = c.o1 + 1 + (int)(ils_mix(base + 2) % (u64)(W - 2 - c.o1));
-    c.o3 = c.o2 + 1 + (int)(ils_mix(base + 3) % (u64)(W - 1 - c.o2));
-    c.o4 = c.o3 + 1 + (int)(ils_mix(base + 4) % (u64)(W - c.o3));
-    return c;
+    const u64 base = ils_base(seed, b, it);
+    return ils_cuts_from((int)(ils_mix(base) % (u64)n), W, ils_mix(base + 1), ils_mix(base + 2), ils_mix(base + 3),
+                         ils_mix(base + 4));
 }
 
 template <int NT>

@@ -203,7 +203,11 @@ struct NlData {
     int *d_taken = nullptr;
     NlbCtl *d_bctl = nullptr;
     int bparts = 0;
+    // windowed iterated local search (seg_ils.hip), allocated by its first call at this B: accepted trials per chain
+    u64 *d_seg_acc = nullptr;
     void free_scratch() {
+        (void)hipFree(d_seg_acc);
+        d_seg_acc = nullptr;
         (void)hipFree(d_st); (void)hipHostFree(h_st); (void)hipFree(d_E); (void)hipFree(d_rem); (void)hipFree(d_cost);
         (void)hipFree(d_part); (void)hipFree(d_inc); (void)hipFree(d_ils); (void)hipHostFree(h_ils);
         d_st = nullptr; h_st = nullptr; d_E = d_rem = d_cost = nullptr; d_part = nullptr; B = 0;

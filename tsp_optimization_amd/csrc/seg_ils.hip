@@ -1,0 +1,405 @@
+// seg_ils.hip -- windowed iterated local search (tsp_dev_seg_ils).  The definitions are in include/tsp_hip.h.
+//
+// Launch   k_seg_ils, one per iteration: grid (windows, chains), one workgroup = the T trials of one window of W consecutive tour
+//          nodes.  The window lives in LDS under "home" ids, the slot a node had when the kernel loaded it: seq (home id per slot),
+//          lpos (slot per home id), node (node per home id), the incumbent copy of seq, the edge lengths E, the active list (two
+//          copies, a decision compacts one into the other) with its bitmap and the hit flags.  A node's home id is the incumbent's
+//          global pos minus the window's first position, mod n: below W or not decides "is a window node", and global pos is not
+//          written before the trials are over.  Kick, moves and restore are permutations of a slot interval (seg_permute) followed
+//          by the edge lengths of that interval; a trial keeps the hull of its intervals and copies or restores nothing else.
+//          rem of an Or-opt segment is taken from E and one distance, in k_nl_prep's order, rather than kept per slot.
+// Host     Descent::run queues the launches and looks at the clock between its batches; nothing is read per launch.
+#include "descent.hpp"
+#include "ils_common.hpp"
+#include "nl_common.hpp"
+
+#include <cstddef>
+
+#pragma clang fp contract(off)
+
+using namespace tsp;
+
+namespace {
+
+constexpr int kSegThreads = 256;
+using u16 = unsigned short;
+static_assert(TSP_SEG_ILS_MAX_WINDOW <= 65536, "slots and home ids are 16-bit");
+
+__host__ __device__ __forceinline__ int seg_round8(int W) { return (W + 7) & ~7; }
+// entries of the cost tree behind its first level: P / 2, P the next power of two >= W - 1; its bytes also stage a permutation
+__host__ __device__ __forceinline__ int seg_tree_len(int W) {
+    int P = 8;
+    while (P < W - 1) P *= 2;
+    const int ids = seg_round8(W) / 4;
+    return P / 2 > ids ? P / 2 : ids;
+}
+size_t seg_lds_bytes(int W) { return (size_t)24 * seg_round8(W) + (size_t)8 * seg_tree_len(W); }
+
+struct SegWin {
+    double *E, *tree;
+    int *node;
+    u16 *seq, *inc, *lpos, *alist;   // alist: two lists of W8 ids, one behind the other
+    unsigned char *act, *hit;
+};
+
+// What a lane of the scan reads the window through: NlView's two / oro / roles over slots, a move kept only when every edge it
+// removes is a window edge (the tails at slots 0 .. W - 2) and, Or-opt, its segment is a window path.
+template <int WT, bool INT>
+struct SegView {
+    const double2 *coord;
+    SegWin w;
+    int n, W;
+    double bd;
+    u64 bk;
+    unsigned cnt;
+    bool found;
+
+    __device__ __forceinline__ int at(int p) const { return w.node[w.seq[p]]; }
+    __device__ __forceinline__ double d(int u, int v) const { return dsym<WT, INT>(coord, u, v); }
+    __device__ __forceinline__ void take(double delta, u64 key) {
+        cnt += 1;
+        if (delta < 0.0) {
+            found = true;
+            if (better(delta, key, bd, bk)) { bd = delta; bk = key; }
+        }
+    }
+
+    __device__ __forceinline__ void two(int x, int px, int y, int py, int known, double dk) {
+        if (px < 0 || py < 0 || px > W - 2 || py > W - 2) return;
+        if (x > y) { int t = x; x = y; y = t; t = px; px = py; py = t; }
+        const int i1 = at(px + 1), j1 = at(py + 1);
+        if (y == i1 || j1 == x) return;
+        const double dij = known == 0 ? dk : d(x, y), d11 = known == 1 ? dk : d(i1, j1);
+        take(((dij + d11) - w.E[px]) - w.E[py], (u64)x * (u64)n + (u64)y);
+    }
+
+    __device__ __forceinline__ void oro(int f, int pf, int L, int a, int pa, int o, int known, double dk) {
+        if (pf < 1 || pf + L > W - 1 || pa < 0 || pa > W - 2) return;   // p, s and b are window nodes
+        if (pa >= pf - 1 && pa <= pf + L - 1) return;                     // a in {p, f .. l}
+        const int l = at(pf + L - 1), bb = at(pa + 1);
+        const double d1 = known == 0 ? dk : (o ? d(a, l) : d(a, f));
+        const double d2 = known == 1 ? dk : (o ? d(f, bb) : d(l, bb));
+        const double rem = (w.E[pf - 1] + w.E[pf + L - 1]) - d(at(pf - 1), at(pf + L));
+        take(((d1 + d2) - w.E[pa]) - rem, kNlOrBit | or_key(f, L, a, o, n));
+    }
+
+    __device__ __forceinline__ void roles(int x, int px, int y, int py, double dk) {
+        const int pa = py - 1;
+        const int a = pa >= 0 ? at(pa) : 0;
+#pragma unroll
+        for (int L = 1; L <= 3; ++L) {
+            oro(y, py, L, x, px, 0, 0, dk);
+            const int pf = px - (L - 1);
+            if (pf >= 0 && pa >= 0) oro(at(pf), pf, L, a, pa, 0, 1, dk);
+            if (L > 1) {
+                const int pg = py - (L - 1);
+                if (pg >= 0) oro(at(pg), pg, L, x, px, 1, 0, dk);
+                if (pa >= 0) oro(x, px, L, a, pa, 1, 1, dk);
+            }
+        }
+    }
+};
+
+// Slots lo .. hi take the home ids of the slots src(k), a permutation of lo .. hi.  By every thread; `stage` holds hi - lo + 1 ids.
+template <typename Src>
+__device__ __forceinline__ void seg_permute(const SegWin &w, u16 *stage, int lo, int hi, Src src) {
+    const int tid = threadIdx.x;
+    for (int k = lo + tid; k <= hi; k += kSegThreads) stage[k - lo] = w.seq[src(k)];
+    __syncthreads();
+    for (int k = lo + tid; k <= hi; k += kSegThreads) {
+        const u16 r = stage[k - lo];
+        w.seq[k] = r; w.lpos[r] = (u16)k;
+    }
+    __syncthreads();
+}
+
+// E of the slots lo .. hi that have one.  By every thread, behind the barrier that follows the last write of seq.
+template <int WT, bool INT>
+__device__ __forceinline__ void seg_edges(const double2 *coord, const SegWin &w, int W, int lo, int hi) {
+    lo = max(lo, 0); hi = min(hi, W - 2);
+    for (int k = lo + (int)threadIdx.x; k <= hi; k += kSegThreads)
+        w.E[k] = dsym<WT, INT>(coord, w.node[w.seq[k]], w.node[w.seq[k + 1]]);
+    __syncthreads();
+}
+
+// The window cost of include/tsp_hip.h: the halving tree over E padded with +0.0 to P entries.  By every thread; every thread gets it.
+__device__ __forceinline__ double seg_cost(const SegWin &w, int W) {
+    const int tid = threadIdx.x;
+    int P = 8;
+    while (P < W - 1) P *= 2;
+    int h = P / 2;
+    for (int k = tid; k < h; k += kSegThreads) {
+        const double hi = k + h < W - 1 ? w.E[k + h] : 0.0;
+        w.tree[k] = w.E[k] + hi;   // k < P / 2 < W - 1
+    }
+    __syncthreads();
+    for (h /= 2; h >= 1; h /= 2) {
+        for (int k = tid; k < h; k += kSegThreads) w.tree[k] += w.tree[k + h];   // entries k + h >= h are only read at this level
+        __syncthreads();
+    }
+    const double c = w.tree[0];
+    __syncthreads();   // the tree's bytes stage the next permutation
+    return c;
+}
+
+struct SegArgs {
+    int n, K, kinds, W, S, T;
+    long long cap;   // < 0: none
+    u64 seed;
+    long long it;
+};
+
+template <int WT, bool INT>
+__global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restrict__ coord, int *__restrict__ orders,
+                                                         int *__restrict__ poss, const int *__restrict__ nbr,
+                                                         NlState *__restrict__ st, u64 *__restrict__ acc, SegArgs g) {
+    extern __shared__ double seg_lds[];
+    __shared__ double s_d[kSegThreads / 64];
+    __shared__ u64 s_k[kSegThreads / 64];
+    __shared__ int s_na, s_cnt;
+    const int tid = threadIdx.x, wi = blockIdx.x, b = blockIdx.y;
+    const int n = g.n, W = g.W, S = g.S, K = g.K, W8 = seg_round8(W);
+    int *order = orders + (size_t)b * n, *pos = poss + (size_t)b * n;
+    SegWin w;
+    w.E = seg_lds; w.tree = w.E + W8;
+    w.node = reinterpret_cast<int *>(w.tree + seg_tree_len(W));
+    w.seq = reinterpret_cast<u16 *>(w.node + W8); w.inc = w.seq + W8; w.lpos = w.inc + W8;
+    w.alist = w.lpos + W8;
+    w.act = reinterpret_cast<unsigned char *>(w.alist + 2 * W8); w.hit = w.act + W8;
+    u16 *stage = reinterpret_cast<u16 *>(w.tree);
+
+    const u64 base = ils_base(g.seed, b, g.it);
+    const int s = (int)(ils_mix(base) % (u64)n);
+    int p0 = (int)(((long long)pos[s] + (long long)wi * W) % n);   // pos[s]: the anchor is slot 0 of window 0 and keeps its position
+    for (int k = tid; k < W; k += kSegThreads) {
+        w.node[k] = order[or_wrap(p0 + k, n)];
+        w.seq[k] = w.inc[k] = w.lpos[k] = (u16)k;
+        w.act[k] = w.hit[k] = 0;
+    }
+    __syncthreads();
+    seg_edges<WT, INT>(coord, w, W, 0, W - 2);
+    double c0 = seg_cost(w, W);
+
+    SegView<WT, INT> view;
+    view.coord = coord; view.w = w; view.n = n; view.W = W; view.cnt = 0;
+    // the same values in every thread; thread 0 adds them to the chain's
+    long long decisions = 0, moves_all = 0, m2 = 0, mor = 0, ml1 = 0, ml2 = 0, ml3 = 0, mrev = 0, reversed = 0, active = 0, accepted = 0;
+    // the slot of a window node
+    auto slot_of = [&](int v) { return (int)w.lpos[ahead(pos[v], p0, n)]; };
+
+    for (int t = 0; t < g.T; ++t) {
+        const u64 bw = ils_mix(base + 8 + (u64)wi * (u64)g.T + (u64)t);
+        const int off = (int)(ils_mix(bw) % (u64)(W - S));
+        const IlsCuts c = ils_cuts_from(0, S, ils_mix(bw + 1), ils_mix(bw + 2), ils_mix(bw + 3), ils_mix(bw + 4));
+        const int o[4] = {c.o1, c.o2, c.o3, c.o4};
+        int e[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { e[2 * q] = w.seq[off + o[q] - 1]; e[2 * q + 1] = w.seq[off + o[q]]; }   // off + o4 <= W - 1
+        int ne = 8;   // ends of the kick, then of a move: 4 or 6
+        int tlo = off + c.o1, thi = off + c.o4 - 1;   // the hull of what the trial has permuted
+        {
+            const int lD = c.o4 - c.o3, lC = c.o3 - c.o2, kb = off + c.o1;
+            const int sB = off + c.o1, sC = off + c.o2, sD = off + c.o3;
+            seg_permute(w, stage, tlo, thi, [=](int k) {
+                const int q = k - kb;
+                return q < lD ? sD + q : (q < lD + lC ? sC + (q - lD) : sB + (q - lD - lC));
+            });
+        }
+        seg_edges<WT, INT>(coord, w, W, tlo - 1, thi);
+        int cur = 0;
+        if (tid == 0) {
+            int cnt = 0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (!w.act[e[q]]) { w.act[e[q]] = 1; w.alist[cnt++] = (u16)e[q]; }   // single-node blocks name a node twice
+            s_na = cnt;
+        }
+        __syncthreads();
+        int na = s_na;
+        long long moves = 0;
+        while (g.cap < 0 || moves < g.cap) {
+            decisions += 1; active += na;
+            view.bd = INFINITY; view.bk = kNoKey;
+            const u16 *list = w.alist + cur * W8;
+            for (int ln = tid; ln < na * K; ln += kSegThreads) {
+                const int r = list[ln / K];
+                const int v = w.node[r], u = nbr[(size_t)v * K + (ln % K)];
+                if (u == v) continue;
+                const int hu = ahead(pos[u], p0, n);
+                if (hu >= W) continue;   // a move over the entry (v, u) removes an edge at u
+                const int pv = w.lpos[r], pu = w.lpos[hu];
+                const double dk = view.d(v, u);
+                view.found = false;
+                if (g.kinds & TSP_NL_2OPT) {
+                    view.two(v, pv, u, pu, 0, dk);
+                    if (pv >= 1 && pu >= 1) view.two(view.at(pv - 1), pv - 1, view.at(pu - 1), pu - 1, 1, dk);
+                }
+                if (g.kinds & TSP_NL_OROPT) {
+                    view.roles(v, pv, u, pu, dk);
+                    view.roles(u, pu, v, pv, dk);
+                }
+                if (view.found) w.hit[r] = 1;
+            }
+            double bd = view.bd;
+            u64 bk = view.bk;
+            block_argmin<true>(bd, bk, s_d, s_k);   // (its barriers also stand between the hit flags and their readers)
+            if (bk == kNoKey) break;                // no lane held an improving move: hit is all zero
+            // the move in slots: lo .. hi are permuted, ends(m) as home ids from the window before the move
+            int lo, hi;
+            if (!(bk & kNlOrBit)) {
+                const int px = slot_of((int)(bk / (u64)n)), py = slot_of((int)(bk % (u64)n));
+                lo = min(px, py) + 1; hi = max(px, py);
+                e[0] = w.seq[lo - 1]; e[1] = w.seq[lo]; e[2] = w.seq[hi]; e[3] = w.seq[hi + 1];
+                ne = 4;
+                m2 += 1; reversed += hi - lo + 1;
+            } else {
+                const OrMove mv = or_unkey(bk & (kNlOrBit - 1), n);
+                const int pf = slot_of(mv.f), pa = slot_of(mv.a), L = mv.L;
+                e[0] = w.seq[pf - 1]; e[1] = w.seq[pf]; e[2] = w.seq[pf + L - 1]; e[3] = w.seq[pf + L];
+                e[4] = w.seq[pa]; e[5] = w.seq[pa + 1];
+                ne = 6;
+                lo = pa > pf ? pf : pa + 1; hi = pa > pf ? pa : pf + L - 1;
+                mor += 1; ml1 += L == 1; ml2 += L == 2; ml3 += L == 3; mrev += mv.o;
+            }
+            // A: the listed nodes with a hit, then the ends that are not among them
+            if (tid == 0) s_cnt = 0;
+            __syncthreads();
+            u16 *next = w.alist + (cur ^ 1) * W8;
+            for (int q = tid; q < na; q += kSegThreads) {
+                const int r = list[q];
+                if (w.hit[r]) { w.hit[r] = 0; next[atomicAdd(&s_cnt, 1)] = (u16)r; }
+                else w.act[r] = 0;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int cnt = s_cnt;
+#pragma unroll
+                for (int q = 0; q < 6; ++q)
+                    if (q < ne && !w.act[e[q]]) { w.act[e[q]] = 1; next[cnt++] = (u16)e[q]; }
+                s_na = cnt;
+            }
+            if (!(bk & kNlOrBit)) {
+                const int sum = lo + hi;
+                seg_permute(w, stage, lo, hi, [=](int k) { return sum - k; });
+            } else {
+                const OrMove mv = or_unkey(bk & (kNlOrBit - 1), n);
+                const int pf = slot_of(mv.f), pa = slot_of(mv.a), L = mv.L, o = mv.o;
+                // where the segment lands, and by how much the slots between it and the insertion point shift
+                const int land = pa > pf ? pa - L + 1 : pa + 1, shift = pa > pf ? L : -L;
+                seg_permute(w, stage, lo, hi, [=](int k) {
+                    const int q = k - land;
+                    return q >= 0 && q < L ? (o ? pf + L - 1 - q : pf + q) : k + shift;
+                });
+            }
+            seg_edges<WT, INT>(coord, w, W, lo - 1, hi);
+            tlo = min(tlo, lo); thi = max(thi, hi);
+            cur ^= 1;
+            na = s_na;   // written ahead of seg_permute's barriers
+            moves += 1;
+        }
+        moves_all += moves;
+        for (int q = tid; q < na; q += kSegThreads) w.act[w.alist[cur * W8 + q]] = 0;   // also what a descent ended by the cap left
+        const double c1 = seg_cost(w, W);   // (its barriers stand between the bitmap and the next trial's list)
+        if (c1 < c0) {
+            for (int k = tlo + tid; k <= thi; k += kSegThreads) w.inc[k] = w.seq[k];
+            c0 = c1;
+            accepted += 1;
+            __syncthreads();
+        } else {
+            for (int k = tlo + tid; k <= thi; k += kSegThreads) {
+                const u16 r = w.inc[k];
+                w.seq[k] = r; w.lpos[r] = (u16)k;
+            }
+            __syncthreads();
+            seg_edges<WT, INT>(coord, w, W, tlo - 1, thi);
+        }
+    }
+    if (accepted)
+        for (int k = tid; k < W; k += kSegThreads) {
+            const int v = w.node[w.inc[k]], p = or_wrap(p0 + k, n);
+            order[p] = v; pos[v] = p;
+        }
+    NlState &Z = st[b];
+    auto add = [](long long &to, long long x) { if (x) atomicAdd((unsigned long long *)&to, (unsigned long long)x); };
+    if (tid == 0) {
+        add(Z.decisions, decisions); add(Z.moves, moves_all); add(Z.moves_2opt, m2); add(Z.moves_oropt, mor);
+        add(Z.moves_len[0], ml1); add(Z.moves_len[1], ml2); add(Z.moves_len[2], ml3);
+        add(Z.moves_rev, mrev); add(Z.reversed, reversed); add(Z.active_nodes, active);
+        if (accepted) atomicAdd(&acc[b], (u64)accepted);
+    }
+    unsigned long long cnt = view.cnt;
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+    if ((tid & 63) == 0) add(Z.deltas, (long long)cnt);
+}
+
+// Descent::run ends when every iteration has been queued (and, behind its poll, carried out).
+struct SegHooks : DescentPlain {
+    const long long *queued;
+    long long iterations;
+    bool finished(const NlState &, int) const { return *queued >= iterations; }
+};
+
+}  // namespace
+
+static_assert(offsetof(tsp_seg_ils_stats, iterations) == sizeof(tsp_nl_opt_stats), "tsp_seg_ils_stats starts as tsp_nl_opt_stats");
+
+extern "C" int tsp_dev_seg_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                               uint64_t seed, int64_t iterations, int window, int span, int trials,
+                               int64_t max_moves_per_trial, double time_limit_s, tsp_seg_ils_stats *stats) {
+    int rc = tsp_nl_check(inst, &kinds, TSP_NL_2OPT | TSP_NL_OROPT, B, succ, succ_stride, tour_stride, obj);
+    if (rc) return rc;
+    if (iterations < 0 || trials < 1) return TSP_DEV_E_ARG;
+    const int n = inst->n;
+    const bool none = n < 10;   // no window
+    int W = 0, S = 0;
+    if (!none) {
+        const int top = std::min(TSP_SEG_ILS_MAX_WINDOW, n - 1);
+        W = window <= 0 ? std::min(TSP_SEG_ILS_DEFAULT_WINDOW, n - 1) : window;
+        if (W < 9 || W > top) return TSP_DEV_E_ARG;
+        S = span <= 0 ? W - 1 : span;
+        if (S < 8 || S > W - 1) return TSP_DEV_E_ARG;
+    }
+    const long long I = none ? 0 : iterations, M = none ? 0 : n / W;
+    Descent run;
+    rc = run.open(inst, B, succ, succ_stride, tour_stride, obj);
+    if (rc) return rc;
+    NlData *x = nullptr;
+    rc = tsp_nl_prepare(inst, B, &x);
+    if (rc) return rc;
+    hipStream_t s = inst->ctx->stream;
+    tsp_dev_tours *t = run.t;
+    if (!x->d_seg_acc) TSP_HIP_TRY(hipMalloc(&x->d_seg_acc, sizeof(u64) * B));
+    TSP_HIP_TRY(hipMemsetAsync(x->d_seg_acc, 0, sizeof(u64) * B, s));
+    std::vector<double> start((size_t)B);
+    if (int e = tsp_grid_tour_cost(t, x->d_cost)) return e;
+    TSP_HIP_TRY(hipMemcpyAsync(start.data(), x->d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+    TSP_HIP_TRY(hipStreamSynchronize(s));
+    SegArgs g;
+    g.n = n; g.K = x->K; g.kinds = kinds; g.W = W; g.S = S; g.T = trials;
+    g.cap = max_moves_per_trial < 0 ? -1 : max_moves_per_trial; g.seed = seed; g.it = 0;
+    long long queued = 0;
+    SegHooks hooks;
+    hooks.queued = &queued; hooks.iterations = I;
+    const size_t lds = none ? 0 : seg_lds_bytes(W);
+    const int status = run.run(x->d_st, x->h_st, x->d_cost, I == 0, 256, -1, time_limit_s,
+                               [&](bool) {
+                                   if (queued >= I) return;
+                                   g.it = queued++;
+                                   TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
+                                       hipLaunchKernelGGL((k_seg_ils<WTC, INTC>), dim3((unsigned)M, B), dim3(kSegThreads), lds, s,
+                                                          inst->d_coord, t->d_order, t->d_pos, x->d_nbr, x->d_st, x->d_seg_acc, g);
+                                   });
+                               },
+                               hooks);
+    if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
+    std::vector<u64> acc((size_t)B, 0);
+    TSP_HIP_TRY(hipMemcpy(acc.data(), x->d_seg_acc, sizeof(u64) * B, hipMemcpyDeviceToHost));
+    const double seconds = wall_s() - run.t0;
+    for (int b = 0; b < B && stats; ++b) {
+        tsp_seg_ils_stats &o = stats[b];
+        tsp_nl_write_stats(NlStatsOut{&o, sizeof o, 0}, 0, x->h_st[b], nullptr, 0.0, seconds, run.device_ms);
+        o.iterations = queued; o.windows = M; o.trials = queued * M * trials; o.accepted = (int64_t)acc[b];
+        o.active_nodes = x->h_st[b].active_nodes; o.start_cost = start[b];
+    }
+    return status;
+}

@@ -18,6 +18,7 @@ NL_3OPT = 4   # tsp_dev_nl_3opt only
 DLB_OFF, DLB_ON, DLB_CLOSE = 0, 1, 2   # don't-look bits of nl_3opt and ils
 NL_BATCH_DEFAULT_ROUNDS = 2            # claim rounds of nl_3opt_batch (TSP_NL_BATCH_DEFAULT_ROUNDS)
 NL_MAX_K, NL_DEFAULT_K = 16, 10
+SEG_ILS_MAX_WINDOW, SEG_ILS_DEFAULT_WINDOW = 2048, 1024   # windows of seg_ils (TSP_SEG_ILS_MAX_WINDOW, _DEFAULT_WINDOW)
 HK_DEFAULT_ITERS, HK_DEFAULT_LAMBDA = 300, 2.0
 ALPHA_DEFAULT_K = 5
 
@@ -69,6 +70,11 @@ class NlDlbStats(_Stats):
 
 class IlsDlbStats(_Stats):
     _fields_ = IlsStats._fields_ + [("active_nodes", C.c_int64), ("closing_scans", C.c_int64)]
+
+
+class SegIlsStats(_Stats):
+    _fields_ = NlOptStats._fields_ + [("iterations", C.c_int64), ("windows", C.c_int64), ("trials", C.c_int64),
+                                      ("accepted", C.c_int64), ("active_nodes", C.c_int64), ("start_cost", C.c_double)]
 
 
 class LbStats(_Stats):
@@ -181,6 +187,8 @@ def lib():
                                       C.c_double, C.c_int, C.POINTER(IlsDlbStats)]
         L.tsp_dev_nl_3opt_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_int64, C.c_double,
                                             C.POINTER(Nl3OptStats)]
+        L.tsp_dev_seg_ils.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_uint64, C.c_int64, C.c_int, C.c_int,
+                                      C.c_int, C.c_int64, C.c_double, C.POINTER(SegIlsStats)]
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
@@ -212,6 +220,7 @@ EXPORTED = [
     "tsp_dev_inst_alpha_build", "tsp_dev_alpha_rows",
     "tsp_dev_greedy_edge",
     "tsp_dev_nl_3opt_batch",
+    "tsp_dev_seg_ils",
 ]
 
 COMM_ID_BYTES = 128
@@ -492,6 +501,22 @@ class Instance:
         B, n = succ2.shape
         _check(lib().tsp_dev_ils_kick(self._h, B, _i(succ2), 1, n, int(seed) & (2 ** 64 - 1), int(it), int(span)))
         return succ2[0] if single else succ2
+
+    def seg_ils(self, succ, iterations, window=0, span=0, trials=1, seed=0, kinds=NL_2OPT | NL_OROPT, max_moves_per_trial=-1,
+                time_limit=-1.0, obj=None):
+        """Windowed iterated local search (tsp_dev_seg_ils): per iteration the tour is cut into windows of `window` consecutive
+        nodes (0: SEG_ILS_DEFAULT_WINDOW) from a random anchor, and every window runs `trials` trials of a double-bridge kick
+        within `span` window nodes (0: window - 1), the repair by the 2-opt + Or-opt list moves that stay inside the window, and
+        the better window kept.  There is no descent before the first iteration: pass a local optimum (nl_3opt_batch).  succ [n]
+        or [B,n]: B chains, chain b with random stream b of `seed`.  -> (status, succ', obj' (recomputed cost), stats dict(s)):
+        the nl_opt counters summed over all trials, iterations, windows, trials, accepted, active_nodes, start_cost"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = _obj(obj, B)
+        st = (SegIlsStats * B)()
+        rc = lib().tsp_dev_seg_ils(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations),
+                                   int(window), int(span), int(trials), int(max_moves_per_trial), time_limit, st)
+        return _result(rc, single, succ2, o, st)
 
     # -- Held-Karp lower bound (extension) ---------------------------------------------------
     def _pi(self, pi):

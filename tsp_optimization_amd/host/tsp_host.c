@@ -750,6 +750,70 @@ int HEU_2opt_greedy_edge(instance *inst) { (void)HEU_greedy_edge(inst); return a
 int HEU_nl_greedy_edge(instance *inst) { (void)HEU_greedy_edge(inst); return alg_nl_opt(inst); }
 int HEU_ils_greedy_edge(instance *inst) { (void)HEU_greedy_edge(inst); return alg_ils(inst); }
 
+/* ---- windowed iterated local search (extension) -------------------------------------------------------------- */
+
+static __thread tsp_seg_ils_stats t_seg_stats;
+static int g_seg_iters = 100, g_seg_window = 0, g_seg_span = 50, g_seg_trials = 1;   /* tsp_host_set_seg_ils */
+
+int tsp_host_set_seg_ils(int iterations, int window, int span, int trials) {
+    if (iterations < 0 || trials < 1 || (span >= 1 && span <= 7)) return TSP_DEV_E_ARG;
+    if (window > TSP_SEG_ILS_MAX_WINDOW || (window >= 1 && window <= 8)) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_seg_iters = iterations;
+    g_seg_window = window < 0 ? 0 : window;
+    g_seg_span = span < 0 ? 0 : span;
+    g_seg_trials = trials;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+void tsp_host_last_seg_ils_stats(tsp_seg_ils_stats *out) {
+    if (out) *out = t_seg_stats;
+}
+
+/* tsp_dev_seg_ils over the lists alg_nl_opt would use, one chain from inst->solution */
+int alg_seg_ils(instance *inst) {
+    const int n = inst->num_nodes;
+    tsp_seg_ils_stats st;
+    memset(&st, 0, sizeof st);
+    double obj = inst->solution.obj_best;
+    pthread_mutex_lock(&g_lock);
+    int W = g_seg_window > 0 ? g_seg_window : TSP_SEG_ILS_DEFAULT_WINDOW;
+    if (g_seg_window <= 0 && W > n - 1) W = n - 1;
+    const int span = g_seg_span > W - 1 ? W - 1 : g_seg_span;
+    tsp_dev_inst *dev = dev_inst_locked(inst);
+    int rc = lists_locked(inst, dev, obj);
+    if (rc == 0)
+        rc = tsp_dev_seg_ils(dev, TSP_NL_2OPT | TSP_NL_OROPT, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
+                             (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
+                             limit_of(inst), &st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_seg_ils", rc);
+    inst->solution.obj_best = obj;
+    t_seg_stats = st;
+    if (rc == TIME_LIMIT_EXCEEDED) LOG_I("windowed iterated local search time exceeded");
+    return rc;
+}
+
+/* construction, the batched 2-opt + Or-opt list descent under its defaults whatever tsp_host_set_batch says, alg_seg_ils: the
+ * status is the last one's */
+int HEU_seg_ils_greedy_edge(instance *inst) {
+    (void)HEU_greedy_edge(inst);
+    tsp_nl3_opt_stats st3;
+    memset(&st3, 0, sizeof st3);
+    double obj = inst->solution.obj_best;
+    pthread_mutex_lock(&g_lock);
+    tsp_dev_inst *dev = dev_inst_locked(inst);
+    int rc = lists_locked(inst, dev, obj);
+    if (rc == 0)
+        rc = tsp_dev_nl_3opt_batch(dev, TSP_NL_2OPT | TSP_NL_OROPT, 0, 0, 1, &inst->solution.edges[0].j, 2,
+                                   2 * (int64_t)inst->num_nodes, &obj, -1, limit_of(inst), &st3);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_nl_3opt_batch", rc);
+    inst->solution.obj_best = obj;
+    return alg_seg_ils(inst);
+}
+
 /* ---- Held-Karp lower bound (extension) -------------------------------------------------------------------- */
 
 static __thread tsp_lb_stats t_lb_stats;
