@@ -82,9 +82,11 @@ struct alignas(32) ScanColDeg { double x, y; int deg, pad0; long long pad1; };  
 static_assert(sizeof(ScanCol) == 32 && sizeof(ScanColDeg) == 32, "a column record is one 32-byte scalar load");
 
 // d(a, b) with the same bits from either end.  Every metric but GEO is symmetric to the bit (a - b = -(b - a) exactly, and only
-// squares and absolute values of it are used), so the row goes first; GEO (products of cosines, acos) is not, and takes the
-// lower id first.  k_alpha_scan's lane carries the same two rules written out.  k_knn_scan does NOT use this:
-// its lists are defined on the device's distance matrix, which is computed row first (test_knn_geo_on_the_devices_own_matrix).
+// squares and absolute values of it are used), so the row goes first.  GEO (products of cosines, acos) is symmetric only if
+// ocml's cos is even: measured so on gfx950 -- the distance matrices of tests/test_gpu_geo.py are symmetric to the bit -- but
+// promised nowhere, so GEO takes the lower id first.  k_alpha_scan's lane carries the same two rules written out (DESIGN.md
+// 4.18).  k_knn_scan does NOT use this: its lists are defined on the device's distance matrix, which is computed row first
+// (test_knn_geo_on_the_devices_own_matrix).
 template <int WT, bool INT>
 __device__ __forceinline__ double pair_dist(int ida, double ax, double ay, int idb, double bx, double by) {
     const bool alo = WT != WT_GEO || ida < idb;
