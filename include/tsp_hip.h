@@ -607,6 +607,39 @@ int tsp_dev_seg_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_st
                     uint64_t seed, int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial,
                     double time_limit_s, tsp_seg_ils_stats *stats);
 
+/* ---- windowed iterated local search with the 3-opt kind (extension): segment moves inside a window -----------------------------
+ * (DESIGN.md 4.21 has the kernel.)  A new entry point beside tsp_dev_seg_ils, which keeps refusing TSP_NL_3OPT and keeps its
+ * trajectories.  kinds: a non-empty subset of TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT; with TSP_NL_3OPT, n > 2^20 is
+ * TSP_DEV_E_ARG as in tsp_dev_nl_3opt.  Everything else -- windows, draws, kick, A, accept, window cost, time limit, n < 10 -- is
+ * the text of the section above, with three additions.
+ * Window 3-opt move.  A 3-opt move of the list neighbourhood all three removed edges of which are window edges: the tails a, b, c
+ * lie at slots 0 .. W - 2 of the window path.  cand(v), delta, key and the order (delta, kind, key) are those of the don't-look
+ * section and of tsp_dev_nl_3opt: the delta is summed in its stated order under the (a, b, c, type) labelling, where a is the tail
+ * of lowest node id and b and c follow it in tour order, through the outside of the window where that is the way round.
+ * ends(m) = a, a1, b, b1, c, c1.
+ * Applied, it gives the same undirected tour as tsp_dev_nl_3opt's move, written so that slots 0 and W - 1 keep their nodes and no
+ * successor outside the window changes.  With the tails at slots i < j < k, X = slots i+1 .. j, Y = slots j+1 .. k and a at slot
+ * i (r = 0), j (r = 1) or k (r = 2), the slots i+1 .. k become (' = reversed)
+ *                type 0   type 1   type 2   type 3
+ *         r = 0   Y X     X' Y'    Y' X     Y X'
+ *         r = 1   Y X     Y X'     X' Y'    Y' X
+ *         r = 2   Y X     Y' X     Y X'     X' Y'
+ * that is Y X for type 0 and else form (type - 1 + 2 r) mod 3 of (X' Y', Y' X, Y X').  Key and delta stay those of the
+ * (a, b, c, type) labelling; only the permutation is relabelled.
+ * Counters.  A window 3-opt move adds to moves, moves_3opt and moves_by_type[type], type as in its key, and to nothing else:
+ * `reversed` stays the count of the 2-opt moves.
+ * With kinds inside TSP_NL_2OPT | TSP_NL_OROPT the call returns the bits of tsp_dev_seg_ils. */
+typedef struct {
+    int64_t decisions, moves, moves_2opt, moves_oropt, moves_by_len[3], moves_reversed, reversed, deltas_executed;
+    double seconds, device_ms;
+    int64_t iterations, windows, trials, accepted, active_nodes;
+    double start_cost;                    /* tsp_seg_ils_stats, in its layout                                                   */
+    int64_t moves_3opt, moves_by_type[4]; /* the window 3-opt moves, summed over all trials                                     */
+} tsp_seg_ils3_stats;
+int tsp_dev_seg_ils3(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                     uint64_t seed, int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial,
+                     double time_limit_s, tsp_seg_ils3_stats *stats);
+
 /* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
  * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
  * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.

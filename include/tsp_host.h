@@ -190,12 +190,17 @@ int HEU_ils_greedy_edge(instance *inst);   /* HEU_greedy_edge + alg_ils    */
  * TSP_SEG_ILS_MAX_WINDOW, span 0 (window - 1) or >= 8 (default 50), trials >= 1 (default 1); else TSP_DEV_E_ARG and the settings
  * stay.  Whether window and span fit the instance is the device call's check. */
 int tsp_host_set_seg_ils(int iterations, int window, int span, int trials);
-int alg_seg_ils(instance *inst);              /* tsp_dev_seg_ils from inst->solution: 2-opt + Or-opt over the lists
-                                                 tsp_host_set_knn / tsp_host_set_alpha select, one chain, seed = params.seed (as
-                                                 unsigned), params.time_limit when > 0, no cap on the moves of a trial; a span
-                                                 above window - 1 is cut to it; obj_best receives the recomputed cost          */
+int alg_seg_ils(instance *inst);              /* tsp_dev_seg_ils from inst->solution: 2-opt + Or-opt (or the kinds set below)
+                                                 over the lists tsp_host_set_knn / tsp_host_set_alpha select, one chain, seed =
+                                                 params.seed (as unsigned), params.time_limit when > 0, no cap on the moves of
+                                                 a trial; a span above window - 1 is cut to it; obj_best receives the
+                                                 recomputed cost                                                               */
 int HEU_seg_ils_greedy_edge(instance *inst);  /* HEU_greedy_edge, the batched 2-opt + Or-opt list descent (tsp_dev_nl_3opt_batch
                                                  with its default max_arc and rounds), then alg_seg_ils                        */
+/* The kinds of the two functions above: a non-empty subset of TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT (default: the first two);
+ * else TSP_DEV_E_ARG and the setting stays.  With TSP_NL_3OPT alg_seg_ils calls tsp_dev_seg_ils3 and the batched descent of
+ * HEU_seg_ils_greedy_edge runs over the same kinds; without it alg_seg_ils calls tsp_dev_seg_ils over `kinds`. */
+int tsp_host_set_seg_ils_kinds(int kinds);
 
 /* ---- src/tabusearch.c (externally linked there, not in its header) --------------------------- */
 int alg_2opt_tabu(instance *inst, int *skip_edge, int *stored_prev, const int iter, const int tenure); /* :107 */
@@ -314,6 +319,8 @@ void tsp_host_last_lb_stats(tsp_lb_stats *out);
 void tsp_host_last_greedy_edge_stats(tsp_greedy_edge_stats *out);
 /* Counters of the last alg_seg_ils call of this thread (also through HEU_seg_ils_greedy_edge). */
 void tsp_host_last_seg_ils_stats(tsp_seg_ils_stats *out);
+/* ... with the counters of the 3-opt kind behind them (all 0 when the call ran without it). */
+void tsp_host_last_seg_ils3_stats(tsp_seg_ils3_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */
 void tsp_host_shutdown(void);
 

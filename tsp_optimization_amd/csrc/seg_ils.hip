@@ -1,4 +1,4 @@
-// seg_ils.hip -- windowed iterated local search (tsp_dev_seg_ils).  The definitions are in include/tsp_hip.h.
+// seg_ils.hip -- windowed iterated local search (tsp_dev_seg_ils, tsp_dev_seg_ils3).  The definitions are in include/tsp_hip.h.
 //
 // Launch   k_seg_ils, one per iteration: grid (windows, chains), one workgroup = the T trials of one window of W consecutive tour
 //          nodes.  The window lives in LDS under "home" ids, the slot a node had when the kernel loaded it: seq (home id per slot),
@@ -8,10 +8,13 @@
 //          written before the trials are over.  Kick, moves and restore are permutations of a slot interval (seg_permute) followed
 //          by the edge lengths of that interval; a trial keeps the hull of its intervals and copies or restores nothing else.
 //          rem of an Or-opt segment is taken from E and one distance, in k_nl_prep's order, rather than kept per slot.
+//          With the 3-opt kind (k_seg_ils<.., true>) a decision also deals one lane per (p, u, w) of the active nodes p, and a
+//          3-opt move is the slot permutation of seg_move3.hpp.
 // Host     Descent::run queues the launches and looks at the clock between its batches; nothing is read per launch.
 #include "descent.hpp"
 #include "ils_common.hpp"
 #include "nl_common.hpp"
+#include "seg_move3.hpp"
 
 #include <cstddef>
 
@@ -42,8 +45,13 @@ struct SegWin {
     unsigned char *act, *hit;
 };
 
-// What a lane of the scan reads the window through: NlView's two / oro / roles over slots, a move kept only when every edge it
-// removes is a window edge (the tails at slots 0 .. W - 2) and, Or-opt, its segment is a window path.
+// k_nl3_scan's helpers (nl3_opt.hip) over window slots: two slots that hold different nodes which are not tour neighbours
+__device__ __forceinline__ bool seg_apart(int px, int py) { return px - py > 1 || py - px > 1; }
+__device__ __forceinline__ unsigned seg_pair_slots(int s, int t) { return ((unsigned)t << (3 * s)) | ((unsigned)s << (3 * t)); }
+__device__ __forceinline__ bool seg_same_edge(int x, int y, int p, int u) { return (x == p && y == u) || (x == u && y == p); }
+
+// What a lane of the scan reads the window through: NlView's two / oro / roles and k_nl3_scan's lane over slots, a move kept only
+// when every edge it removes is a window edge (the tails at slots 0 .. W - 2) and, Or-opt, its segment is a window path.
 template <int WT, bool INT>
 struct SegView {
     const double2 *coord;
@@ -98,6 +106,67 @@ struct SegView {
             }
         }
     }
+
+    // k_nl3_scan's lane (nl3_opt.hip) for one w of the list of q = succ p, over slots: the moves that remove (p, q) and add {p, u}
+    // and {q, w}; pos is the slot, order[] is at(), E[node] is E[the tail's slot].  p is a tail (pp <= W - 2), u and w are window
+    // nodes.  Two window slots differ by what their positions differ by (W <= n - 1), so the cyclic differences stay mod n.
+    __device__ __forceinline__ void three(int p, int pp, int u, int pu, int wn, int pw, double dk) {
+        const int pq = pp + 1, q = at(pq);
+        if (!seg_apart(pp, pu) || !seg_apart(pq, pw)) return;
+        const double dqw = d(q, wn);
+        // the neighbours of u and w inside the window (a choice that needs another one is no window move)
+        const int uP = pu >= 1 ? at(pu - 1) : 0, uS = pu <= W - 2 ? at(pu + 1) : 0;
+        const int wP = pw >= 1 ? at(pw - 1) : 0, wS = pw <= W - 2 ? at(pw + 1) : 0;
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) {
+            const int su = ch & 1, sw = ch >> 1;   // 0: the removed edge starts at u / w, 1: it ends there
+            if ((su ? pu < 1 : pu > W - 2) || (sw ? pw < 1 : pw > W - 2)) continue;   // the tail is at slot -1 or W - 1
+            const int tY = su ? uP : u, ptY = su ? pu - 1 : pu, hY = su ? u : uS;
+            const int tZ = sw ? wP : wn, ptZ = sw ? pw - 1 : pw, hZ = sw ? wn : wS;
+            const int yo = su ? uP : uS, pyo = su ? pu - 1 : pu + 1;   // the ends that the third new edge joins
+            const int zo = sw ? wP : wS, pzo = sw ? pw - 1 : pw + 1;
+            if (ptY == pp || ptZ == pp || ptY == ptZ || !seg_apart(pyo, pzo)) continue;
+            // roles 0, 1, 2 = a, b, c: a has the lowest tail, b and c follow it in tour order
+            const int pA = (p < tY && p < tZ) ? pp : (tY < tZ ? ptY : ptZ);
+            const int oX = ahead(pp, pA, n), oY = ahead(ptY, pA, n), oZ = ahead(ptZ, pA, n);
+            const int rX = (oY < oX) + (oZ < oX), rY = (oX < oY) + (oZ < oY), rZ = (oX < oZ) + (oY < oZ);
+            // the new edges as a matching of the slots role * 2 + (0 tail, 1 head)
+            const unsigned M = seg_pair_slots(rX * 2, rY * 2 + su) | seg_pair_slots(rX * 2 + 1, rZ * 2 + sw) |
+                               seg_pair_slots(rY * 2 + 1 - su, rZ * 2 + 1 - sw);
+            const int m0 = M & 7, m1 = (M >> 3) & 7, m3 = (M >> 9) & 7, m4 = (M >> 12) & 7;
+            int T = -1;
+            if (m0 == 3) T = m4 == 1 ? 0 : (m4 == 2 ? 3 : -1);   // (a,b1): with (c,a1) type 0, with (c,b) type 3
+            else if (m0 == 2) T = m1 == 4 ? 1 : -1;              // (a,b) (a1,c)
+            else if (m0 == 4) T = m3 == 1 ? 2 : -1;              // (a,c) (b1,a1)
+            if (T < 0) continue;
+            const int a = rX == 0 ? p : (rY == 0 ? tY : tZ), a1 = rX == 0 ? q : (rY == 0 ? hY : hZ);
+            const int b = rX == 1 ? p : (rY == 1 ? tY : tZ), b1 = rX == 1 ? q : (rY == 1 ? hY : hZ);
+            const int c = rX == 2 ? p : (rY == 2 ? tY : tZ), c1 = rX == 2 ? q : (rY == 2 ? hY : hZ);
+            const int pB = rX == 1 ? pp : (rY == 1 ? ptY : ptZ), pC = rX == 2 ? pp : (rY == 2 ? ptY : ptZ);
+            const int ob = rX == 1 ? oX : (rY == 1 ? oY : oZ), oc = rX == 2 ? oX : (rY == 2 ? oY : oZ);
+            const int s1 = ob, s2 = oc - ob, s3 = n - oc;
+            // a segment of one node: type 0 and the type that reverses that segment are the same new edges
+            int T2 = -1;
+            if (T == 0) T2 = s1 == 1 ? 3 : (s2 == 1 ? 2 : (s3 == 1 ? 1 : -1));
+            else if ((T == 3 && s1 == 1) || (T == 2 && s2 == 1) || (T == 1 && s3 == 1)) T2 = 0;
+            const double d3 = d(yo, zo);
+            const double old = (w.E[pA] + w.E[pB]) + w.E[pC];
+            const u64 key0 = (((u64)a * (u64)n + (u64)b) * (u64)n + (u64)c) * 4ull;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int Tq = r ? T2 : T;
+                if (Tq < 0) continue;
+                // (e1, e2, e3) of the type; each is one of the lane's three edges
+                const int x1 = a, y1 = Tq == 1 ? b : (Tq == 2 ? c : b1);
+                const int x2 = Tq == 1 ? a1 : (Tq == 2 ? b1 : c), y2 = Tq == 0 ? a1 : (Tq == 1 ? c : (Tq == 2 ? a1 : b));
+                const int x3 = Tq == 1 ? b1 : (Tq == 3 ? a1 : b), y3 = c1;
+                const double e1 = seg_same_edge(x1, y1, p, u) ? dk : (seg_same_edge(x1, y1, q, wn) ? dqw : d3);
+                const double e2 = seg_same_edge(x2, y2, p, u) ? dk : (seg_same_edge(x2, y2, q, wn) ? dqw : d3);
+                const double e3 = seg_same_edge(x3, y3, p, u) ? dk : (seg_same_edge(x3, y3, q, wn) ? dqw : d3);
+                take(((e1 + e2) + e3) - old, kNl3Bit | (key0 + (u64)Tq));
+            }
+        }
+    }
 };
 
 // Slots lo .. hi take the home ids of the slots src(k), a permutation of lo .. hi.  By every thread; `stage` holds hi - lo + 1 ids.
@@ -149,7 +218,8 @@ struct SegArgs {
     long long it;
 };
 
-template <int WT, bool INT>
+// K3: with the 3-opt kind (tsp_dev_seg_ils3 when kinds has TSP_NL_3OPT); without it no 3-opt code is compiled.
+template <int WT, bool INT, bool K3>
 __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restrict__ coord, int *__restrict__ orders,
                                                          int *__restrict__ poss, const int *__restrict__ nbr,
                                                          NlState *__restrict__ st, u64 *__restrict__ acc, SegArgs g) {
@@ -184,6 +254,7 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
     view.coord = coord; view.w = w; view.n = n; view.W = W; view.cnt = 0;
     // the same values in every thread; thread 0 adds them to the chain's
     long long decisions = 0, moves_all = 0, m2 = 0, mor = 0, ml1 = 0, ml2 = 0, ml3 = 0, mrev = 0, reversed = 0, active = 0, accepted = 0;
+    long long m3 = 0, mt[4] = {0, 0, 0, 0};   // K3
     // the slot of a window node
     auto slot_of = [&](int v) { return (int)w.lpos[ahead(pos[v], p0, n)]; };
 
@@ -240,13 +311,44 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
                 }
                 if (view.found) w.hit[r] = 1;
             }
+            if constexpr (K3) {
+                // one lane per (p, u, w): entry k1 of p's list and entry k2 of the list of q = succ p
+                if (g.kinds & TSP_NL_3OPT)
+                    for (int ln = tid; ln < na * K * K; ln += kSegThreads) {
+                        const int r = list[ln / (K * K)], k1 = (ln / K) % K, k2 = ln % K;
+                        const int pv = w.lpos[r];
+                        if (pv > W - 2) continue;   // p is no tail
+                        const int v = w.node[r], u = nbr[(size_t)v * K + k1];
+                        const int hu = ahead(pos[u], p0, n);
+                        if (hu >= W) continue;
+                        const int x = nbr[(size_t)view.at(pv + 1) * K + k2];
+                        const int hx = ahead(pos[x], p0, n);
+                        if (hx >= W) continue;
+                        view.found = false;
+                        view.three(v, pv, u, w.lpos[hu], x, w.lpos[hx], view.d(v, u));
+                        if (view.found) w.hit[r] = 1;
+                    }
+            }
             double bd = view.bd;
             u64 bk = view.bk;
             block_argmin<true>(bd, bk, s_d, s_k);   // (its barriers also stand between the hit flags and their readers)
             if (bk == kNoKey) break;                // no lane held an improving move: hit is all zero
             // the move in slots: lo .. hi are permuted, ends(m) as home ids from the window before the move
             int lo, hi;
-            if (!(bk & kNlOrBit)) {
+            bool is3 = false;
+            SegMove3 mv3 = {0, 0, 0, 0};
+            if constexpr (K3) is3 = (bk & kNl3Bit) != 0;
+            if (is3) {
+                const u64 key = bk & (kNl3Bit - 1), abc = key >> 2;
+                const int type = (int)(key & 3);
+                mv3 = seg3_make(slot_of((int)(abc / ((u64)n * (u64)n))), slot_of((int)((abc / (u64)n) % (u64)n)),
+                                slot_of((int)(abc % (u64)n)), type);
+                e[0] = w.seq[mv3.i]; e[1] = w.seq[mv3.i + 1]; e[2] = w.seq[mv3.j]; e[3] = w.seq[mv3.j + 1];
+                e[4] = w.seq[mv3.k]; e[5] = w.seq[mv3.k + 1];
+                ne = 6;
+                lo = mv3.i + 1; hi = mv3.k;
+                m3 += 1; mt[type] += 1;
+            } else if (!(bk & kNlOrBit)) {
                 const int px = slot_of((int)(bk / (u64)n)), py = slot_of((int)(bk % (u64)n));
                 lo = min(px, py) + 1; hi = max(px, py);
                 e[0] = w.seq[lo - 1]; e[1] = w.seq[lo]; e[2] = w.seq[hi]; e[3] = w.seq[hi + 1];
@@ -278,7 +380,9 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
                     if (q < ne && !w.act[e[q]]) { w.act[e[q]] = 1; next[cnt++] = (u16)e[q]; }
                 s_na = cnt;
             }
-            if (!(bk & kNlOrBit)) {
+            if (is3) {
+                seg_permute(w, stage, lo, hi, [=](int k) { return seg3_src(mv3, k); });
+            } else if (!(bk & kNlOrBit)) {
                 const int sum = lo + hi;
                 seg_permute(w, stage, lo, hi, [=](int k) { return sum - k; });
             } else {
@@ -325,6 +429,10 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
         add(Z.decisions, decisions); add(Z.moves, moves_all); add(Z.moves_2opt, m2); add(Z.moves_oropt, mor);
         add(Z.moves_len[0], ml1); add(Z.moves_len[1], ml2); add(Z.moves_len[2], ml3);
         add(Z.moves_rev, mrev); add(Z.reversed, reversed); add(Z.active_nodes, active);
+        if constexpr (K3) {
+            add(Z.moves_3opt, m3);
+            for (int q = 0; q < 4; ++q) add(Z.moves_type[q], mt[q]);
+        }
         if (accepted) atomicAdd(&acc[b], (u64)accepted);
     }
     unsigned long long cnt = view.cnt;
@@ -342,11 +450,14 @@ struct SegHooks : DescentPlain {
 }  // namespace
 
 static_assert(offsetof(tsp_seg_ils_stats, iterations) == sizeof(tsp_nl_opt_stats), "tsp_seg_ils_stats starts as tsp_nl_opt_stats");
+static_assert(offsetof(tsp_seg_ils3_stats, moves_3opt) == sizeof(tsp_seg_ils_stats), "tsp_seg_ils3_stats starts as tsp_seg_ils_stats");
 
-extern "C" int tsp_dev_seg_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
-                               uint64_t seed, int64_t iterations, int window, int span, int trials,
-                               int64_t max_moves_per_trial, double time_limit_s, tsp_seg_ils_stats *stats) {
-    int rc = tsp_nl_check(inst, &kinds, TSP_NL_2OPT | TSP_NL_OROPT, B, succ, succ_stride, tour_stride, obj);
+// What the two entry points do.  `allowed` is the kinds mask the entry point takes; the B records are `stride` bytes apart and
+// start as tsp_seg_ils_stats, with3: they are tsp_seg_ils3_stats.
+static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
+                   uint64_t seed, int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial,
+                   double time_limit_s, void *stats, size_t stride, bool with3) {
+    int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
     if (iterations < 0 || trials < 1) return TSP_DEV_E_ARG;
     const int n = inst->n;
@@ -386,8 +497,12 @@ extern "C" int tsp_dev_seg_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, 
                                    if (queued >= I) return;
                                    g.it = queued++;
                                    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-                                       hipLaunchKernelGGL((k_seg_ils<WTC, INTC>), dim3((unsigned)M, B), dim3(kSegThreads), lds, s,
-                                                          inst->d_coord, t->d_order, t->d_pos, x->d_nbr, x->d_st, x->d_seg_acc, g);
+                                       if (kinds & TSP_NL_3OPT)
+                                           hipLaunchKernelGGL((k_seg_ils<WTC, INTC, true>), dim3((unsigned)M, B), dim3(kSegThreads), lds,
+                                                              s, inst->d_coord, t->d_order, t->d_pos, x->d_nbr, x->d_st, x->d_seg_acc, g);
+                                       else
+                                           hipLaunchKernelGGL((k_seg_ils<WTC, INTC, false>), dim3((unsigned)M, B), dim3(kSegThreads), lds,
+                                                              s, inst->d_coord, t->d_order, t->d_pos, x->d_nbr, x->d_st, x->d_seg_acc, g);
                                    });
                                },
                                hooks);
@@ -396,10 +511,33 @@ extern "C" int tsp_dev_seg_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, 
     TSP_HIP_TRY(hipMemcpy(acc.data(), x->d_seg_acc, sizeof(u64) * B, hipMemcpyDeviceToHost));
     const double seconds = wall_s() - run.t0;
     for (int b = 0; b < B && stats; ++b) {
-        tsp_seg_ils_stats &o = stats[b];
+        tsp_seg_ils_stats &o = *reinterpret_cast<tsp_seg_ils_stats *>(static_cast<char *>(stats) + (size_t)b * stride);
         tsp_nl_write_stats(NlStatsOut{&o, sizeof o, 0}, 0, x->h_st[b], nullptr, 0.0, seconds, run.device_ms);
         o.iterations = queued; o.windows = M; o.trials = queued * M * trials; o.accepted = (int64_t)acc[b];
         o.active_nodes = x->h_st[b].active_nodes; o.start_cost = start[b];
+        if (with3) {
+            tsp_seg_ils3_stats &o3 = reinterpret_cast<tsp_seg_ils3_stats &>(o);
+            o3.moves_3opt = x->h_st[b].moves_3opt;
+            for (int k = 0; k < 4; ++k) o3.moves_by_type[k] = x->h_st[b].moves_type[k];
+        }
     }
     return status;
 }
+
+extern "C" {
+
+int tsp_dev_seg_ils(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj, uint64_t seed,
+                    int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial, double time_limit_s,
+                    tsp_seg_ils_stats *stats) {
+    return seg_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT, B, succ, succ_stride, tour_stride, obj, seed, iterations, window, span,
+                   trials, max_moves_per_trial, time_limit_s, stats, sizeof *stats, false);
+}
+
+int tsp_dev_seg_ils3(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj, uint64_t seed,
+                     int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial, double time_limit_s,
+                     tsp_seg_ils3_stats *stats) {
+    return seg_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj, seed, iterations,
+                   window, span, trials, max_moves_per_trial, time_limit_s, stats, sizeof *stats, true);
+}
+
+}  // extern "C"

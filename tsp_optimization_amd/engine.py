@@ -14,7 +14,7 @@ ENGINE_AUTO, ENGINE_GRID, ENGINE_LDS, ENGINE_CLUSTER = 0, 1, 2, 3
 OK, WRONG_STARTING_NODE, TIME_LIMIT_EXCEEDED = 0, 1, 2
 E_ARG = -3
 NL_2OPT, NL_OROPT = 1, 2
-NL_3OPT = 4   # tsp_dev_nl_3opt only
+NL_3OPT = 4   # tsp_dev_nl_3opt and what builds on it, and seg_ils3
 DLB_OFF, DLB_ON, DLB_CLOSE = 0, 1, 2   # don't-look bits of nl_3opt and ils
 NL_BATCH_DEFAULT_ROUNDS = 2            # claim rounds of nl_3opt_batch (TSP_NL_BATCH_DEFAULT_ROUNDS)
 NL_MAX_K, NL_DEFAULT_K = 16, 10
@@ -75,6 +75,10 @@ class IlsDlbStats(_Stats):
 class SegIlsStats(_Stats):
     _fields_ = NlOptStats._fields_ + [("iterations", C.c_int64), ("windows", C.c_int64), ("trials", C.c_int64),
                                       ("accepted", C.c_int64), ("active_nodes", C.c_int64), ("start_cost", C.c_double)]
+
+
+class SegIls3Stats(_Stats):
+    _fields_ = SegIlsStats._fields_ + [("moves_3opt", C.c_int64), ("moves_by_type", C.c_int64 * 4)]
 
 
 class LbStats(_Stats):
@@ -189,6 +193,7 @@ def lib():
                                             C.POINTER(Nl3OptStats)]
         L.tsp_dev_seg_ils.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_uint64, C.c_int64, C.c_int, C.c_int,
                                       C.c_int, C.c_int64, C.c_double, C.POINTER(SegIlsStats)]
+        L.tsp_dev_seg_ils3.argtypes = L.tsp_dev_seg_ils.argtypes[:-1] + [C.POINTER(SegIls3Stats)]
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
@@ -221,6 +226,7 @@ EXPORTED = [
     "tsp_dev_greedy_edge",
     "tsp_dev_nl_3opt_batch",
     "tsp_dev_seg_ils",
+    "tsp_dev_seg_ils3",
 ]
 
 COMM_ID_BYTES = 128
@@ -516,6 +522,20 @@ class Instance:
         st = (SegIlsStats * B)()
         rc = lib().tsp_dev_seg_ils(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations),
                                    int(window), int(span), int(trials), int(max_moves_per_trial), time_limit, st)
+        return _result(rc, single, succ2, o, st)
+
+    def seg_ils3(self, succ, iterations, window=0, span=0, trials=1, seed=0, kinds=NL_2OPT | NL_OROPT | NL_3OPT,
+                 max_moves_per_trial=-1, time_limit=-1.0, obj=None):
+        """seg_ils with the 3-opt kind in the repair (tsp_dev_seg_ils3): kinds is any non-empty subset of NL_2OPT | NL_OROPT |
+        NL_3OPT, a window 3-opt move is a segment move all three removed edges of which are window edges.  Arguments and result as
+        seg_ils, the stats with moves_3opt and moves_by_type behind them.  With kinds inside NL_2OPT | NL_OROPT it returns the bits
+        of seg_ils"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = _obj(obj, B)
+        st = (SegIls3Stats * B)()
+        rc = lib().tsp_dev_seg_ils3(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations),
+                                    int(window), int(span), int(trials), int(max_moves_per_trial), time_limit, st)
         return _result(rc, single, succ2, o, st)
 
     # -- Held-Karp lower bound (extension) ---------------------------------------------------

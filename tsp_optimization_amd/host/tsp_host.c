@@ -752,8 +752,9 @@ int HEU_ils_greedy_edge(instance *inst) { (void)HEU_greedy_edge(inst); return al
 
 /* ---- windowed iterated local search (extension) -------------------------------------------------------------- */
 
-static __thread tsp_seg_ils_stats t_seg_stats;
+static __thread tsp_seg_ils3_stats t_seg_stats;   /* starts as tsp_seg_ils_stats */
 static int g_seg_iters = 100, g_seg_window = 0, g_seg_span = 50, g_seg_trials = 1;   /* tsp_host_set_seg_ils */
+static int g_seg_kinds = TSP_NL_2OPT | TSP_NL_OROPT;                                 /* tsp_host_set_seg_ils_kinds */
 
 int tsp_host_set_seg_ils(int iterations, int window, int span, int trials) {
     if (iterations < 0 || trials < 1 || (span >= 1 && span <= 7)) return TSP_DEV_E_ARG;
@@ -767,14 +768,27 @@ int tsp_host_set_seg_ils(int iterations, int window, int span, int trials) {
     return 0;
 }
 
+int tsp_host_set_seg_ils_kinds(int kinds) {
+    if (kinds < 1 || (kinds & ~(TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT))) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_seg_kinds = kinds;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
 void tsp_host_last_seg_ils_stats(tsp_seg_ils_stats *out) {
+    if (out) memcpy(out, &t_seg_stats, sizeof *out);
+}
+
+void tsp_host_last_seg_ils3_stats(tsp_seg_ils3_stats *out) {
     if (out) *out = t_seg_stats;
 }
 
-/* tsp_dev_seg_ils over the lists alg_nl_opt would use, one chain from inst->solution */
+/* tsp_dev_seg_ils, or with the 3-opt kind set tsp_dev_seg_ils3, over the lists alg_nl_opt would use, one chain from
+ * inst->solution */
 int alg_seg_ils(instance *inst) {
     const int n = inst->num_nodes;
-    tsp_seg_ils_stats st;
+    tsp_seg_ils3_stats st;   /* without the 3-opt kind its first part is written and the 3-opt counters stay 0 */
     memset(&st, 0, sizeof st);
     double obj = inst->solution.obj_best;
     pthread_mutex_lock(&g_lock);
@@ -783,20 +797,25 @@ int alg_seg_ils(instance *inst) {
     const int span = g_seg_span > W - 1 ? W - 1 : g_seg_span;
     tsp_dev_inst *dev = dev_inst_locked(inst);
     int rc = lists_locked(inst, dev, obj);
-    if (rc == 0)
-        rc = tsp_dev_seg_ils(dev, TSP_NL_2OPT | TSP_NL_OROPT, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
+    const int three = (g_seg_kinds & TSP_NL_3OPT) != 0;
+    if (rc == 0 && three)
+        rc = tsp_dev_seg_ils3(dev, g_seg_kinds, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
+                              (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
+                              limit_of(inst), &st);
+    else if (rc == 0)
+        rc = tsp_dev_seg_ils(dev, g_seg_kinds, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
                              (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
-                             limit_of(inst), &st);
+                             limit_of(inst), (tsp_seg_ils_stats *)&st);
     pthread_mutex_unlock(&g_lock);
-    if (rc < 0) dev_fail("tsp_dev_seg_ils", rc);
+    if (rc < 0) dev_fail(three ? "tsp_dev_seg_ils3" : "tsp_dev_seg_ils", rc);
     inst->solution.obj_best = obj;
     t_seg_stats = st;
     if (rc == TIME_LIMIT_EXCEEDED) LOG_I("windowed iterated local search time exceeded");
     return rc;
 }
 
-/* construction, the batched 2-opt + Or-opt list descent under its defaults whatever tsp_host_set_batch says, alg_seg_ils: the
- * status is the last one's */
+/* construction, the batched 2-opt + Or-opt list descent (with the 3-opt kind set: over the kinds of tsp_host_set_seg_ils_kinds)
+ * under its defaults whatever tsp_host_set_batch says, alg_seg_ils: the status is the last one's */
 int HEU_seg_ils_greedy_edge(instance *inst) {
     (void)HEU_greedy_edge(inst);
     tsp_nl3_opt_stats st3;
@@ -806,7 +825,8 @@ int HEU_seg_ils_greedy_edge(instance *inst) {
     tsp_dev_inst *dev = dev_inst_locked(inst);
     int rc = lists_locked(inst, dev, obj);
     if (rc == 0)
-        rc = tsp_dev_nl_3opt_batch(dev, TSP_NL_2OPT | TSP_NL_OROPT, 0, 0, 1, &inst->solution.edges[0].j, 2,
+        rc = tsp_dev_nl_3opt_batch(dev, (g_seg_kinds & TSP_NL_3OPT) ? g_seg_kinds : (TSP_NL_2OPT | TSP_NL_OROPT), 0, 0, 1,
+                                   &inst->solution.edges[0].j, 2,
                                    2 * (int64_t)inst->num_nodes, &obj, -1, limit_of(inst), &st3);
     pthread_mutex_unlock(&g_lock);
     if (rc < 0) dev_fail("tsp_dev_nl_3opt_batch", rc);
