@@ -4,6 +4,7 @@
 //   two n pi pj | three n pa pc | or n pf pa L   -> "start len" of the kind's own function
 //   disj n s1 l1 s2 l2                -> 1 when the arcs are disjoint, else 0, from nl_arc_disjoint and, position by position, from
 //                                        nl_arc_holds: "d h"
+//   key n a b c type                  -> "k a b c type": k = nl3_key(a, b, c, type, n) and what nl3_unkey(k, n) gives back
 #include "nl_arc.hpp"
 
 #include <iostream>
@@ -35,6 +36,12 @@ int main() {
             in >> pf >> pa >> L;
             const tsp::NlArc a = tsp::nl_arc_or(pf, pa, L, n);
             std::cout << a.start << " " << a.len << "\n";
+        } else if (cmd == "key") {
+            int a = 0, b = 0, c = 0, type = 0;
+            in >> a >> b >> c >> type;
+            const unsigned long long k = tsp::nl3_key(a, b, c, type, n);
+            const tsp::Nl3Move m = tsp::nl3_unkey(k, n);
+            std::cout << k << " " << m.a() << " " << m.b() << " " << m.c() << " " << m.type() << "\n";
         } else if (cmd == "disj") {
             tsp::NlArc x{0, 0}, y{0, 0};
             in >> x.start >> x.len >> y.start >> y.len;

@@ -181,8 +181,9 @@ def commands(arc_cases):
         if m[1] == 0:
             out.append(("two %d %d %d" % (n, pos[m[2] // n], pos[m[2] % n]), want))
         elif m[1] == 2:
-            a, _, c, _ = N3.decode(m[2], n)
+            a, b, c, T = N3.decode(m[2], n)
             out.append(("three %d %d %d" % (n, pos[a], pos[c]), want))
+            out.append(("key %d %d %d %d %d" % (n, a, b, c, T), "%d %d %d %d %d" % (m[2], a, b, c, T)))   # nl3_key / nl3_unkey
         else:
             f, L, a, _ = R.decode(m[2], n)
             out.append(("or %d %d %d %d" % (n, pos[f], pos[a], L), want))
@@ -190,6 +191,8 @@ def commands(arc_cases):
     n = 1 << 20
     out.append(("two %d %d %d" % (n, n - 1, 0), "%d 3" % (n - 1)))
     out.append(("three %d %d %d" % (n, 5, 4), "5 %d" % n))
+    for a, b, c, T in ((0, 1, 2, 0), (n - 3, n - 2, n - 1, 3), (n - 3, n - 1, n - 2, 2), (7, n - 1, 8, 1)):   # the key's ends
+        out.append(("key %d %d %d %d %d" % (n, a, b, c, T), "%d %d %d %d %d" % (N3.key(a, b, c, T, n), a, b, c, T)))
     rng = np.random.default_rng(11)
     for n in (5, 6, 9, 16):
         for _ in range(200):

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void k_nl3_scan(const double2 *__restrict__ co
                     else if ((T == 3 && s1 == 1) || (T == 2 && s2 == 1) || (T == 1 && s3 == 1)) T2 = 0;
                     const double d3 = dsym<WT, INT>(coord, yo, zo);
                     const double old = (E[a] + E[b]) + E[c];
-                    const u64 key0 = (((u64)a * (u64)n + (u64)b) * (u64)n + (u64)c) * 4ull;
+                    const u64 key0 = nl3_key(a, b, c, 0, n);
 #pragma unroll
                     for (int r = 0; r < 2; ++r) {
                         const int Tq = r ? T2 : T;

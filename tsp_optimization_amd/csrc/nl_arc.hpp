@@ -1,6 +1,7 @@
 // nl_arc.hpp -- the arc of a move of the list descents: the cyclic range of tour positions that nl_apply_move
-// writes, extended by the ends of the removed edges, and when two arcs are disjoint.  Plain C++ for the host compiler and for
-// hipcc: the scans of the batched descent, its claim kernels (nl_batch.hip) and tests/nl_arc_check.cpp compile this very text.
+// writes, extended by the ends of the removed edges, and when two arcs are disjoint; and the key of a 3-opt move (nl3_key,
+// nl3_unkey).  Plain C++ for the host compiler and for hipcc: the scans of the batched descent, its claim kernels (nl_batch.hip),
+// the scans and the decoders of the 3-opt kind and tests/nl_arc_check.cpp compile this very text.
 // All positions are along the successor orientation, modulo n.
 #pragma once
 
@@ -42,13 +43,30 @@ TSP_ARC_HD NlArc nl_arc_or(int pf, int pa, int L, int n) {
     return arc_make(pa, m2 + L + 2, n);
 }
 
-// The arc of the move with decision key `key` (nl_common.hpp: bit 63 the 3-opt kind over ((a n + b) n + c) 4 + T, bit 62 Or-opt
-// over (((f 3 + L - 1) n + a) 2 + o), neither 2-opt over i n + j) on the tour whose node v is at position pos[v].
+// The 3-opt kind's own key, ((a n + b) n + c) 4 + type, below the kind bit of the decision key (nl_common.hpp), and back.  The
+// decoded move divides when it is asked, so that a caller pays for the tails it reads, in the order it reads them.
+TSP_ARC_HD unsigned long long nl3_key(int a, int b, int c, int type, int n) {
+    const unsigned long long un = (unsigned long long)n;
+    return (((unsigned long long)a * un + (unsigned long long)b) * un + (unsigned long long)c) * 4ull + (unsigned long long)type;
+}
+struct Nl3Move {
+    unsigned long long key;
+    int n;
+    TSP_ARC_HD unsigned long long abc() const { return key >> 2; }
+    TSP_ARC_HD int type() const { return (int)(key & 3); }
+    TSP_ARC_HD int a() const { return (int)(abc() / ((unsigned long long)n * (unsigned long long)n)); }
+    TSP_ARC_HD int b() const { return (int)((abc() / (unsigned long long)n) % (unsigned long long)n); }
+    TSP_ARC_HD int c() const { return (int)(abc() % (unsigned long long)n); }
+};
+TSP_ARC_HD Nl3Move nl3_unkey(unsigned long long key, int n) { return Nl3Move{key, n}; }
+
+// The arc of the move with decision key `key` (nl_common.hpp: bit 63 the 3-opt kind over nl3_key, bit 62 Or-opt over
+// (((f 3 + L - 1) n + a) 2 + o), neither 2-opt over i n + j) on the tour whose node v is at position pos[v].
 TSP_ARC_HD NlArc nl_arc_of_key(const int *pos, int n, unsigned long long key) {
     const unsigned long long un = (unsigned long long)n;
     if (key >> 63) {
-        const unsigned long long abc = (key & ~(1ull << 63)) >> 2;
-        return nl_arc_three(pos[(int)(abc / (un * un))], pos[(int)(abc % un)], n);
+        const Nl3Move m = nl3_unkey(key & ~(1ull << 63), n);
+        return nl_arc_three(pos[m.a()], pos[m.c()], n);
     }
     if (key >> 62) {
         const unsigned long long t = (key & ~(1ull << 62)) >> 1;

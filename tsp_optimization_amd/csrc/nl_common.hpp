@@ -14,7 +14,8 @@ namespace tsp {
 
 constexpr int kNlPickThreads = 1024;
 // decision key: the kind above the kind's own key, so that the unsigned order is (kind, key): 2-opt nothing, Or-opt bit 62,
-// 3-opt bit 63 (6 n^2 < 2^62; 4 n^3 <= 2^62 for n <= 2^20).  kNoKey (all ones) is no key of any kind.
+// 3-opt bit 63 (6 n^2 < 2^62; 4 n^3 <= 2^62 for n <= 2^20).  kNoKey (all ones) is no key of any kind.  The kinds' own keys: or_key /
+// or_unkey (or_opt_shift.hpp), nl3_key / nl3_unkey (nl_arc.hpp, which the host compiler reads too).
 constexpr u64 kNlOrBit = 1ull << 62;
 constexpr u64 kNl3Bit = 1ull << 63;
 constexpr int kNlMaxN3 = 1 << 20;   // 4 n^3 must stay below the kind bits of the decision key
@@ -98,10 +99,9 @@ template <int NT>
 __device__ __forceinline__ void nl_apply_move(int *__restrict__ order, int *__restrict__ pos, NlState &S, int n, u64 bk) {
     const int tid = threadIdx.x;
     if (bk & kNl3Bit) {
-        const u64 key = bk & (kNl3Bit - 1);
-        const int T = (int)(key & 3);
-        const u64 abc = key >> 2;
-        const int c = (int)(abc % (u64)n), b = (int)((abc / (u64)n) % (u64)n), a = (int)(abc / ((u64)n * (u64)n));
+        const Nl3Move m = nl3_unkey(bk & (kNl3Bit - 1), n);
+        const int T = m.type();
+        const int c = m.c(), b = m.b(), a = m.a();
         const int pa = pos[a];
         const int s1 = ahead(pos[b], pa, n), s2 = ahead(pos[c], pa, n) - s1;
         const int at1 = or_wrap(pa + 1, n), at2 = or_wrap(at1 + s1, n);   // where S1 = a1 .. b and S2 = b1 .. c start

@@ -250,7 +250,7 @@ struct NlEnds {
 __device__ __forceinline__ NlEnds nl_move_ends(const int *__restrict__ order, const int *__restrict__ pos, int n, u64 bk) {
     NlEnds r;
     if (bk & kNl3Bit) {
-        const u64 abc = (bk & (kNl3Bit - 1)) >> 2;
+        const u64 abc = (bk & (kNl3Bit - 1)) >> 2;   // nl3_unkey's divisions, written out: see profiles/nl3_lane_refactor.txt
         r.e0 = (int)(abc / ((u64)n * (u64)n)); r.e2 = (int)((abc / (u64)n) % (u64)n); r.e4 = (int)(abc % (u64)n);
         r.e1 = order[or_wrap(pos[r.e0] + 1, n)]; r.e3 = order[or_wrap(pos[r.e2] + 1, n)]; r.e5 = order[or_wrap(pos[r.e4] + 1, n)];
         r.ne = 6;

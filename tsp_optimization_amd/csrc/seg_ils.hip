@@ -151,7 +151,7 @@ struct SegView {
             else if ((T == 3 && s1 == 1) || (T == 2 && s2 == 1) || (T == 1 && s3 == 1)) T2 = 0;
             const double d3 = d(yo, zo);
             const double old = (w.E[pA] + w.E[pB]) + w.E[pC];
-            const u64 key0 = (((u64)a * (u64)n + (u64)b) * (u64)n + (u64)c) * 4ull;
+            const u64 key0 = nl3_key(a, b, c, 0, n);
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 const int Tq = r ? T2 : T;
@@ -339,10 +339,9 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
             SegMove3 mv3 = {0, 0, 0, 0};
             if constexpr (K3) is3 = (bk & kNl3Bit) != 0;
             if (is3) {
-                const u64 key = bk & (kNl3Bit - 1), abc = key >> 2;
-                const int type = (int)(key & 3);
-                mv3 = seg3_make(slot_of((int)(abc / ((u64)n * (u64)n))), slot_of((int)((abc / (u64)n) % (u64)n)),
-                                slot_of((int)(abc % (u64)n)), type);
+                const Nl3Move m = nl3_unkey(bk & (kNl3Bit - 1), n);
+                const int type = m.type();
+                mv3 = seg3_make(slot_of(m.a()), slot_of(m.b()), slot_of(m.c()), type);
                 e[0] = w.seq[mv3.i]; e[1] = w.seq[mv3.i + 1]; e[2] = w.seq[mv3.j]; e[3] = w.seq[mv3.j + 1];
                 e[4] = w.seq[mv3.k]; e[5] = w.seq[mv3.k + 1];
                 ne = 6;
