@@ -2,19 +2,24 @@
 // on one at a time, what follows them in the kernel: the DPP-fed sums, the min3 / compare / branch on a scalar bound, the update
 // of the kept sums.  4 chains per wave; 1 and 4 waves per SIMD.  kb: the same tails with the test once per batch of four rows --
 // DPP sums + min + compare per row, the four masks OR-ed, one branch per four rows (k_exh's row loop since the batched bound).
+// SEED: the distance body is the shortened chain from an fp32 root (csrc/exh_arith.hpp, the seed form, NINT) instead of the fp64
+// root with floor and v_cvt_i32_f64; run with the tail the kernel uses (7, one branch per row).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include "../../tsp_optimization_amd/csrc/exh_arith.hpp"
 #pragma clang fp contract(off)
 #define ITER 2048
+template <bool SEED = false>
 __device__ __forceinline__ int dist(double cx, double cy, double rx, double ry) {
     const double dx = cx - rx, dy = cy - ry;
     const double s = __builtin_fma(dx, dx, dy * dy);
+    if (SEED) return tsp::exh_seed_round<tsp::EXH_NINT>(s, __builtin_amdgcn_sqrtf(tsp::exh_seed_arg<tsp::EXH_NINT>(s)));
     const double k = floor(__builtin_amdgcn_sqrt(s) + 0.25);
     const double e = __builtin_fma(-k, k, s);
     return __double2int_rz(k) + (e > k ? 1 : 0);
 }
-template <int TAIL>
+template <int TAIL, bool SEED = false>
 __global__ __launch_bounds__(256) void k(int *out, const double2 *__restrict__ rows, const int *__restrict__ er, int nrows, int wbd) {
     constexpr int NCH = 4;
     double cx[NCH], cy[NCH];
@@ -27,7 +32,7 @@ __global__ __launch_bounds__(256) void k(int *out, const double2 *__restrict__ r
         p = p + 1 == nrows ? 0 : p + 1;
         int D[NCH], sum[NCH];
 #pragma unroll
-        for (int q = 0; q < NCH; ++q) D[q] = dist(cx[q], cy[q], r.x, r.y);
+        for (int q = 0; q < NCH; ++q) D[q] = dist<SEED>(cx[q], cy[q], r.x, r.y);
         if (TAIL & 1) {
             sum[0] = __builtin_amdgcn_update_dpp(0, S[NCH - 1], 0x138, 0xf, 0xf, true) + D[0];
 #pragma unroll
@@ -96,18 +101,18 @@ __global__ __launch_bounds__(256) void kb(int *out, const double2 *__restrict__ 
     for (int q = 0; q < NCH; ++q) s += S[q];
     out[blockIdx.x * 256 + threadIdx.x] = s;
 }
-template <int TAIL, bool BATCH = false>
+template <int TAIL, bool BATCH = false, bool SEED = false>
 void run(int waves_per_simd, int *d, double2 *rows, int *er) {
     const int blocks = 256 * waves_per_simd;
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    auto *kern = BATCH ? kb<TAIL> : k<TAIL>;
+    auto *kern = BATCH ? kb<TAIL> : k<TAIL, SEED>;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, 0, d, rows, er, 4096, -100000000);
     (void)hipEventRecord(e0);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, 0, d, rows, er, 4096, -100000000);
     (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
     float ms; (void)hipEventElapsedTime(&ms, e0, e1);
     const double per_simd = (double)waves_per_simd * ITER;
-    printf("tail %d%s, waves per SIMD %d: %7.3f ms, %6.1f ns per wave row step per SIMD (= %5.1f cycles at 2.15 GHz; 4 distances alone: 241)\n", TAIL, BATCH ? " one branch per 4 rows" : "", waves_per_simd, ms,
+    printf("tail %d%s%s, waves per SIMD %d: %7.3f ms, %6.1f ns per wave row step per SIMD (= %5.1f cycles at 2.15 GHz; 4 distances alone: 241)\n", TAIL, BATCH ? " one branch per 4 rows" : "", SEED ? " fp32-seed chain" : "", waves_per_simd, ms,
            ms * 1e6 / per_simd, ms * 1e-3 * 2.15e9 / per_simd);
 }
 int main(int argc, char **argv) {
@@ -116,6 +121,7 @@ int main(int argc, char **argv) {
     int *er; (void)hipMalloc(&er, 4096 * sizeof(int));
     (void)hipMemset(rows, 0, 4096 * sizeof(double2)); (void)hipMemset(er, 0, 4096 * sizeof(int));
     for (int w : {1, 4}) { run<0>(w, d, rows, er); run<1>(w, d, rows, er); run<2>(w, d, rows, er); run<3>(w, d, rows, er); run<4>(w, d, rows, er); run<7>(w, d, rows, er);
-                          run<3, true>(w, d, rows, er); run<7, true>(w, d, rows, er); }
+                          run<3, true>(w, d, rows, er); run<7, true>(w, d, rows, er);
+                          run<0, false, true>(w, d, rows, er); run<7, false, true>(w, d, rows, er); }
     return 0;
 }

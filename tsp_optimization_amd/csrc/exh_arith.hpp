@@ -76,6 +76,32 @@ TSP_EXH_HD int exh_round(double s, double g) {
     return exh_d(exh_ki(k), exh_up<MODE>(k, exh_e<MODE>(s, k)));
 }
 
+// ---- the seed form: the same integer from an fp32 root (what k_exh computes; tests/test_cpu_exh_seed.py) ------------------------
+// The one-sided fix-up above needs the seed within 0.5 of the true root r, not 0.25, and that an fp32 root delivers: the
+// argument rounded to fp32 (2^-25 relative, 2^-26 in the root) and the root instruction's own error (1 ulp) leave the seed
+// within 1.25 fp32 ulps of r, and below 2^21 an ulp is at most 0.125.  (Checked with the seed moved by +-2 ulps: exact for every
+// root below 2^21, and no further -- at 2^21 the ulp is 0.25 and +-2 ulps reach the 0.5.)  s = 0 gives the seed 0 and k = 0.
+// The integer root then comes straight out of the fp32 value and ONE conversion feeds the residual, which is the fp64 fma of
+// the form above -- exact --, so no fp64 root, no fp64 rounding and no fp64-to-integer conversion is left:
+//   cvt_f32_f64 -> sqrt_f32 -> cvt_i32_f32 (NINT: truncation = floor, g >= 0; CEIL / ATT: of rint(g)) -> cvt_f64_i32 -> fma ->
+//   compare -> add-with-carry.
+// gf is the approximate fp32 root of exh_seed_arg(s).
+template <int MODE>
+TSP_EXH_HD float exh_seed_arg(double s) { return (float)exh_root_arg<MODE>(s); }
+
+template <int MODE>
+TSP_EXH_HD int exh_seed_ki(float gf) { return MODE == EXH_NINT ? (int)gf : (int)__builtin_rintf(gf); }
+
+TSP_EXH_HD double exh_seed_k(int ki) { return (double)ki; }
+
+// residual, compare and final add are exh_e, exh_up and exh_d of the form above
+template <int MODE>
+TSP_EXH_HD int exh_seed_round(double s, float gf) {
+    const int ki = exh_seed_ki<MODE>(gf);
+    const double k = exh_seed_k(ki);
+    return exh_d(ki, exh_up<MODE>(k, exh_e<MODE>(s, k)));
+}
+
 // the same distance from two records (the first one as the column): what k_exh computes for a pair of positions, and what
 // k_move_pos computes at a cut point of a move.  root(v) is the approximate root of v: the hardware's on the device.
 template <int MODE, class Root>

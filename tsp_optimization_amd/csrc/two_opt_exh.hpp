@@ -17,6 +17,13 @@
 // sweep may visit the pairs in any order: the decision is the arg-min of (delta, (i, j)) with the nodes' own ids as the
 // tie-break (strict '<' at tabusearch.c:151 keeps the first pair in (i < j) order), which is what every lane keeps.
 // Every delta is still computed exactly (integer-valued distances from the exact roots of tsp_dist.hpp's int_root).
+// The root.  k_exh takes the integer root from an fp32 seed (exh_arith.hpp, the seed form): s, exact in fp64, is rounded to
+// fp32, v_sqrt_f32 gives the seed, the integer comes out of the fp32 value (truncated for EUC_2D, rounded for CEIL_2D and ATT), its
+// fp64 image feeds the exact residual s - k^2, and the one-sided fix-up adds the carry: convert, root, convert, convert, fma,
+// compare, add-with-carry -- no v_sqrt_f64 (16 cycles of the port against 8), no fp64 floor, no fp64-to-integer conversion.
+// Exact for every root below 2^21 with the seed up to 2 fp32 ulps off (tests/test_cpu_exh_seed.py, tests/test_gpu_exh_seed.py;
+// +3.2 % on bench.py).  k_move_pos keeps the fp64 root for its two cut-point distances per sweep (exh_perm_rec): both
+// forms give the same integers.
 //
 // Layout.  k_move_pos (one thread per position) DECIDES the previous sweep's move -- every block for itself, from the
 // candidates k_exh left and the positions of their pairs beside them (sweep_load + sweep_reduce, two_opt_step.hpp: pos is not
@@ -87,15 +94,17 @@ constexpr bool exh_metric() { return WT == WT_EUC_2D_ICOORD || WT == WT_CEIL_2D_
 template <int WT>
 constexpr int exh_mode() { return WT == WT_EUC_2D_ICOORD ? EXH_NINT : (WT == WT_CEIL_2D_ICOORD ? EXH_CEIL : EXH_ATT); }
 
-// the exact integer-valued distance of tsp_dist.hpp's int_root as an int32 (exh_arith.hpp)
+// the exact integer-valued distance of tsp_dist.hpp's int_root as an int32 (exh_arith.hpp, the seed form: an fp32 root under
+// the one-sided fix-up in fp64)
 template <int WT>
 __device__ __forceinline__ int exh_dist(double cx, double cy, double cn, const ExhRec &r) {
     const double s = exh_s(cx, cy, cn, r.m2x, r.m2y, r.nrm);
-    return exh_round<exh_mode<WT>()>(s, __builtin_amdgcn_sqrt(exh_root_arg<exh_mode<WT>()>(s)));
+    return exh_seed_round<exh_mode<WT>()>(s, __builtin_amdgcn_sqrtf(exh_seed_arg<exh_mode<WT>()>(s)));
 }
 
 // The same for the RJ columns of a lane against one row, STAGE BY STAGE across the columns: the wave issues in order, so the RJ
-// dependent chains (add -> fma -> fma -> sqrt -> round -> fma -> compare -> convert -> add-with-carry) only overlap if
+// dependent chains (add -> fma -> fma -> convert to fp32 -> fp32 root -> convert to integer -> convert to fp64 -> fma -> compare ->
+// add-with-carry; CEIL_2D and ATT round the fp32 root first, ATT multiplies twice more) only overlap if
 // their instructions are interleaved in the stream.  Left to itself the scheduler keeps most of a chain together (fewer live
 // registers) and a lone wave then runs the chains one after the other (RJ = 16, one wave per SIMD: 2 960 cycles per row step
 // against 1 056 of issue).  The scheduling barriers pin the stage order.
@@ -104,22 +113,29 @@ __device__ __forceinline__ void exh_dist_row(const double (&cx)[RJ], const doubl
                                              int (&D)[RJ]) {
     constexpr int M = exh_mode<WT>();
     double s[RJ], k[RJ], e[RJ];
+    float g[RJ];
     int ki[RJ];
     bool up[RJ];
 #pragma unroll
     for (int q = 0; q < RJ; ++q) s[q] = exh_s(cx[q], cy[q], cn[q], r.m2x, r.m2y, r.nrm);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int q = 0; q < RJ; ++q) k[q] = __builtin_amdgcn_sqrt(exh_root_arg<M>(s[q]));
+    for (int q = 0; q < RJ; ++q) g[q] = exh_seed_arg<M>(s[q]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int q = 0; q < RJ; ++q) k[q] = exh_k<M>(k[q]);
+    for (int q = 0; q < RJ; ++q) g[q] = __builtin_amdgcn_sqrtf(g[q]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < RJ; ++q) ki[q] = exh_seed_ki<M>(g[q]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < RJ; ++q) k[q] = exh_seed_k(ki[q]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < RJ; ++q) e[q] = exh_e<M>(s[q], k[q]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int q = 0; q < RJ; ++q) { ki[q] = exh_ki(k[q]); up[q] = exh_up<M>(k[q], e[q]); }   // every compare before the first
+    for (int q = 0; q < RJ; ++q) up[q] = exh_up<M>(k[q], e[q]);   // every compare before the first
     __builtin_amdgcn_sched_barrier(0);   // add-with-carry, each with a carry register of its own (back to back they wait on VCC)
 #pragma unroll
     for (int q = 0; q < RJ; ++q) {
