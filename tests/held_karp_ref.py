@@ -3,10 +3,12 @@
   weight of edge {i,j}, lo = min, hi = max:  w = (d(lo,hi) + pi[lo]) + pi[hi]
   edge order: lexicographic on (w, lo, hi) -- strict, so the minimum spanning tree is unique
   1-tree: the minimum spanning tree of nodes 1 .. n-1 under that order + the two smallest edges at node 0
-  value:  W(pi) = sum of w(e) - 2 sum of pi   (math.fsum here)
+  value:  W(pi) = sum of w(e) - 2 sum of pi   (math.fsum here; `sum_order`: plain sums in a random order instead)
   ascent: pi as given, lambda = lambda0, best = -inf, stall = 0; per iteration the 1-tree, W, g = deg - 2; W > best keeps
           best / pi_best and clears stall, else stall += 1 and at `patience` lambda is halved; |g|^2 == 0 stops (a tour);
           t = lambda (ub - W) / |g|^2, pi += t (0.7 g + 0.3 g_prev), g_prev = g in the first iteration.
+  Boruvka rounds (what the device's `rounds` counts): over nodes 1 .. n-1, every component takes its smallest outgoing edge
+          under the same order, all chosen edges are contracted; a round counts while more than one component exists.
 
 `D` is the oracle's distance matrix (oracle.oracle.dist_matrix), or any object with `n` and `row(t)` = d(min(t,u), max(t,u))
 for every u (Euc2DRows: sizes whose matrix does not fit)."""
@@ -50,9 +52,18 @@ def _weights(R, pi, t, idx):
     return (d + np.where(below, pi, pi[t])) + np.where(below, pi[t], pi)
 
 
-def one_tree(D, pi=None):
+def _plain_sum(x, rng):
+    """x summed left to right in double, in an order drawn from rng: some summation order other than fsum's"""
+    s = 0.0
+    for v in x[rng.permutation(len(x))].tolist():
+        s += v
+    return s
+
+
+def one_tree(D, pi=None, sum_order=None):
     """-> (edges [n,2] sorted (lo, hi), deg [n], value, weights [n] in the edges' order).  Prim, vectorised over the
-    frontier; every choice is the smallest (w, lo, hi) across the cut."""
+    frontier; every choice is the smallest (w, lo, hi) across the cut.  sum_order: None = math.fsum, or a numpy generator:
+    the value from plain sums of the randomly permuted weights and penalties."""
     R = _rows(D)
     n = R.n
     assert n >= 3
@@ -85,7 +96,10 @@ def one_tree(D, pi=None):
     edges = np.array([(a, b) for a, b, _ in E], dtype=np.int32)
     deg = np.bincount(edges.ravel(), minlength=n).astype(np.int32)
     ws = np.array([w for _, _, w in E])
-    value = math.fsum(ws) - 2.0 * math.fsum(pi)
+    if sum_order is None:
+        value = math.fsum(ws) - 2.0 * math.fsum(pi)
+    else:
+        value = _plain_sum(ws, sum_order) - 2.0 * _plain_sum(pi, sum_order)
     return edges, deg, value, ws
 
 
@@ -127,8 +141,18 @@ def default_patience(n):
     return max(10, n // 20)
 
 
-def ascent(D, ub, iters=300, lambda0=2.0, patience=0, pi=None):
-    """-> (best, pi_best, info); info: iterations, tour_found, lambda, trace (best after every iteration)."""
+class Step:
+    """One iteration of the ascent: `pi` the penalties its tree was built for, `W`, `deg`, `g2` = |g|^2 of that tree, and
+    `best`, `lam`, `pi_best` after the iteration's bookkeeping."""
+    __slots__ = ("k", "pi", "W", "deg", "g2", "best", "lam", "pi_best")
+
+    def __init__(self, **kw):
+        for f, v in kw.items():
+            setattr(self, f, v)
+
+
+def ascent_trace(D, ub, iters, lambda0=2.0, patience=0, pi=None, sum_order=None):
+    """The ascent, every iteration kept -> [Step]; it ended on a tour iff the last step's g2 is 0.  sum_order as one_tree's."""
     R = _rows(D)
     n = R.n
     pi = np.zeros(n) if pi is None else np.array(pi, dtype=np.float64)
@@ -136,11 +160,9 @@ def ascent(D, ub, iters=300, lambda0=2.0, patience=0, pi=None):
     lam, best, stall = float(lambda0), -math.inf, 0
     pi_best = pi.copy()
     g_prev = None
-    trace = []
-    tour = False
-    k = 0
+    steps = []
     for k in range(1, iters + 1):
-        _, deg, W, _ = one_tree(R, pi)
+        _, deg, W, _ = one_tree(R, pi, sum_order)
         g = deg.astype(np.float64) - 2.0
         if W > best:
             best, pi_best, stall = W, pi.copy(), 0
@@ -148,14 +170,58 @@ def ascent(D, ub, iters=300, lambda0=2.0, patience=0, pi=None):
             stall += 1
             if stall >= patience:
                 lam, stall = lam * 0.5, 0
-        trace.append(best)
         g2 = float(np.dot(g, g))
+        steps.append(Step(k=k, pi=pi, W=W, deg=deg, g2=g2, best=best, lam=lam, pi_best=pi_best))
         if g2 == 0.0:
-            tour = True
             break
         if g_prev is None:
             g_prev = g
         t = lam * (ub - W) / g2
         pi = pi + t * (0.7 * g + 0.3 * g_prev)
         g_prev = g
-    return best, pi_best, {"iterations": k, "tour_found": tour, "lambda": lam, "trace": trace}
+    return steps
+
+
+def ascent(D, ub, iters=300, lambda0=2.0, patience=0, pi=None):
+    """-> (best, pi_best, info); info: iterations, tour_found, lambda, trace (best after every iteration)."""
+    steps = ascent_trace(D, ub, iters, lambda0, patience, pi)
+    last = steps[-1]
+    return last.best, last.pi_best, {"iterations": last.k, "tour_found": last.g2 == 0.0, "lambda": last.lam,
+                                     "trace": [s.best for s in steps]}
+
+
+def boruvka(D, pi=None, hi_first=False):
+    """Boruvka over nodes 1 .. n-1 -> (rounds, the spanning tree's edges, sorted).  In a round every component takes its
+    smallest outgoing edge under (w, lo, hi), all chosen edges are contracted, and the round counts while more than one
+    component exists at its start.  hi_first: the order (w, hi, lo) instead (to show that the order matters)."""
+    R = _rows(D)
+    n = R.n
+    pi = np.zeros(n) if pi is None else np.asarray(pi, dtype=np.float64)
+    idx = np.arange(n)
+    w = np.array([_weights(R, pi, t, idx) for t in range(n)])
+    w[0, :] = w[:, 0] = np.inf   # node 0 is not part of the spanning tree
+    comp = idx.copy()
+    E = set()
+    rounds = 0
+    while len(set(comp[1:].tolist())) > 1:
+        rounds += 1
+        out = np.where(comp[:, None] != comp[None, :], w, np.inf)
+        other = out.argmin(axis=1)   # of a node's equal weights the lowest other end: its smallest (lo, hi) and (hi, lo) alike
+        pick = {}
+        for v in range(1, n):
+            u = int(other[v])
+            lo, hi = min(u, v), max(u, v)
+            key = (float(out[v, u]), hi, lo) if hi_first else (float(out[v, u]), lo, hi)
+            c = int(comp[v])
+            if c not in pick or key < pick[c][0]:
+                pick[c] = (key, lo, hi)
+        for _, lo, hi in pick.values():
+            E.add((lo, hi))
+            a, b = comp[lo], comp[hi]
+            if a != b:   # (equal when both chose this edge and the first pick has joined them)
+                comp[comp == b] = a
+    return rounds, sorted(E)
+
+
+def boruvka_rounds(D, pi=None):
+    return boruvka(D, pi)[0]
