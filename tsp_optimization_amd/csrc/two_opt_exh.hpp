@@ -34,8 +34,8 @@
 // Records by permutation.  A 2-opt move only permutes positions: but for the two cut points, the record of the new position k is
 // bit for bit an old record and its e is an old e (exh_perm, exh_arith.hpp; tests/test_cpu_exh_permute.py).  A tour has two
 // record buffers; k_move_pos<HOT> reads one and writes the other, the k_exh behind it reads what it wrote, the host flips
-// them with the pair of launches.  The chain of a hot launch is kernel arguments -> {control block, candidates} -> arg-min ->
-// old records -> stores: order, pos and coord are not read (order and pos are still written, for every other reader).  The
+// them with the pair of launches.  The chain of a hot launch is {control block, candidates} -> arg-min -> old records ->
+// stores (their addresses come from preloaded kernel arguments): order, pos and coord are not read (order and pos are still written, for every other reader).  The
 // first sweep of a run call is cold (built from order and coord): only inside a run call does the host know that the old buffer
 // describes the tour (tsp_dev_tours::exh_hot).
 // Hand-off.  k_exh ends at its block's candidate and, from the lane that owns the winning key, (pos[i], pos[j]) of that pair in
@@ -52,8 +52,13 @@
 // a strip's rows are its units of work, and the units of all strips, laid end to end, are dealt to the waves in
 // contiguous ranges -- by the host, once per tours handle (exh_deal, exh_arith.hpp: strip, row and number of units per wave, in
 // a table the wave reads with one scalar load); the wave walks the strips from there, over as many as its range covers.
-// The start of a wave, which every wave of the launch goes through at once and nothing hides, is three waits on memory: the
-// kernel arguments; `done` and the descriptor; the columns' records, row pa and the first batch of rows.  Per row step a lane
+// The start of a wave, which every wave of the launch goes through at once and nothing hides, is two waits on memory: `done`
+// and the descriptor; the columns' records, row pa and the first batch of rows.  The kernel arguments those need are in the
+// wave's SGPRs when it starts (kernel-argument preload: the parameters of both kernels are ordered for it; firmware that does
+// not preload runs the compiler's prologue, which loads them, and then the waits are three).  Measured and not kept, DESIGN
+// 4.9: the descriptor evaluated by the wave in closed form instead of loaded (one wait, but about 90 scalar instructions more
+// per wave: -2.0 %), and the ids of a lane's best pair asked for where the pair is taken (the compiler waits for them at the
+// join behind every row's branch: -2.8 %).  Per row step a lane
 // computes D(p, q) for its RJ columns (row operands are wave-uniform: scalar loads, no LDS), forms
 //     sum = D(p - 1, q - 1) + D(p, q) - e[q - 1]             (one three-operand add; D(p - 1, q - 1): own register, or
 //                                                             v_mov_b32_dpp wave_shr:1 for the lane's first column)
@@ -151,15 +156,18 @@ __device__ __forceinline__ void exh_dist_row(const double (&cx)[RJ], const doubl
 // HOT: `rec_old` holds the records of the tour BEFORE the move (the previous sweep's, written by the previous k_move_pos of the
 // same run call: the host knows, tsp_dev_tours::exh_hot) and the new ones are a permutation of them (exh_perm, exh_arith.hpp):
 // order, pos and coord are not read, no root is taken but at the move's two cut points, and the chain of the launch is
-// kernel arguments -> {control block, candidates} -> arg-min -> old records -> stores.  Otherwise (the first sweep of a run
+// {control block, candidates} -> arg-min -> old records -> stores.  Otherwise (the first sweep of a run
 // call) the records are built from order and coord, two round trips more.
+// The order of the parameters: what the head of the chain needs comes first and fills the 14 dwords that a wave finds in its
+// SGPRs when it starts (kernel-argument preload, csrc/Makefile), so {control block, candidates} are asked for with no wait in
+// front of them; the rest is fetched by the entry's one batch of scalar loads.
 template <int WT, bool INT, bool HOT>
-__global__ __launch_bounds__(kScanThreads) void k_move_pos(const double2 *__restrict__ coord, int *orders, int *poss, int *orders2,
-                                                           int *poss2, const TourState *__restrict__ states,
-                                                           TourState *__restrict__ states_next, const Partial *__restrict__ partials,
-                                                           const int2 *__restrict__ wpos, size_t partial_per_tour, int flat_slots,
-                                                           const ExhRec *__restrict__ rec_old, ExhRec *__restrict__ rec,
-                                                           int *__restrict__ pid, int n) {
+__global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__restrict__ states, const Partial *__restrict__ partials,
+                                                           const int2 *__restrict__ wpos, const ExhRec *__restrict__ rec_old,
+                                                           size_t partial_per_tour, int flat_slots, int n, ExhRec *__restrict__ rec,
+                                                           int *__restrict__ pid, TourState *__restrict__ states_next,
+                                                           const double2 *__restrict__ coord, int *orders, int *poss, int *orders2,
+                                                           int *poss2) {
     static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only (integer costs: the tour cost needs no staging)");
     __shared__ double s_d[kScanThreads / 64];
     __shared__ u64 s_k[kScanThreads / 64];
@@ -279,11 +287,16 @@ __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__res
     }
 }
 
-// RJ = kExhRJ columns per lane, four workgroups of four waves per CU (the host pins that with its LDS request)
+// RJ = kExhRJ columns per lane, four workgroups of four waves per CU (the host pins that with its LDS request).
+// The order of the parameters: `states` (the read-only view: `done`), the records, n, the table of the dealing, the ids, the
+// positions' array and the stride of the candidates are 14 dwords, which a wave finds in its SGPRs when it starts
+// (kernel-argument preload, csrc/Makefile: a struct by value ends the preload, so there is none), and the loads of `done` and of
+// the descriptor are issued with no wait in front of them; the two pointers of the epilogue follow.
 template <int WT, bool INT, int RJ>
-__global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const ExhRec *__restrict__ rec_all,
-                                                      const int *__restrict__ pid_all, const ExhDeal *__restrict__ deal,
-                                                      int2 *__restrict__ wpos_all) {
+__global__ __launch_bounds__(kScanThreads, 1) void k_exh(const TourState *__restrict__ states, const ExhRec *__restrict__ rec_all, int n,
+                                                      const ExhDeal *__restrict__ deal, const int *__restrict__ pid_all,
+                                                      int2 *__restrict__ wpos_all, int partial_per_tour,
+                                                      Partial *__restrict__ partials, TourState *states_w) {
     // the position arrays and the table of the dealing are kernel arguments of their own, restrict-qualified: the row operands
     // and a wave's descriptor are wave-uniform loads, and the compiler only issues them as scalar loads (s_load: no
     // vector-memory slot, no VGPRs) when it can prove that the kernel's own stores (the candidate slot, `open`) never touch them
@@ -294,15 +307,16 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
     unsigned long long stamp_hits = 0, stamp_hit_cycles = 0, stamp_first = 0;
 #endif
     const int tour = blockIdx.z;
-    const int n = a.n, tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     // ---- this wave's share (exh_deal, evaluated by the host when the handle was created) and the tour's `done`: every wave of
     // the launch is here at once and nothing hides the latency, so the two loads travel together -- one wait, then the branch
     const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kScanThreads / 64) + (tid >> 6));
-    int done = a.states[tour].done;
+    int done = states[tour].done;
     ExhDeal dl = deal[gw];
-    // (both loaded before the branch; and the kernel arguments of the rows fetched by the entry's one batch of loads, not by
-    // batches of their own further down.  The pointers only as a comparison: handed to the statement themselves they would count
-    // as escaped, and the loads through them would no longer be scalar loads.)
+    // (both loaded before the branch; and the kernel arguments that are not preloaded fetched by the entry's one batch of loads,
+    // not by a batch of their own behind the last row.  The arrays the kernel reads only as a comparison: handed to the
+    // statement themselves they would count as escaped, and the loads through them would no longer be scalar loads; the two
+    // pointers it only stores through as they are.)
 #ifdef TSP_STAMPS
     // (in the stamped build the compiler fetches `done` with a vector load: back to scalar registers for the statement below)
     done = __builtin_amdgcn_readfirstlane(done);
@@ -311,7 +325,8 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
                            (unsigned)__builtin_amdgcn_readfirstlane((int)(u64)dl.count));
 #endif
     const int args_null = (int)(rec_all == nullptr) | (int)(pid_all == nullptr) | (int)(wpos_all == nullptr);
-    asm volatile("" : "+s"(done), "+s"(dl.strip), "+s"(dl.row), "+s"(dl.count) : "s"(n), "s"(args_null), "s"(a.partial_per_tour));
+    asm volatile("" : "+s"(done), "+s"(dl.strip), "+s"(dl.row), "+s"(dl.count)
+                 : "s"(n), "s"(args_null), "s"(partial_per_tour), "s"(partials), "s"(states_w));
     if (done) return;
     const size_t pbase = (size_t)tour * (n + kExhPad);
     const ExhRec *__restrict__ rec = rec_all + pbase;
@@ -461,14 +476,14 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const StepArgs a, const
     // The winner's positions travel with the candidate (sweep_decide reads them in the same round and never asks pos): stored by
     // the lane that owns the winning key.  A key names one pair of positions, so two owners (strip 0 overlaps strip 1) store
     // the same words.
-    if (mine == key && key != kNoKey) wpos_all[(size_t)tour * a.partial_per_tour + blockIdx.x] = wp;
+    if (mine == key && key != kNoKey) wpos_all[(size_t)tour * (size_t)partial_per_tour + blockIdx.x] = wp;
     // The launch ends here: the block's candidate, empty or not, as plain stores -- its readers (every block of the next
     // k_move_pos, or k_exh_close) are later launches.  `open` tells them so; nothing in this launch reads it.
     if (tid == 0) {
         Partial p;
         p.delta = d; p.i = key_i(key); p.j = key_j(key);
-        a.partials[(size_t)tour * a.partial_per_tour + blockIdx.x] = p;
-        if (blockIdx.x == 0) a.states[tour].open = 1;
+        partials[(size_t)tour * (size_t)partial_per_tour + blockIdx.x] = p;
+        if (blockIdx.x == 0) states_w[tour].open = 1;
 #ifdef TSP_STAMPS
         atomicMax(&g_exh_t[4], wall_clock64());
 #endif

@@ -384,19 +384,18 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
             ExhRec *rec_new = t->d_prec[t->exh_buf];
             const dim3 gm((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B);
             if (rec_old)
-                hipLaunchKernelGGL((k_move_pos<WT, INT, true>), gm, dim3(kScanThreads), 0, s, t->inst->d_coord, t->d_order, t->d_pos,
-                                   t->d_order2, t->d_pos2, cur, t->d_state, t->d_partial, t->d_exh_wpos, t->partial_per_tour,
-                                   t->exh_blocks, rec_old, rec_new, t->d_pid, t->n);
+                hipLaunchKernelGGL((k_move_pos<WT, INT, true>), gm, dim3(kScanThreads), 0, s, cur, t->d_partial, t->d_exh_wpos, rec_old,
+                                   t->partial_per_tour, t->exh_blocks, t->n, rec_new, t->d_pid, t->d_state, t->inst->d_coord,
+                                   t->d_order, t->d_pos, t->d_order2, t->d_pos2);
             else
-                hipLaunchKernelGGL((k_move_pos<WT, INT, false>), gm, dim3(kScanThreads), 0, s, t->inst->d_coord, t->d_order, t->d_pos,
-                                   t->d_order2, t->d_pos2, cur, t->d_state, t->d_partial, t->d_exh_wpos, t->partial_per_tour,
-                                   t->exh_blocks, rec_old, rec_new, t->d_pid, t->n);
+                hipLaunchKernelGGL((k_move_pos<WT, INT, false>), gm, dim3(kScanThreads), 0, s, cur, t->d_partial, t->d_exh_wpos, rec_old,
+                                   t->partial_per_tour, t->exh_blocks, t->n, rec_new, t->d_pid, t->d_state, t->inst->d_coord,
+                                   t->d_order, t->d_pos, t->d_order2, t->d_pos2);
             t->exh_hot = true;   // (tsp_grid_run takes it back when the call returns)
-            a.states = t->d_state;
-            a.flat_slots = t->exh_blocks;
             const dim3 g(t->exh_blocks, 1, t->B);
-            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, a, rec_new, t->d_pid, t->d_exh_deal,
-                               t->d_exh_wpos);
+            hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, (const TourState *)t->d_state,
+                               (const ExhRec *)rec_new, t->n, (const ExhDeal *)t->d_exh_deal, (const int *)t->d_pid, t->d_exh_wpos,
+                               (int)t->partial_per_tour, t->d_partial, t->d_state);
             return TSP_OK;
         }
     }
