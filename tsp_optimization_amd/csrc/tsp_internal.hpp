@@ -13,6 +13,7 @@
 #include "../../include/tsp_hip.h"
 #include "tsp_dist.hpp"
 #include "exh_arith.hpp"
+#include "exh_decide.hpp"
 
 namespace tsp {
 
@@ -177,11 +178,10 @@ struct tsp_dev_tours {
     tsp::ExhRec *d_prec[2] = {nullptr, nullptr};
     int exh_buf = 0;
     bool exh_hot = false;
-    int *d_pid = nullptr;            // ... and the node ids by position, for k_exh
     int exh_share[4] = {0, 0, 0, 0};   // k_exh: rows per wave of each part of the grid (0: equal shares)
     int exh_gens = 0;                  // ... parts (= workgroups per CU)
     tsp::ExhDeal *d_exh_deal = nullptr;   // k_exh: where each wave of a tour's grid starts and how many row units it has (exh_deal)
-    int2 *d_exh_wpos = nullptr;           // k_exh: (pos[i], pos[j]) of each block's candidate, parallel to d_partial
+    tsp::ExhCand *d_exh_cand = nullptr;   // k_exh: each workgroup's candidate by tour position (exh_decide.hpp), B x exh_blocks
     int exh_lds = 0;                 // k_exh: dynamic LDS a workgroup asks for (unused; it pins the number of workgroups per CU)
     int exh_blocks = 0;              // k_exh: workgroups per tour (0: the tiled k_step executes the exhaustive sweep)
     int *d_pairtab = nullptr;        // group pairs per cluster of k_sweep blocks (host-built), or nullptr

@@ -26,22 +26,29 @@
 // forms give the same integers.
 //
 // Layout.  k_move_pos (one thread per position) DECIDES the previous sweep's move -- every block for itself, from the
-// candidates k_exh left and the positions of their pairs beside them (sweep_load + sweep_reduce, two_opt_step.hpp: pos is not
-// read; the candidates are asked for together with the control block, one wait) --, carries it out of place (as k_move_recs
-// does) and writes, in position order and padded: rec[p] = the record of u_p (exh_arith.hpp: -2x, -2y and the norm of its
-// coordinates relative to node 0, e[p - 1], and u_p itself; position n repeats position 0; further pads lie far outside the
-// instance and carry the id -1), pid[p] = u_p once more, as the array k_exh reads its pairs' ids from.
+// candidates k_exh left, which name their pairs by tour POSITION (exh_decide below, the rule in exh_decide.hpp: pos is not read, a
+// node id only when two different pairs share the minimal delta; the candidates are asked for together with the control block,
+// one wait) --, carries it out of place (as k_move_recs does) and writes, in position order and padded: rec[p] = the record of
+// u_p (exh_arith.hpp: -2x, -2y and the norm of its coordinates relative to node 0, e[p - 1], and u_p itself; position n repeats
+// position 0; further pads lie far outside the instance and carry the id -1).  There is no array of ids by position beside them.
 // Records by permutation.  A 2-opt move only permutes positions: but for the two cut points, the record of the new position k is
 // bit for bit an old record and its e is an old e (exh_perm, exh_arith.hpp; tests/test_cpu_exh_permute.py).  A tour has two
 // record buffers; k_move_pos<HOT> reads one and writes the other, the k_exh behind it reads what it wrote, the host flips
-// them with the pair of launches.  The chain of a hot launch is {control block, candidates} -> arg-min -> old records ->
-// stores (their addresses come from preloaded kernel arguments): order, pos and coord are not read (order and pos are still written, for every other reader).  The
+// them with the pair of launches.  The chain of a hot launch is {control block, candidates} -> arg-min -> {old records, the ids
+// at the pair's two positions} -> stores (their addresses come from preloaded kernel arguments): the pair is decided by position
+// and its orientation -- pa is the position of the smaller id -- is not known when the records are asked for, so a thread
+// evaluates exh_perm for both orientations, asks for the records of both and the two ids in one round, and keeps one behind the
+// single wait.  order, pos and coord are not read (order and pos are still written, for every other reader).  The
 // first sweep of a run call is cold (built from order and coord): only inside a run call does the host know that the old buffer
 // describes the tour (tsp_dev_tours::exh_hot).
-// Hand-off.  k_exh ends at its block's candidate and, from the lane that owns the winning key, (pos[i], pos[j]) of that pair in
-// an array parallel to the candidates: no counter, no last block.  (Measured and not kept: the ids of a lane's pair taken from
-// the records and kept in registers, so that k_exh ends without the loads of pid[bp] and pid[bq] -- four more VGPRs and their
-// moves at every strip start cost more than the round trip behind the last row saves: -1.5 %)
+// Hand-off.  k_exh ends at its block's candidate {delta, p, q}, p < q the POSITIONS of the pair, one 16-byte store: no counter,
+// no last block, and no node id -- behind a wave's last row come one wave_min, a ballot, one barrier and one thread's fold of the
+// block's four waves.  The ids are needed for the tie-break among different pairs at the minimal delta (rare: loaded from the
+// records inside that branch, in a lane's bookkeeping, in the wave, in the block and in k_move_pos alike) and for the move's
+// orientation, which k_move_pos settles in the round of loads it waits for anyway: +3.2 % on bench.py, DESIGN 4.9.  (Measured
+// and not kept: the ids of a lane's pair taken from the records and kept in registers -- four more VGPRs and their moves at every
+// strip start: -1.5 %; one candidate per WAVE, 4 096 of them and no barrier in k_exh -- k_exh as short as with one per block,
+// k_move_pos 0.3 us longer with sixteen candidates per thread instead of four: +0.4 to +1.0 % only)
 // No word is read and written by different blocks
 // of one launch: a tour has two control blocks, k_move_pos reads slot s and its block 0 writes the advanced block to slot
 // s ^ 1; k_exh reads `done` there and one thread of it sets `open` there ("candidates written, not decided"), which nobody
@@ -75,6 +82,7 @@
 #pragma once
 #include "two_opt_step.hpp"
 #include "exh_arith.hpp"
+#include "exh_decide.hpp"
 
 #pragma clang fp contract(off)
 
@@ -82,7 +90,7 @@ namespace tsp {
 
 #ifdef TSP_STAMPS
 // diagnostic build: per wave {100 MHz wall clock at start, at the end of its rows, shader cycles in between, 0}; [4] last
-// block's candidate stored in g_exh_t (tools/diag_exh.py reads them).  Plain stores to slots of their own: 4 096
+// wave's candidate stored in g_exh_t (tools/diag_exh.py reads them).  Plain stores to slots of their own: 4 096
 // atomics on one word at the start of a kernel would be the thing measured.
 __device__ unsigned long long g_exh_w[8192 * 4];
 __device__ unsigned long long g_exh_t[8];
@@ -150,8 +158,105 @@ __device__ __forceinline__ void exh_dist_row(const double (&cx)[RJ], const doubl
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// ---- the decision of a sweep from the candidates a FINISHED k_exh has left (exh_decide.hpp has the rule) -------------------------
+// One candidate per workgroup of k_exh: kExhCandPU per thread and round, and at most two rounds (k_exh's grid is capped at 2 048
+// workgroups of four waves).  The candidates' addresses depend on the thread alone, so a caller with loads of its own to wait for
+// (k_move_pos: the control block) issues exh_cand_load first and lets both travel together.
+constexpr int kExhCandPU = 4;   // 1 024 candidates = 4 per thread: one round
+constexpr int kExhMaxCand = 2 * kExhCandPU * kScanThreads;
+struct ExhCandLoads { ExhCand c[kExhCandPU]; };
+
+// one round of a thread's loads: slots s0, s0 + kScanThreads, ...  Every load is issued, none under a condition of its own (the
+// compiler waits for a load inside a branch at the branch's end: a round trip per load instead of one for all): a slot past the end reads
+// the last one and is emptied by exh_cand_settle, behind the wait.  nslots >= 1.
+__device__ __forceinline__ ExhCandLoads exh_cand_load(const ExhCand *__restrict__ cand, int nslots, int s0) {
+    ExhCandLoads l;
+#pragma unroll
+    for (int k = 0; k < kExhCandPU; ++k) l.c[k] = cand[min(s0 + k * kScanThreads, nslots - 1)];
+    return l;
+}
+__device__ __forceinline__ void exh_cand_settle(ExhCandLoads &l, int nslots, int s0) {
+#pragma unroll
+    for (int k = 0; k < kExhCandPU; ++k)
+        if (s0 + k * kScanThreads >= nslots) l.c[k].p = -1;
+}
+
+// keeps the loads of a round where they were issued: to be called behind the caller's own loads and a scheduling barrier,
+// before the first use of any of them
+__device__ __forceinline__ void exh_cand_pin(const ExhCandLoads &l) {
+#pragma unroll
+    for (int k = 0; k < kExhCandPU; ++k) asm volatile("" : : "v"(l.c[k].delta), "v"(l.c[k].p), "v"(l.c[k].q));
+}
+
+// Block-wide (kScanThreads threads), for every block that wants the answer: the pair the sweep chose, by position (p < q), or
+// found == 0 at the local optimum.  `first`: the round exh_cand_load(cand, nslots, threadIdx.x) fetched; the second round, where
+// there is one, is issued here before the first fold.  id_at(position) is asked only when two different pairs share the minimal
+// delta.  s_d, s_k: >= kScanThreads / 64 entries each.
+struct ExhPair { int found, p, q; };
+template <class IdAt>
+__device__ __forceinline__ ExhPair exh_decide(const ExhCandLoads &first, const ExhCand *__restrict__ cand, int nslots, IdAt id_at,
+                                              double *s_d, u64 *s_k) {
+    __shared__ u64 s_pair;
+    const bool two = nslots > kExhCandPU * kScanThreads;   // (block-uniform)
+    const int tid = threadIdx.x;
+    ExhCandLoads one = first, more;
+    if (two) more = exh_cand_load(cand, nslots, tid + kExhCandPU * kScanThreads);
+    exh_cand_settle(one, nslots, tid);
+    ExhBest b;
+#pragma unroll
+    for (int k = 0; k < kExhCandPU; ++k) exh_fold(b, one.c[k]);
+    if (two) {
+        exh_cand_settle(more, nslots, tid + kExhCandPU * kScanThreads);
+#pragma unroll
+        for (int k = 0; k < kExhCandPU; ++k) exh_fold(b, more.c[k]);
+    }
+    // The block's arg-min of (delta, position key) and the OR of exh_ambiguous in ONE exchange through LDS: a wave hands on its
+    // arg-min and whether one of its lanes is ambiguous against THAT -- which is the lane's word against the block's arg-min
+    // wherever the wave's delta is the block's, and is not looked at elsewhere; a wave whose arg-min is another pair at the
+    // block's delta is ambiguous by itself.  (block_argmin of two_opt_common.hpp with a third word: no barrier of its own.)
+    __shared__ int s_amb[kScanThreads / 64];
+    double d = (double)b.delta;
+    u64 key = b.key;
+    wave_argmin<true>(d, key);
+    const bool wave_amb = __any(exh_ambiguous(b, (int)d, key));
+    __syncthreads();
+    if ((tid & 63) == 0) { s_d[tid >> 6] = d; s_k[tid >> 6] = key; s_amb[tid >> 6] = wave_amb; }
+    __syncthreads();
+    d = s_d[0]; key = s_k[0];
+    for (int w = 1; w < kScanThreads / 64; ++w)
+        if (better(s_d[w], s_k[w], d, key)) { d = s_d[w]; key = s_k[w]; }
+    if (key == kNoKey || !(d < 0)) return {0, -1, -1};   // (block-uniform)
+    const int delta = (int)d;
+    bool ambiguous = false;
+    for (int w = 0; w < kScanThreads / 64; ++w)
+        ambiguous = ambiguous || (s_k[w] != kNoKey && s_d[w] == d && (s_amb[w] != 0 || s_k[w] != key));
+    if (ambiguous) {   // (block-uniform)
+        ExhIdBest ib;
+#pragma unroll
+        for (int k = 0; k < kExhCandPU; ++k) exh_fold_ids(ib, one.c[k], delta, id_at);
+        if (two) {
+#pragma unroll
+            for (int k = 0; k < kExhCandPU; ++k) exh_fold_ids(ib, more.c[k], delta, id_at);
+        }
+        u64 idkey = ib.idkey;
+        double unused = 0.0;
+        block_argmin<false>(unused, idkey, s_d, s_k);
+        if (ib.idkey == idkey) s_pair = ib.poskey;   // an id key names one pair: every owner holds the same positions
+        __syncthreads();
+        key = s_pair;
+    }
+    return {1, exh_key_hi(key), exh_key_lo(key)};
+}
+
+// the decided and oriented pair as the move the control block counts (sweep_count)
+__device__ __forceinline__ SweepDecision exh_decision(const ExhMove &m) {
+    SweepDecision d;
+    d.found = 1; d.pa = m.pa; d.pb = m.pb; d.L = m.L;
+    return d;
+}
+
 // (1) the move: the open sweep's, decided here by every block for itself, or a pending one (decided by k_exh_close); (2) that move,
-// out of place; (3) the tour AFTER it in position order: records (ids in them) and ids.  Reads the control block `states`, which no block of
+// out of place; (3) the tour AFTER it in position order: records, ids in them.  Reads the control block `states`, which no block of
 // this launch writes; block 0 writes the advanced one to `states_next` (the tour's other slot), which no block of this launch reads.
 // HOT: `rec_old` holds the records of the tour BEFORE the move (the previous sweep's, written by the previous k_move_pos of the
 // same run call: the host knows, tsp_dev_tours::exh_hot) and the new ones are a permutation of them (exh_perm, exh_arith.hpp):
@@ -162,10 +267,9 @@ __device__ __forceinline__ void exh_dist_row(const double (&cx)[RJ], const doubl
 // SGPRs when it starts (kernel-argument preload, csrc/Makefile), so {control block, candidates} are asked for with no wait in
 // front of them; the rest is fetched by the entry's one batch of scalar loads.
 template <int WT, bool INT, bool HOT>
-__global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__restrict__ states, const Partial *__restrict__ partials,
-                                                           const int2 *__restrict__ wpos, const ExhRec *__restrict__ rec_old,
-                                                           size_t partial_per_tour, int flat_slots, int n, ExhRec *__restrict__ rec,
-                                                           int *__restrict__ pid, TourState *__restrict__ states_next,
+__global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__restrict__ states, const ExhCand *__restrict__ cands,
+                                                           const ExhRec *__restrict__ rec_old, int cand_per_tour, int n,
+                                                           ExhRec *__restrict__ rec, TourState *__restrict__ states_next,
                                                            const double2 *__restrict__ coord, int *orders, int *poss, int *orders2,
                                                            int *poss2) {
     static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only (integer costs: the tour cost needs no staging)");
@@ -176,9 +280,8 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
     const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
     // The candidates' addresses do not depend on the control block: both are asked for before either is used -- one wait.
     // (A finished tour, or one without an open sweep, has loaded candidates it does not look at.)
-    const Partial *part = partials + (size_t)tour * partial_per_tour;
-    const int2 *wp = wpos + (size_t)tour * partial_per_tour;
-    const SweepLoads cand = sweep_load<true>(part, wp, flat_slots, threadIdx.x);
+    const ExhCand *cand = cands + (size_t)tour * cand_per_tour;
+    const ExhCandLoads first = exh_cand_load(cand, cand_per_tour, threadIdx.x);
     int done = st->done, is_open = st->open, parity = st->parity, pending = st->pending, mv_pa = st->mv_pa, mv_pb = st->mv_pb;
     __builtin_amdgcn_sched_barrier(0);
     // (and every kernel argument fetched by the entry's one batch of loads, not by batches of their own further down; the
@@ -186,18 +289,21 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
     const int args_null = (int)(coord == nullptr) | (int)(orders == nullptr) | (int)(poss == nullptr) | (int)(orders2 == nullptr) |
                           (int)(poss2 == nullptr) | (int)(states_next == nullptr) | (int)(rec_old == nullptr) | (int)(rec == nullptr);
     asm volatile("" : "+s"(done), "+s"(is_open), "+s"(parity), "+s"(pending), "+s"(mv_pa), "+s"(mv_pb) : "s"(n), "s"(args_null));
-    sweep_pin(cand);
+    exh_cand_pin(first);
     if (done) {   // a finished tour stays finished in both slots
         if (writer) states_next[tour] = *st;
         return;
     }
     const size_t base = (size_t)tour * n, pbase = (size_t)tour * (n + kExhPad);
     MoveView mv = move_view(parity, pending, mv_pa, mv_pb, orders + base, poss + base, orders2 + base, poss2 + base, n);
+    const ExhRec *__restrict__ old = rec_old + pbase;   // (HOT only)
     const bool open = is_open != 0;   // (then nothing is pending: mv.L == 0)
     SweepDecision dec;
+    ExhPair pr = {0, -1, -1};
     if (open) {
-        dec = sweep_reduce<true>(cand, part, wp, flat_slots, mv.pos, n, s_d, s_k);   // the winner's positions came with its candidate: pos is not read
-        if (!dec.found) {   // the local optimum: block 0 recomputes the cost (tabusearch.c:168-172), nobody has records to build
+        // the pair by position; its ids only if two different pairs share the minimal delta (from the old records, or through order)
+        pr = exh_decide(first, cand, cand_per_tour, [&](int p) { if constexpr (HOT) return old[p].id; else return mv.order[p]; }, s_d, s_k);
+        if (!pr.found) {   // the local optimum: block 0 recomputes the cost (tabusearch.c:168-172), nobody has records to build
             if (blockIdx.x != 0) return;
             const double cost = tour_cost_block<WT, INT>(coord, mv.order, mv.pos, n, s_d, nullptr);
             if (writer) {
@@ -208,25 +314,41 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
             }
             return;
         }
-        mv.L = dec.L; mv.pa1 = dec.pa + 1 == n ? 0 : dec.pa + 1;
     }
     const int k = blockIdx.x * kScanThreads + threadIdx.x;
     if (k >= n + kExhPad) return;
     int u;
     ExhRec r;
     if constexpr (HOT) {
-        // old records a and b and old record n's eprev (the closing edge): three loads whose addresses the move decides, in
-        // flight together; no thread, the two at the cut points included, waits a second time
-        const ExhRec *__restrict__ old = rec_old + pbase;
-        const ExhPerm pm = exh_perm(k, n, mv.pa1, mv.L);
-        const ExhRec ra = old[pm.a], rb = old[pm.b];
+        // The pair is known, its orientation is not: the position of the smaller id is pa.  Both orientations are evaluated and
+        // everything either of them needs is asked for in ONE round -- old records a and b of both, old record n's eprev (the
+        // closing edge), the ids at p and q -- so no thread, the two at the cut points included, waits a second time.  (A pending
+        // move is oriented already: the same move twice.)
+        ExhMove m1 = {mv_pa, mv_pb, mv.pa1, mv.L}, m2 = m1;
+        if (open) { m1 = exh_orient(pr.p, pr.q, n, true); m2 = exh_orient(pr.p, pr.q, n, false); }
+        const ExhPerm pm1 = exh_perm(k, n, m1.pa1, m1.L), pm2 = exh_perm(k, n, m2.pa1, m2.L);
+        const ExhRec ra1 = old[pm1.a], rb1 = old[pm1.b], ra2 = old[pm2.a], rb2 = old[pm2.b];
         const int wrap = old[n].eprev;
+        int idp = 0, idq = 1;
+        if (open) { idp = old[pr.p].id; idq = old[pr.q].id; }
         __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" : : "v"(ra.m2x), "v"(ra.m2y), "v"(ra.nrm), "v"(ra.eprev), "v"(rb.m2x), "v"(rb.m2y), "v"(rb.nrm),
-                     "v"(rb.eprev), "v"(rb.id), "v"(wrap));
-        r = exh_perm_rec<exh_mode<WT>()>(pm, ra, rb, wrap, [](double v) { return __builtin_amdgcn_sqrt(v); });
+        asm volatile("" : : "v"(ra1.m2x), "v"(ra1.m2y), "v"(ra1.nrm), "v"(ra1.eprev), "v"(rb1.m2x), "v"(rb1.m2y), "v"(rb1.nrm),
+                     "v"(rb1.eprev), "v"(rb1.id), "v"(wrap));
+        asm volatile("" : : "v"(ra2.m2x), "v"(ra2.m2y), "v"(ra2.nrm), "v"(ra2.eprev), "v"(rb2.m2x), "v"(rb2.m2y), "v"(rb2.nrm),
+                     "v"(rb2.eprev), "v"(rb2.id), "v"(idp), "v"(idq));
+        const bool p_first = idp < idq;
+        const ExhMove m = p_first ? m1 : m2;
+        r = exh_perm_rec<exh_mode<WT>()>(p_first ? pm1 : pm2, p_first ? ra1 : ra2, p_first ? rb1 : rb2, wrap,
+                                         [](double v) { return __builtin_amdgcn_sqrt(v); });
         u = r.id;
+        mv.L = m.L; mv.pa1 = m.pa1;
+        if (open) dec = exh_decision(m);
     } else {
+        if (open) {   // the orientation by two dependent loads through order (nothing is pending: order is the tour as it stands)
+            const ExhMove m = exh_orient(pr.p, pr.q, n, mv.order[pr.p] < mv.order[pr.q]);
+            mv.L = m.L; mv.pa1 = m.pa1;
+            dec = exh_decision(m);
+        }
         // every load of the current copy (which this kernel never writes) comes before the first store
         u = k < n ? mv.node_at(k) : (k == n ? mv.node_at(0) : -1);
         const int v = k >= 1 && k <= n ? mv.node_at(k - 1) : -1;   // the position before
@@ -246,7 +368,6 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
         p_new[u] = k;
     }
     rec[pbase + k] = r;
-    pid[pbase + k] = u;
     if (writer) {   // the next control block: the sweep counted, the move carried out (the other copy is the current one now)
         // (the writer is thread 0 of block 0: k = 0, never past the early return above)
         TourState z = *st;
@@ -259,12 +380,12 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
 
 // Before the host looks at a control block (a poll, the end of a run): an open sweep becomes a decided one -- the counters, and
 // either a pending move, which the next k_move_pos or the flush carries out, or the finished tour's recomputed cost.  One block
-// per tour, so it updates the control block it reads (behind the barriers of the decision).
+// per tour, so it updates the control block it reads (behind the barriers of the decision).  Ids and orientation by dependent
+// loads through order: one launch in many.
 template <int WT, bool INT>
 __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__restrict__ coord, const int *orders, const int *poss,
                                                             const int *orders2, const int *poss2, TourState *states,
-                                                            const Partial *__restrict__ partials, const int2 *__restrict__ wpos,
-                                                            size_t partial_per_tour, int flat_slots, int n) {
+                                                            const ExhCand *__restrict__ cands, int cand_per_tour, int n) {
     static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only");
     __shared__ double s_d[kScanThreads / 64];
     __shared__ u64 s_k[kScanThreads / 64];
@@ -274,11 +395,13 @@ __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__res
     const size_t base = (size_t)tour * n;
     const bool second = st->parity != 0;
     const int *order = (second ? orders2 : orders) + base, *pos = (second ? poss2 : poss) + base;
-    const Partial *part = partials + (size_t)tour * partial_per_tour;
-    const int2 *wp = wpos + (size_t)tour * partial_per_tour;
-    const SweepDecision dec = sweep_reduce<true>(sweep_load<true>(part, wp, flat_slots, threadIdx.x), part, wp, flat_slots, pos, n, s_d, s_k);
+    const ExhCand *cand = cands + (size_t)tour * cand_per_tour;
+    const ExhPair pr = exh_decide(exh_cand_load(cand, cand_per_tour, threadIdx.x), cand, cand_per_tour,
+                                  [&](int p) { return order[p]; }, s_d, s_k);
+    SweepDecision dec;
     double cost = 0.0;
-    if (!dec.found) cost = tour_cost_block<WT, INT>(coord, order, pos, n, s_d, nullptr);
+    if (pr.found) dec = exh_decision(exh_orient(pr.p, pr.q, n, order[pr.p] < order[pr.q]));
+    else cost = tour_cost_block<WT, INT>(coord, order, pos, n, s_d, nullptr);
     if (threadIdx.x == 0) {
         TourState z = *st;
         sweep_count(z, dec, n, cost);
@@ -288,15 +411,18 @@ __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__res
 }
 
 // RJ = kExhRJ columns per lane, four workgroups of four waves per CU (the host pins that with its LDS request).
-// The order of the parameters: `states` (the read-only view: `done`), the records, n, the table of the dealing, the ids, the
-// positions' array and the stride of the candidates are 14 dwords, which a wave finds in its SGPRs when it starts
-// (kernel-argument preload, csrc/Makefile: a struct by value ends the preload, so there is none), and the loads of `done` and of
-// the descriptor are issued with no wait in front of them; the two pointers of the epilogue follow.
+// The order of the parameters: `states` (the read-only view: `done`), the records, n, the stride of the candidates, the table of
+// the dealing, the candidates and the control block to set `open` in are 12 dwords, all within the 14 which a wave finds in its
+// SGPRs when it starts (kernel-argument preload, csrc/Makefile: a struct by value ends the preload, so there is none), and the
+// loads of `done` and of the descriptor are issued with no wait in front of them.
+// The tail: the wave's candidate by position -- one wave_min over the lanes' best deltas, a ballot of the lanes that hold it;
+// one owner, or owners that all hold the same pair: no id is loaded (owners with different pairs, rare, load theirs inside that
+// branch) --, then the block's from its four waves' behind the kernel's one barrier, one 16-byte store.  Ties between blocks and
+// the orientation of the move are k_move_pos's (exh_decide.hpp), which holds the records with the ids in them.
 template <int WT, bool INT, int RJ>
 __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const TourState *__restrict__ states, const ExhRec *__restrict__ rec_all, int n,
-                                                      const ExhDeal *__restrict__ deal, const int *__restrict__ pid_all,
-                                                      int2 *__restrict__ wpos_all, int partial_per_tour,
-                                                      Partial *__restrict__ partials, TourState *states_w) {
+                                                      int cand_per_tour, const ExhDeal *__restrict__ deal,
+                                                      ExhCand *__restrict__ cand_all, TourState *states_w) {
     // the position arrays and the table of the dealing are kernel arguments of their own, restrict-qualified: the row operands
     // and a wave's descriptor are wave-uniform loads, and the compiler only issues them as scalar loads (s_load: no
     // vector-memory slot, no VGPRs) when it can prove that the kernel's own stores (the candidate slot, `open`) never touch them
@@ -313,9 +439,9 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const TourState *__rest
     const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kScanThreads / 64) + (tid >> 6));
     int done = states[tour].done;
     ExhDeal dl = deal[gw];
-    // (both loaded before the branch; and the kernel arguments that are not preloaded fetched by the entry's one batch of loads,
-    // not by a batch of their own behind the last row.  The arrays the kernel reads only as a comparison: handed to the
-    // statement themselves they would count as escaped, and the loads through them would no longer be scalar loads; the two
+    // (both loaded before the branch; and, on firmware that does not preload, every kernel argument fetched by the entry's one
+    // batch of loads, not by a batch of their own behind the last row.  The array the kernel reads only as a comparison: handed to
+    // the statement itself it would count as escaped, and the loads through it would no longer be scalar loads; the two
     // pointers it only stores through as they are.)
 #ifdef TSP_STAMPS
     // (in the stamped build the compiler fetches `done` with a vector load: back to scalar registers for the statement below)
@@ -324,27 +450,29 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const TourState *__rest
     dl.count = (long long)(((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)((u64)dl.count >> 32)) << 32) |
                            (unsigned)__builtin_amdgcn_readfirstlane((int)(u64)dl.count));
 #endif
-    const int args_null = (int)(rec_all == nullptr) | (int)(pid_all == nullptr) | (int)(wpos_all == nullptr);
+    const int args_null = (int)(rec_all == nullptr);
     asm volatile("" : "+s"(done), "+s"(dl.strip), "+s"(dl.row), "+s"(dl.count)
-                 : "s"(n), "s"(args_null), "s"(partial_per_tour), "s"(partials), "s"(states_w));
+                 : "s"(n), "s"(args_null), "s"(cand_per_tour), "s"(cand_all), "s"(states_w));
     if (done) return;
     const size_t pbase = (size_t)tour * (n + kExhPad);
     const ExhRec *__restrict__ rec = rec_all + pbase;
-    const int *__restrict__ pid = pid_all + pbase;
 
     int bd = -1, bp = -1, bq = -1;     // integer costs: delta < 0  <=>  delta <= -1; (bd, no pair) loses every tie
     int wbd = -1;                      // wave-uniform: the lowest delta any lane of this wave has seen
 
-    // exact bookkeeping for a pair that reached the wave's best: delta, then -- on a tie only -- the reference's tie-break on
-    // node ids (two dependent global loads: not on the path of a strict improvement)
+    // the reference's scan-order key of the pair at positions (pp, qq): its node ids, from the records
+    auto id_key = [&](int pp, int qq) {
+        const int i = rec[pp].id, j = rec[qq].id;
+        return make_key(min(i, j), max(i, j));
+    };
+    // exact bookkeeping for a pair that reached the wave's best: delta, then -- on a tie only -- first the positions (the same
+    // pair once more, from a range that runs from strip 0 into strip 1: skipped), then the reference's tie-break on node ids
+    // (dependent global loads: not on the path of a strict improvement)
     auto consider = [&](int sum, int erow, int pp, int qq, bool valid) {
         const int d = sum - erow;
         if (valid && d <= bd) {
             bool take = d < bd || bp < 0;
-            if (!take) {
-                const int i1 = pid[pp], j1 = pid[qq], i0 = pid[bp], j0 = pid[bq];
-                take = make_key(min(i1, j1), max(i1, j1)) < make_key(min(i0, j0), max(i0, j0));
-            }
+            if (!take && (pp != bp || qq != bq)) take = id_key(pp, qq) < id_key(bp, bq);
             if (take) { bd = d; bp = pp; bq = qq; }
         }
     };
@@ -446,7 +574,7 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const TourState *__rest
         pa = 0;
     }
 
-    // ---- the wave's and the block's arg-min (delta, (i, j)); the tour's is taken by the next launch -----------------------
+    // ---- the wave's candidate, then the block's: the arg-min of (delta, (i, j)) by position; the tour's is taken by the next launch
 #ifdef TSP_STAMPS
     if (lane == 0 && tour == 0) {
         const int w = (int)blockIdx.x * (kScanThreads / 64) + (tid >> 6);
@@ -456,33 +584,46 @@ __global__ __launch_bounds__(kScanThreads, 1) void k_exh(const TourState *__rest
             g_exh_w[4 * w + 2] = (clock64() - stamp_c0) | ((unsigned long long)hwid << 32); g_exh_w[4 * w + 3] = 1 | (stamp_hits << 8) | ((unsigned long long)(xcc & 0xf) << 60) | ((stamp_hit_cycles & 0xfffffffffull) << 24); }
     }
 #endif
-    // only the lanes that hold the wave's lowest delta need their pair's node ids (usually one lane: one pair of loads)
-    double d = 0.0;
-    u64 key = kNoKey;
-    int2 wp = make_int2(0, 0);   // (pos[i], pos[j]) of the lane's pair, i < j the node ids of the key
-    {
-        const int wmin = (int)(unsigned)(wave_min_u64((u64)((unsigned)bd ^ 0x80000000u)) ^ 0x80000000u);
-        if (bp >= 0 && bd == wmin) {
-            const int i = pid[bp], j = pid[bq];
-            d = (double)bd;
-            key = make_key(min(i, j), max(i, j));
-            wp = i < j ? make_int2(bp, bq) : make_int2(bq, bp);
+    const int wmin = (int)(unsigned)(wave_min_u64((u64)((unsigned)bd ^ 0x80000000u)) ^ 0x80000000u);
+    const bool owner = bp >= 0 && bd == wmin;
+    const u64 owners = __ballot(owner);
+    int cp = -1, cq = -1;
+    if (owners) {
+        const int first = __builtin_ctzll(owners);
+        cp = __builtin_amdgcn_readlane(bp, first); cq = __builtin_amdgcn_readlane(bq, first);
+        // owners with different pairs (rare): the reference's tie-break, the ids loaded and consumed inside this branch
+        if (__builtin_expect(__any(owner && (bp != cp || bq != cq)), 0)) {
+            u64 key = kNoKey;
+            if (owner) key = id_key(bp, bq);
+            const int src = __builtin_ctzll(__ballot(key == wave_min_u64(key)));
+            cp = __builtin_amdgcn_readlane(bp, src); cq = __builtin_amdgcn_readlane(bq, src);
         }
     }
-    const u64 mine = key;
-    __shared__ double s_d[kScanThreads / 64];
-    __shared__ u64 s_k[kScanThreads / 64];
-    block_argmin<true>(d, key, s_d, s_k);
-    // The winner's positions travel with the candidate (sweep_decide reads them in the same round and never asks pos): stored by
-    // the lane that owns the winning key.  A key names one pair of positions, so two owners (strip 0 overlaps strip 1) store
-    // the same words.
-    if (mine == key && key != kNoKey) wpos_all[(size_t)tour * (size_t)partial_per_tour + blockIdx.x] = wp;
-    // The launch ends here: the block's candidate, empty or not, as plain stores -- its readers (every block of the next
-    // k_move_pos, or k_exh_close) are later launches.  `open` tells them so; nothing in this launch reads it.
+    // The block's candidate: its waves' candidates meet in LDS behind the kernel's one barrier and one thread folds them by
+    // exh_decide.hpp's rule -- (delta, position key), and the ids of the pairs at the minimal delta only if two different pairs
+    // share it (rare: loaded and consumed inside that branch).
+    __shared__ int s_wd[kScanThreads / 64];
+    __shared__ u64 s_wk[kScanThreads / 64];
+    if (lane == 0) { s_wd[tid >> 6] = wmin; s_wk[tid >> 6] = exh_pair_key(cp, cq); }
+    __syncthreads();
+    // The launch ends here: the block's candidate, empty or not, as one plain 16-byte store -- its readers (every block of the
+    // next k_move_pos, or k_exh_close) are later launches.  `open` tells them so; nothing in this launch reads it.
     if (tid == 0) {
-        Partial p;
-        p.delta = d; p.i = key_i(key); p.j = key_j(key);
-        partials[(size_t)tour * (size_t)partial_per_tour + blockIdx.x] = p;
+        auto wave_cand = [&](int w) {
+            ExhCand c;
+            c.delta = s_wd[w]; c.p = s_wk[w] == kExhNoPair ? -1 : exh_key_hi(s_wk[w]); c.q = exh_key_lo(s_wk[w]); c.pad = 0;
+            return c;
+        };
+        ExhBest b;
+        for (int w = 0; w < kScanThreads / 64; ++w) exh_fold(b, wave_cand(w));
+        if (__builtin_expect(b.tie, 0)) {
+            ExhIdBest ib;
+            for (int w = 0; w < kScanThreads / 64; ++w) exh_fold_ids(ib, wave_cand(w), b.delta, [&](int p) { return rec[p].id; });
+            b.key = ib.poskey;
+        }
+        ExhCand c;
+        c.delta = b.delta; c.p = b.key == kExhNoPair ? -1 : exh_key_hi(b.key); c.q = exh_key_lo(b.key); c.pad = 0;
+        cand_all[(size_t)tour * (size_t)cand_per_tour + blockIdx.x] = c;
         if (blockIdx.x == 0) states_w[tour].open = 1;
 #ifdef TSP_STAMPS
         atomicMax(&g_exh_t[4], wall_clock64());

@@ -259,7 +259,10 @@ bool exh_run(const tsp_dev_tours *t, int mode, const tsp_dev_tabu *tabu) {
            (t->inst->wtype == WT_EUC_2D_ICOORD || t->inst->wtype == WT_CEIL_2D_ICOORD || t->inst->wtype == WT_ATT_ICOORD);
 }
 
-constexpr long long kTabuListMax = 16384;   // more non-zero stamps than this: the dense scan (k_step<TABU>)
+// candidates of one tour's exhaustive sweep: one per workgroup of k_exh's grid
+int exh_cands(const tsp_dev_tours *t) { return t->exh_blocks; }
+
+constexpr long long kTabuListMax = 16384;  // more non-zero stamps than this: the dense scan (k_step<TABU>)
 // Entries whose stamp has been cleared stay in the list until it is compacted, and every sweep of a run with a list passes over
 // them (CLUSTER engine: an entry per thread, the cluster waits for the slowest).  The list is compacted once this many entries
 // have been appended since the last time (2 048 until round 4: at tenure 200 three entries in four were dead ones).
@@ -334,8 +337,7 @@ void launch_exh_close(tsp_dev_tours *t) {
     TSP_DISPATCH_METRIC(t->inst->wtype, t->inst->integer_cost, {
         if constexpr (exh_metric<WTC>())
             hipLaunchKernelGGL((k_exh_close<WTC, INTC>), dim3(t->B), dim3(kScanThreads), 0, s, t->inst->d_coord, t->d_order, t->d_pos,
-                               t->d_order2, t->d_pos2, t->d_state, t->d_partial, t->d_exh_wpos, t->partial_per_tour, t->exh_blocks,
-                               t->n);
+                               t->d_order2, t->d_pos2, t->d_state, (const ExhCand *)t->d_exh_cand, exh_cands(t), t->n);
     });
 }
 
@@ -383,19 +385,17 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
             t->exh_buf ^= 1;
             ExhRec *rec_new = t->d_prec[t->exh_buf];
             const dim3 gm((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B);
+            const ExhCand *cands = t->d_exh_cand;
             if (rec_old)
-                hipLaunchKernelGGL((k_move_pos<WT, INT, true>), gm, dim3(kScanThreads), 0, s, cur, t->d_partial, t->d_exh_wpos, rec_old,
-                                   t->partial_per_tour, t->exh_blocks, t->n, rec_new, t->d_pid, t->d_state, t->inst->d_coord,
-                                   t->d_order, t->d_pos, t->d_order2, t->d_pos2);
+                hipLaunchKernelGGL((k_move_pos<WT, INT, true>), gm, dim3(kScanThreads), 0, s, cur, cands, rec_old, exh_cands(t), t->n,
+                                   rec_new, t->d_state, t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2);
             else
-                hipLaunchKernelGGL((k_move_pos<WT, INT, false>), gm, dim3(kScanThreads), 0, s, cur, t->d_partial, t->d_exh_wpos, rec_old,
-                                   t->partial_per_tour, t->exh_blocks, t->n, rec_new, t->d_pid, t->d_state, t->inst->d_coord,
-                                   t->d_order, t->d_pos, t->d_order2, t->d_pos2);
+                hipLaunchKernelGGL((k_move_pos<WT, INT, false>), gm, dim3(kScanThreads), 0, s, cur, cands, rec_old, exh_cands(t), t->n,
+                                   rec_new, t->d_state, t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2);
             t->exh_hot = true;   // (tsp_grid_run takes it back when the call returns)
             const dim3 g(t->exh_blocks, 1, t->B);
             hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, (const TourState *)t->d_state,
-                               (const ExhRec *)rec_new, t->n, (const ExhDeal *)t->d_exh_deal, (const int *)t->d_pid, t->d_exh_wpos,
-                               (int)t->partial_per_tour, t->d_partial, t->d_state);
+                               (const ExhRec *)rec_new, t->n, exh_cands(t), (const ExhDeal *)t->d_exh_deal, t->d_exh_cand, t->d_state);
             return TSP_OK;
         }
     }
@@ -1001,11 +1001,13 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
         // CU's LDS (it uses none of it): one more does not fit.  (Below 64 KiB: no opt-in attribute needed.)
         if (B == 1 && inst->ctx->lds_bytes >= 65536)
             t->exh_lds = std::min(65536, inst->ctx->lds_bytes / waves) - 1024;
-        t->partial_per_tour = std::max(t->partial_per_tour, (size_t)t->exh_blocks);
+        static_assert(2048 <= kExhMaxCand, "exh_decide takes a tour's candidates in two rounds at the most");
         const size_t pn = (size_t)B * (inst->n + kExhPad);
         TSP_HIP_TRY(hipMalloc(&t->d_prec[0], pn * sizeof(ExhRec)));
         TSP_HIP_TRY(hipMalloc(&t->d_prec[1], pn * sizeof(ExhRec)));
-        TSP_HIP_TRY(hipMalloc(&t->d_pid, pn * sizeof(int)));
+        // one candidate per workgroup of the grid, by position; all empty (p = -1) until a sweep has written them
+        TSP_HIP_TRY(hipMalloc(&t->d_exh_cand, (size_t)B * exh_cands(t) * sizeof(ExhCand)));
+        TSP_HIP_TRY(hipMemset(t->d_exh_cand, 0xff, (size_t)B * exh_cands(t) * sizeof(ExhCand)));
         {   // rows per wave for each of the `waves` equal parts of the grid (k_exh: the older a workgroup, the larger its share);
             // TSP_EXH_SHARES = per-cent figures (or "0": equal shares), the default measured on MI355X
             t->exh_share[0] = t->exh_share[1] = t->exh_share[2] = t->exh_share[3] = 0;
@@ -1041,10 +1043,6 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
     TSP_HIP_TRY(hipMalloc(&t->d_state_base, 2 * (size_t)B * sizeof(TourState)));   // two slots per tour (k_first)
     t->d_state = t->d_state_base; t->slot = 0;
     TSP_HIP_TRY(hipMalloc(&t->d_partial, (size_t)B * t->partial_per_tour * sizeof(Partial)));
-    if (t->exh_blocks > 0) {   // the positions of each block's candidate (k_exh), parallel to d_partial
-        TSP_HIP_TRY(hipMalloc(&t->d_exh_wpos, (size_t)B * t->partial_per_tour * sizeof(int2)));
-        TSP_HIP_TRY(hipMemset(t->d_exh_wpos, 0, (size_t)B * t->partial_per_tour * sizeof(int2)));
-    }
     TSP_HIP_TRY(hipMalloc(&t->d_slot_evals, (size_t)B * t->partial_per_tour * sizeof(int)));
     TSP_HIP_TRY(hipMalloc(&t->d_ticket, (size_t)B * sizeof(int)));
     t->use_recs = TSP_SW(inst, BEST_RECS, 1);
@@ -1067,7 +1065,7 @@ void tsp_dev_tours_destroy(tsp_dev_tours *t) {
     (void)hipFree(t->d_state_base); (void)hipFree(t->d_partial); (void)hipFree(t->d_slot_evals); (void)hipFree(t->d_ticket); (void)hipFree(t->d_rec);
     (void)hipFree(t->d_gmax); (void)hipFree(t->d_order2); (void)hipFree(t->d_pos2); (void)hipFree(t->d_pairtab); (void)hipFree(t->d_cl_ticket);
     (void)hipFree(t->d_row_ticket); (void)hipFree(t->d_row_evals); (void)hipFree(t->d_row_slot);
-    (void)hipFree(t->d_prec[0]); (void)hipFree(t->d_prec[1]); (void)hipFree(t->d_pid); (void)hipFree(t->d_exh_deal); (void)hipFree(t->d_exh_wpos);
+    (void)hipFree(t->d_prec[0]); (void)hipFree(t->d_prec[1]); (void)hipFree(t->d_exh_deal); (void)hipFree(t->d_exh_cand);
     (void)hipFree(t->d_cl_slots); (void)hipFree(t->d_cl_pairtab); (void)hipFree(t->d_cl_stats);
     (void)hipFree(t->d_chain); (void)hipHostFree(t->h_chain); (void)hipFree(t->d_order_snap); (void)hipFree(t->d_kick_result); (void)hipHostFree(t->h_kick_result); (void)hipHostFree(t->h_cl_err);
     (void)hipHostFree(t->h_state);
