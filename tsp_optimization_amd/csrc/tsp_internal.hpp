@@ -48,7 +48,11 @@ struct alignas(16) TourState {
     // exhaustive sweep (k_move_pos + k_exh): the sweep's candidates are written and its move is not decided yet -- the next
     // k_move_pos decides it, or k_exh_close before the host looks.  Never set together with `pending`, never seen by the host.
     int open;
-    int pad1, pad2;
+    // exhaustive sweep: which record buffer (1 or 2: d_prec[0], d_prec[1]) holds the tour's records, written by k_move_pos with
+    // them; 0 between run calls (k_flush_state) and for a tour no launch of the run call has written records of.  Read by
+    // k_exh_settle alone.
+    int rec_buf;
+    int pad2;
 };
 
 constexpr int kScanThreads = 256;
@@ -174,7 +178,9 @@ struct tsp_dev_tours {
     // Two buffers: k_move_pos writes d_prec[exh_buf ^ 1] -- from d_prec[exh_buf] when exh_hot says that those are the records of
     // the tour as it stands -- and the k_exh behind it reads what it wrote; the host flips exh_buf with the pair of launches.
     // exh_hot is true only inside a run call that has queued an exhaustive pair (tsp_grid_run): between calls anything may
-    // move the tour (the flush carries out a pending move, other engines, an upload).
+    // move the tour (the flush carries out a pending move, other engines, an upload).  While it is true the records are the
+    // tour and d_order / d_pos (both copies) are STALE: hot launches of k_move_pos do not write them.  Whoever takes exh_hot
+    // back (launch_flush) queues k_exh_settle first, which writes them from the records; nothing else may read them before.
     tsp::ExhRec *d_prec[2] = {nullptr, nullptr};
     int exh_buf = 0;
     bool exh_hot = false;
@@ -212,8 +218,11 @@ struct tsp_dev_tours {
     int *d_order0 = nullptr;
     std::vector<double> h_obj0;
     std::vector<int> h_order_buf;    // staging of tsp_dev_tours_upload
-    // pinned host mirror of the states, for polling
+    // pinned host mirror of the states, for polling: 3 x B.  The first B are what every reader of h_state looks at; the other two
+    // slots take the copies of a run whose polls stay one burst behind the queue (tsp_grid_run), poll k into slot 1 + k mod 2 and
+    // poll_ev[k mod 2] recorded behind it, so that a copy in flight never lands in a block the host is reading.
     tsp::TourState *h_state = nullptr;
+    hipEvent_t poll_ev[2] = {nullptr, nullptr};
     // scan geometry
     int first_grid_rows = 32;        // k_first: tile rows of its fixed grid
     int first_max_rows2 = 2048;      // k_first: largest chunk

@@ -38,9 +38,15 @@
 // at the pair's two positions} -> stores (their addresses come from preloaded kernel arguments): the pair is decided by position
 // and its orientation -- pa is the position of the smaller id -- is not known when the records are asked for, so a thread
 // evaluates exh_perm for both orientations, asks for the records of both and the two ids in one round, and keeps one behind the
-// single wait.  order, pos and coord are not read (order and pos are still written, for every other reader).  The
-// first sweep of a run call is cold (built from order and coord): only inside a run call does the host know that the old buffer
-// describes the tour (tsp_dev_tours::exh_hot).
+// single wait.  order, pos and coord are neither read nor written, and the pads (written into both buffers when the handle is
+// created, k_exh_pads) are not touched: a hot launch covers positions 0 .. n.
+// Who owns the truth.  The first sweep of a run call is cold: built from order and coord, which describe the tour between run
+// calls.  From then on, for as long as the host's tsp_dev_tours::exh_hot holds, the RECORDS are the tour (the buffer a tour's
+// control block names, TourState::rec_buf; a pending move not yet carried out in them) and order / pos / parity are stale: no
+// launch of the run reads them -- the decision, the orientation, the tie-break and the finished tour's cost (the sum of eprev)
+// all come from the records, in k_move_pos and in k_exh_close alike.  Where exh_hot ends -- the flush at the end of a run call,
+// a failed launch, an error return -- k_exh_settle writes order and pos back from the records, one launch, and only then is a
+// pending move carried out in them: when the run call returns they describe the tour exactly as before.
 // Hand-off.  k_exh ends at its block's candidate {delta, p, q}, p < q the POSITIONS of the pair, one 16-byte store: no counter,
 // no last block, and no node id -- behind a wave's last row come one wave_min, a ballot, one barrier and one thread's fold of the
 // block's four waves.  The ids are needed for the tie-break among different pairs at the minimal delta (rare: loaded from the
@@ -53,7 +59,8 @@
 // of one launch: a tour has two control blocks, k_move_pos reads slot s and its block 0 writes the advanced block to slot
 // s ^ 1; k_exh reads `done` there and one thread of it sets `open` there ("candidates written, not decided"), which nobody
 // else in that launch reads.  The host flips s per pair of launches; before it looks at a control block k_exh_close (one
-// block per tour) turns an open sweep into a pending move, which the next k_move_pos or the flush carries out.
+// block per tour) turns an open sweep into a pending move, which the next k_move_pos (in the records) or the flush (in order / pos,
+// behind k_exh_settle) carries out.
 // k_exh: the pair-columns are cut into strips of W - 1 (W = 64 RJ columns of D per wave, RJ adjacent columns per lane),
 // laid out from the RIGHT end (exh_strip: the partial strip is the leftmost one, which has the fewest rows);
 // a strip's rows are its units of work, and the units of all strips, laid end to end, are dealt to the waves in
@@ -255,6 +262,50 @@ __device__ __forceinline__ SweepDecision exh_decision(const ExhMove &m) {
     return d;
 }
 
+// The cost of the tour whose records these are (tabusearch.c:168-172): the sum of the edges that end at positions 1 .. n, position
+// n being the repeat of position 0 with the closing edge.  Integer-valued terms below 2^53 in all: exact in any order, so the
+// same double, bit for bit, as tour_cost_block's sum over the nodes.  Block-wide.
+__device__ __forceinline__ double exh_rec_cost(const ExhRec *__restrict__ rec, int n, double *s_d) {
+    double c = 0.0;
+    for (int k = 1 + (int)threadIdx.x; k <= n; k += (int)blockDim.x) c += (double)rec[k].eprev;
+    return block_sum<double>(c, s_d);
+}
+
+// Positions n + 1 .. n + kExhPad - 1 of both record buffers, once per tours handle: far outside the instance, no edge, id -1 --
+// what a cold k_move_pos writes there.  Hot launches stop at position n.
+__global__ void k_exh_pads(const double2 *__restrict__ coord, ExhRec *__restrict__ rec_a, ExhRec *__restrict__ rec_b, int n) {
+    const int k = n + 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n + kExhPad) return;
+    const double2 c0 = coord[0];
+    const double2 cu = make_double2(c0.x - 6.0e6, c0.y - 6.0e6);
+    ExhRec r;
+    exh_rec_xy(cu.x - c0.x, cu.y - c0.y, r);
+    r.eprev = 0;
+    r.id = -1;
+    const size_t at = (size_t)blockIdx.y * (n + kExhPad) + k;
+    rec_a[at] = r;
+    rec_b[at] = r;
+}
+
+// When the records stop being the tour (the end of a run call, before the flush carries out a pending move; a failed launch):
+// order and pos, in the copy that parity names, back from the tour's last records.  One launch per run call instead of two
+// stores per thread and sweep.  (The flush behind it clears the mark with parity and pending, k_flush_state.)
+// Which buffer: the one the tour's control block names (rec_buf: 1 or 2, set by the last k_move_pos that wrote records of this
+// tour -- a tour that finished some launches ago has its last records in either buffer, whatever the host's exh_buf says now);
+// 0: no launch since the last flush has written any (a tour that was finished when the run call began), order and pos are current.
+__global__ void k_exh_settle(const ExhRec *__restrict__ rec_a, const ExhRec *__restrict__ rec_b, const TourState *__restrict__ states,
+                             int *orders, int *poss, int *orders2, int *poss2, int n) {
+    const int tour = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int mark = states[tour].rec_buf;
+    if (k >= n || mark == 0) return;
+    const bool second = states[tour].parity != 0;
+    const size_t base = (size_t)tour * n;
+    const int u = (mark == 1 ? rec_a : rec_b)[(size_t)tour * (n + kExhPad) + k].id;
+    if ((unsigned)u >= (unsigned)n) return;   // (positions 0 .. n - 1 of written records hold node ids; never a store out of bounds)
+    ((second ? orders2 : orders) + base)[k] = u;
+    ((second ? poss2 : poss) + base)[u] = k;
+}
+
 // (1) the move: the open sweep's, decided here by every block for itself, or a pending one (decided by k_exh_close); (2) that move,
 // out of place; (3) the tour AFTER it in position order: records, ids in them.  Reads the control block `states`, which no block of
 // this launch writes; block 0 writes the advanced one to `states_next` (the tour's other slot), which no block of this launch reads.
@@ -271,7 +322,7 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
                                                            const ExhRec *__restrict__ rec_old, int cand_per_tour, int n,
                                                            ExhRec *__restrict__ rec, TourState *__restrict__ states_next,
                                                            const double2 *__restrict__ coord, int *orders, int *poss, int *orders2,
-                                                           int *poss2) {
+                                                           int *poss2, int rec_mark) {
     static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only (integer costs: the tour cost needs no staging)");
     __shared__ double s_d[kScanThreads / 64];
     __shared__ u64 s_k[kScanThreads / 64];
@@ -305,7 +356,9 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
         pr = exh_decide(first, cand, cand_per_tour, [&](int p) { if constexpr (HOT) return old[p].id; else return mv.order[p]; }, s_d, s_k);
         if (!pr.found) {   // the local optimum: block 0 recomputes the cost (tabusearch.c:168-172), nobody has records to build
             if (blockIdx.x != 0) return;
-            const double cost = tour_cost_block<WT, INT>(coord, mv.order, mv.pos, n, s_d, nullptr);
+            double cost;
+            if constexpr (HOT) cost = exh_rec_cost(old, n, s_d);   // (order / pos may be stale: the records are the tour)
+            else cost = tour_cost_block<WT, INT>(coord, mv.order, mv.pos, n, s_d, nullptr);
             if (writer) {
                 TourState z = *st;
                 sweep_count(z, dec, n, cost);
@@ -316,7 +369,7 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
         }
     }
     const int k = blockIdx.x * kScanThreads + threadIdx.x;
-    if (k >= n + kExhPad) return;
+    if (k >= (HOT ? n + 1 : n + kExhPad)) return;   // (the pads never change: written once per buffer, k_exh_pads)
     int u;
     ExhRec r;
     if constexpr (HOT) {
@@ -361,30 +414,35 @@ __global__ __launch_bounds__(kScanThreads) void k_move_pos(const TourState *__re
         r.eprev = len;
         r.id = u;
     }
-    // order and pos stay current for every other reader (these stores are on nobody's path)
-    if (mv.L > 0 && k < n) {
-        int *o_new = (parity ? orders : orders2) + base, *p_new = (parity ? poss : poss2) + base;
-        o_new[k] = u;
-        p_new[u] = k;
+    // A cold launch keeps order and pos current (it can only have a move to carry out when someone left one pending).  A hot
+    // one leaves them alone, and parity with them: while the host's exh_hot holds, the records are the tour and nobody reads
+    // order or pos; k_exh_settle brings them back from the records before anybody does.
+    if constexpr (!HOT) {
+        if (mv.L > 0 && k < n) {
+            int *o_new = (parity ? orders : orders2) + base, *p_new = (parity ? poss : poss2) + base;
+            o_new[k] = u;
+            p_new[u] = k;
+        }
     }
     rec[pbase + k] = r;
     if (writer) {   // the next control block: the sweep counted, the move carried out (the other copy is the current one now)
         // (the writer is thread 0 of block 0: k = 0, never past the early return above)
         TourState z = *st;
         if (open) sweep_count(z, dec, n, 0.0);
-        if (mv.L > 0) z.parity ^= 1;
+        if (!HOT && mv.L > 0) z.parity ^= 1;
         z.pending = 0;
+        z.rec_buf = rec_mark;   // `rec` holds this tour's records from here on (a finished tour keeps the mark of its last ones)
         states_next[tour] = z;
     }
 }
 
 // Before the host looks at a control block (a poll, the end of a run): an open sweep becomes a decided one -- the counters, and
 // either a pending move, which the next k_move_pos or the flush carries out, or the finished tour's recomputed cost.  One block
-// per tour, so it updates the control block it reads (behind the barriers of the decision).  Ids and orientation by dependent
-// loads through order: one launch in many.
+// per tour, so it updates the control block it reads (behind the barriers of the decision).  Ids, orientation and the finished
+// tour's cost from the records the open sweep ran on (a sweep is only ever open behind its own pair of launches: `rec_all` is the
+// buffer that pair wrote and read); order, pos and coord are not read.  Dependent loads: one launch in many.
 template <int WT, bool INT>
-__global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__restrict__ coord, const int *orders, const int *poss,
-                                                            const int *orders2, const int *poss2, TourState *states,
+__global__ __launch_bounds__(kScanThreads) void k_exh_close(const ExhRec *__restrict__ rec_all, TourState *states,
                                                             const ExhCand *__restrict__ cands, int cand_per_tour, int n) {
     static_assert(exh_metric<WT>() && INT, "integer-coordinate metrics only");
     __shared__ double s_d[kScanThreads / 64];
@@ -392,16 +450,14 @@ __global__ __launch_bounds__(kScanThreads) void k_exh_close(const double2 *__res
     const int tour = blockIdx.x;
     TourState *st = states + tour;
     if (st->done || !st->open) return;
-    const size_t base = (size_t)tour * n;
-    const bool second = st->parity != 0;
-    const int *order = (second ? orders2 : orders) + base, *pos = (second ? poss2 : poss) + base;
+    const ExhRec *__restrict__ rec = rec_all + (size_t)tour * (n + kExhPad);
     const ExhCand *cand = cands + (size_t)tour * cand_per_tour;
     const ExhPair pr = exh_decide(exh_cand_load(cand, cand_per_tour, threadIdx.x), cand, cand_per_tour,
-                                  [&](int p) { return order[p]; }, s_d, s_k);
+                                  [&](int p) { return rec[p].id; }, s_d, s_k);
     SweepDecision dec;
     double cost = 0.0;
-    if (pr.found) dec = exh_decision(exh_orient(pr.p, pr.q, n, order[pr.p] < order[pr.q]));
-    else cost = tour_cost_block<WT, INT>(coord, order, pos, n, s_d, nullptr);
+    if (pr.found) dec = exh_decision(exh_orient(pr.p, pr.q, n, rec[pr.p].id < rec[pr.q].id));
+    else cost = exh_rec_cost(rec, n, s_d);
     if (threadIdx.x == 0) {
         TourState z = *st;
         sweep_count(z, dec, n, cost);

@@ -298,22 +298,31 @@ int tabu_list_prepare(tsp_dev_tours *t, tsp_dev_tabu *tb, bool *usable, long lon
     return TSP_OK;
 }
 
-// Whoever queues exhaustive pairs (launch_step) holds one of these for as long as it does: the records of the last pair describe
-// the tour only until the caller stops -- false on entry, false again on every way out (tsp_dev_tours::exh_hot).
+void launch_flush(tsp_dev_tours *t);
+
+// Whoever queues exhaustive pairs (launch_step) holds one of these for as long as it does: the records of the last pair ARE
+// the tour until the caller stops, order and pos are stale meanwhile -- false on entry, false again on every way out
+// (tsp_dev_tours::exh_hot).  The way out is launch_flush, which settles order and pos from the records first; a caller that
+// leaves without it (an error return) gets it from here.
 struct ExhHotScope {
     tsp_dev_tours *t;
     explicit ExhHotScope(tsp_dev_tours *t_) : t(t_) { t->exh_hot = false; }
-    ~ExhHotScope() { t->exh_hot = false; }
+    ~ExhHotScope() { if (t->exh_hot) launch_flush(t); }
     ExhHotScope(const ExhHotScope &) = delete;
     ExhHotScope &operator=(const ExhHotScope &) = delete;
 };
 
 // After sorted sweeps: pending move carried out, tour back in the first copy of order/pos.
 void launch_flush(tsp_dev_tours *t) {
-    t->exh_hot = false;   // a pending move is carried out in order / pos: the exhaustive sweep's records no longer describe the tour
-    if (!t->d_order2) return;
     hipStream_t s = t->inst->ctx->stream;
     const dim3 g((t->n + 255) / 256, t->B);
+    // behind hot exhaustive pairs order / pos are stale: back from the records (k_exh_settle), before the pending move is carried
+    // out in them -- from here on the records no longer describe the tour
+    if (t->exh_hot)
+        hipLaunchKernelGGL(k_exh_settle, g, dim3(256), 0, s, (const ExhRec *)t->d_prec[0], (const ExhRec *)t->d_prec[1],
+                           (const TourState *)t->d_state, t->d_order, t->d_pos, t->d_order2, t->d_pos2, t->n);
+    t->exh_hot = false;
+    if (!t->d_order2) return;
     hipLaunchKernelGGL(k_flush_move, g, dim3(256), 0, s, t->d_order, t->d_pos, t->d_order2, t->d_pos2, t->d_state, t->n);
     hipLaunchKernelGGL(k_flush_copy, g, dim3(256), 0, s, t->d_order, t->d_pos, t->d_order2, t->d_pos2, t->d_state, t->n);
     hipLaunchKernelGGL(k_flush_state, dim3((t->B + 255) / 256), dim3(256), 0, s, t->d_state, t->B);
@@ -336,8 +345,8 @@ void launch_exh_close(tsp_dev_tours *t) {
     hipStream_t s = t->inst->ctx->stream;
     TSP_DISPATCH_METRIC(t->inst->wtype, t->inst->integer_cost, {
         if constexpr (exh_metric<WTC>())
-            hipLaunchKernelGGL((k_exh_close<WTC, INTC>), dim3(t->B), dim3(kScanThreads), 0, s, t->inst->d_coord, t->d_order, t->d_pos,
-                               t->d_order2, t->d_pos2, t->d_state, (const ExhCand *)t->d_exh_cand, exh_cands(t), t->n);
+            hipLaunchKernelGGL((k_exh_close<WTC, INTC>), dim3(t->B), dim3(kScanThreads), 0, s, (const ExhRec *)t->d_prec[t->exh_buf],
+                               t->d_state, (const ExhCand *)t->d_exh_cand, exh_cands(t), t->n);
     });
 }
 
@@ -384,14 +393,16 @@ int launch_step(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int te
             const ExhRec *rec_old = t->exh_hot ? t->d_prec[t->exh_buf] : nullptr;
             t->exh_buf ^= 1;
             ExhRec *rec_new = t->d_prec[t->exh_buf];
-            const dim3 gm((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B);
+            // a hot launch covers positions 0 .. n (the pads are in both buffers since the handle was created), a cold one the pads too
+            const dim3 gm((t->n + kExhPad + kScanThreads - 1) / kScanThreads, t->B), gh((t->n + 1 + kScanThreads - 1) / kScanThreads, t->B);
             const ExhCand *cands = t->d_exh_cand;
+            const int mark = t->exh_buf + 1;   // (TourState::rec_buf)
             if (rec_old)
-                hipLaunchKernelGGL((k_move_pos<WT, INT, true>), gm, dim3(kScanThreads), 0, s, cur, cands, rec_old, exh_cands(t), t->n,
-                                   rec_new, t->d_state, t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2);
+                hipLaunchKernelGGL((k_move_pos<WT, INT, true>), gh, dim3(kScanThreads), 0, s, cur, cands, rec_old, exh_cands(t), t->n,
+                                   rec_new, t->d_state, t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2, mark);
             else
                 hipLaunchKernelGGL((k_move_pos<WT, INT, false>), gm, dim3(kScanThreads), 0, s, cur, cands, rec_old, exh_cands(t), t->n,
-                                   rec_new, t->d_state, t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2);
+                                   rec_new, t->d_state, t->inst->d_coord, t->d_order, t->d_pos, t->d_order2, t->d_pos2, mark);
             t->exh_hot = true;   // (tsp_grid_run takes it back when the call returns)
             const dim3 g(t->exh_blocks, 1, t->B);
             hipLaunchKernelGGL((k_exh<WT, INT, kExhRJ>), g, dim3(kScanThreads), (size_t)t->exh_lds, s, (const TourState *)t->d_state,
@@ -498,7 +509,16 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
         tabu->last_run_list = t->tabu_list_run;
         if (t->tabu_list_run) TSP_HIP_TRY(hipMemsetAsync(tabu->d_tabu_pairs, 0, kTabuSideWords * sizeof(unsigned long long), s));
     }
-    const int64_t batch = 64;
+    const bool exh = exh_run(t, mode, tabu);   // the last queued sweep is open until k_exh_close has decided it
+    // A synchronous exhaustive run without a time limit never drains the stream for a poll: poll k (the copy of the control
+    // blocks into poll slot k mod 2, an event) is queued behind burst k, burst k + 1 behind that, and only then does the
+    // host wait for poll k's event -- the chip works on burst k + 1 while the host wakes, reads `done` and queues burst k + 2.
+    // When poll k shows every tour done, burst k + 1 (at most `batch` pairs, polled too) is queued already: its launches find
+    // `done` and return, a microsecond or two each.  A run with a time limit keeps the drain: its overshoot would grow by
+    // a burst.
+    const bool piped = exh && sync && !(time_limit_s > 0);
+    // (a poll that drains nothing is cheap and the burst behind the last one is wasted: half the burst, measured)
+    const int64_t batch = piped ? 32 : 64;
     // launches between two looks at `done`: short descents (a kicked local optimum, a small instance) should not
     // pay for dozens of launches that find their tour finished, long ones not for many polls
     int64_t burst = sync ? 8 : batch;
@@ -506,8 +526,16 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
     int status = TSP_OK;
     bool finished = false;
     if (all_done) *all_done = 0;
-    const bool exh = exh_run(t, mode, tabu);   // the last queued sweep is open until k_exh_close has decided it
     if (!exh) launch_arm(t, mode);             // (the exhaustive sweep takes no tickets, and k_move_pos writes the slot it hands on whole)
+    int64_t polls = 0;   // (piped) polls queued; all but the last have been looked at
+    // waits for poll k, brings it to the front of h_state, where every reader looks, and says whether every tour is done
+    auto look = [&](int64_t k, bool *done) -> int {
+        TSP_HIP_TRY(hipEventSynchronize(t->poll_ev[k & 1]));
+        memcpy(t->h_state, t->h_state + (size_t)(1 + (k & 1)) * t->B, sizeof(TourState) * (size_t)t->B);
+        *done = true;
+        for (int b = 0; b < t->B; ++b) *done = *done && t->h_state[b].done;
+        return TSP_OK;
+    };
     for (;;) {
         int64_t todo = burst;
         burst = std::min(batch, burst * 2);
@@ -523,13 +551,35 @@ int tsp_grid_run(tsp_dev_tours *t, int mode, tsp_dev_tabu *tabu, int iter, int t
         queued += todo;
         TSP_HIP_TRY(hipGetLastError());
         if (!sync) continue;
-        if (exh) launch_exh_close(t);
+        // A poll that drains closes the open sweep, so that the host sees `done` as early as can be.  One that does not drain only
+        // looks: a tour that finishes with the burst's last sweep is found out by the next k_move_pos instead, one poll later, and
+        // k_exh_close (5 us of the stream per poll) is queued only behind the last burst of a capped run, whose sweep nobody else
+        // would decide.
+        if (exh && (!piped || (max_steps >= 0 && queued >= max_steps))) launch_exh_close(t);
+        if (piped) {
+            TSP_HIP_TRY(hipMemcpyAsync(t->h_state + (size_t)(1 + (polls & 1)) * t->B, t->d_state, sizeof(TourState) * (size_t)t->B,
+                                       hipMemcpyDeviceToHost, s));
+            TSP_HIP_TRY(hipEventRecord(t->poll_ev[polls & 1], s));
+            ++polls;
+            if (polls < 2) continue;   // (the first burst has nothing queued behind it yet)
+            bool done = false;
+            const int rc = look(polls - 2, &done);
+            if (rc) return rc;
+            if (done) { finished = true; if (all_done) *all_done = 1; break; }
+            continue;
+        }
         TSP_HIP_TRY(hipMemcpyAsync(t->h_state, t->d_state, sizeof(TourState) * (size_t)t->B, hipMemcpyDeviceToHost, s));
         TSP_HIP_TRY(hipStreamSynchronize(s));
         bool done = true;
         for (int b = 0; b < t->B; ++b) done = done && t->h_state[b].done;
         if (done) { finished = true; if (all_done) *all_done = 1; break; }
         if (time_limit_s > 0 && wall_s() - t0 > time_limit_s) { status = TSP_TIME_LIMIT_EXCEEDED; break; }
+    }
+    if (piped && !finished && polls > 0) {   // max_steps ended the queue: the last poll has nothing behind it to wait for
+        bool done = false;
+        const int rc = look(polls - 1, &done);
+        if (rc) return rc;
+        if (done) { finished = true; if (all_done) *all_done = 1; }
     }
     if (tabu && t->tabu_list_run)   // the sweeps counted every non-adjacent pair; the skipped ones come off
         hipLaunchKernelGGL(k_tabu_fix_evals, dim3(1), dim3(64), 0, s, t->d_state, tabu->d_tabu_pairs);
@@ -1005,6 +1055,10 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
         const size_t pn = (size_t)B * (inst->n + kExhPad);
         TSP_HIP_TRY(hipMalloc(&t->d_prec[0], pn * sizeof(ExhRec)));
         TSP_HIP_TRY(hipMalloc(&t->d_prec[1], pn * sizeof(ExhRec)));
+        // the pads of both buffers, once: hot launches of k_move_pos stop at position n
+        hipLaunchKernelGGL(k_exh_pads, dim3((kExhPad - 1 + 255) / 256, B), dim3(256), 0, inst->ctx->stream,
+                           (const double2 *)inst->d_coord, t->d_prec[0], t->d_prec[1], inst->n);
+        TSP_HIP_TRY(hipGetLastError());
         // one candidate per workgroup of the grid, by position; all empty (p = -1) until a sweep has written them
         TSP_HIP_TRY(hipMalloc(&t->d_exh_cand, (size_t)B * exh_cands(t) * sizeof(ExhCand)));
         TSP_HIP_TRY(hipMemset(t->d_exh_cand, 0xff, (size_t)B * exh_cands(t) * sizeof(ExhCand)));
@@ -1051,7 +1105,8 @@ int tsp_dev_tours_create(tsp_dev_inst *inst, int B, tsp_dev_tours **out) {
     TSP_HIP_TRY(hipMalloc(&t->d_row_ticket, (size_t)B * t->max_tile_rows * sizeof(int)));
     TSP_HIP_TRY(hipMalloc(&t->d_row_evals, (size_t)B * t->max_tile_rows * sizeof(int)));
     TSP_HIP_TRY(hipMalloc(&t->d_row_slot, (size_t)B * t->max_tile_rows * sizeof(Partial)));
-    TSP_HIP_TRY(hipHostMalloc(&t->h_state, (size_t)B * sizeof(TourState)));
+    TSP_HIP_TRY(hipHostMalloc(&t->h_state, 3 * (size_t)B * sizeof(TourState)));   // (+ two poll slots, tsp_internal.hpp)
+    for (hipEvent_t &e : t->poll_ev) TSP_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     guard.t = nullptr;
     *out = t;
     return TSP_OK;
@@ -1069,6 +1124,7 @@ void tsp_dev_tours_destroy(tsp_dev_tours *t) {
     (void)hipFree(t->d_cl_slots); (void)hipFree(t->d_cl_pairtab); (void)hipFree(t->d_cl_stats);
     (void)hipFree(t->d_chain); (void)hipHostFree(t->h_chain); (void)hipFree(t->d_order_snap); (void)hipFree(t->d_kick_result); (void)hipHostFree(t->h_kick_result); (void)hipHostFree(t->h_cl_err);
     (void)hipHostFree(t->h_state);
+    for (hipEvent_t e : t->poll_ev) if (e) (void)hipEventDestroy(e);
     delete t;
 }
 

@@ -86,7 +86,7 @@ __global__ void k_flush_copy(int *orders, int *poss, const int *orders2, const i
 }
 __global__ void k_flush_state(TourState *states, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) { states[b].parity = 0; states[b].pending = 0; }
+    if (b < B) { states[b].parity = 0; states[b].pending = 0; states[b].rec_buf = 0; }   // (rec_buf: the exhaustive sweep's, two_opt_exh.hpp)
 }
 
 // v of lane l (l wave-uniform) in every lane, through two v_readlane_b32
