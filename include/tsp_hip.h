@@ -677,6 +677,59 @@ int tsp_dev_one_tree(tsp_dev_inst *inst, const double *pi, int *edges, int *deg,
 int tsp_dev_held_karp(tsp_dev_inst *inst, double ub, int max_iters, double lambda0, int patience, double time_limit_s,
                       double *pi, double *bound, tsp_lb_stats *stats);
 
+/* ---- Held-Karp ascent over the candidate graph, certified by dense 1-trees (extension) -----------------------
+ * d, pi, the weight w, the order (w, lo, hi), special node 0 and W are those of the Held-Karp section above.
+ * Candidate graph C: the undirected edges {v, nbr[v][k]} of the lists in the handle (tsp_dev_inst_knn_build / _knn_set /
+ * _alpha_build); an edge that several entries name counts once.  Without lists in the handle the call builds nearest-neighbour
+ * lists with K = min(TSP_NL_DEFAULT_K, n - 1), as tsp_dev_nl_opt does.  Any lists tsp_dev_inst_knn_set accepts are legal: C may
+ * be disconnected, a node may be named by every list, K may be 1.
+ * Sparse 1-tree T_C(pi), n >= 3.  Spanning part: Kruskal over the edges of C among nodes 1 .. n-1 in the order (w, lo, hi); if
+ * more than one component is left, Kruskal goes on over ALL edges among nodes 1 .. n-1 in the same order (the completion).
+ * Node 0: the two smallest edges of C at node 0 in the same order; if C has fewer than two edges at node 0, the two smallest of
+ * all n - 1 edges at node 0, as in the dense tree.  W_C(pi) is the same sum as W, taken over T_C.  W_C(pi) >= W(pi), and W_C is
+ * NOT a lower bound.  With C complete (K = n - 1) T_C = T.
+ * Rounds (deterministic under the strict order): sparse_rounds = the Boruvka rounds over C in which at least one component
+ * hooks; completion_rounds = the Boruvka rounds over the complete graph behind them, counted while more than one component exists.
+ * Ascent in two phases.  Sparse phase: steps 1 - 5 of the ascent above with T_C, W_C, best_C, pi_best_C in place of T, W, best,
+ * pi_best, for at most sparse_iters iterations, with two changes: |g|^2 == 0 ends the phase WITHOUT tour_found (a sparse tree that
+ * is a tour proves nothing), and W_C >= ub ends the phase before step 4 (the step length would not be positive).  Dense phase:
+ * exactly tsp_dev_held_karp(ub, dense_iters, lambda0 = the sparse phase's final lambda, patience, what is left of the time
+ * limit, pi = pi_best_C); its best, pi_best and tour_found are the call's.  The returned bound therefore always comes from dense
+ * 1-trees and is valid.  With sparse_iters = 0 the call is tsp_dev_held_karp(ub, dense_iters, lambda0, ...) to the bit; with
+ * K = n - 1 the sparse phase follows the dense ascent step for step.  The sparse phase stops at the time limit (after at least
+ * one iteration), at least one dense iteration always runs, and the status is then TSP_TIME_LIMIT_EXCEEDED.  No floating-point
+ * atomics: two runs return the same bits.
+ * The number of queued rounds of one tree is limited to 32: lists whose candidate graph needs more sparse plus completion
+ * rounds than that (more than about 2^15 components at n = 10^5) end in TSP_DEV_E_HIP with the reason in tsp_dev_last_error(). */
+typedef struct {
+    int64_t iterations;     /* the dense phase's counters, laid out as tsp_lb_stats ...                                     */
+    int64_t trees;
+    int64_t rounds;
+    int64_t dists_executed;
+    int tour_found;
+    double lambda_final;
+    double seconds;         /* ... but seconds and device_ms cover the whole call                                           */
+    double device_ms;
+    int64_t sparse_iterations;  /* iterations of the sparse phase                                                           */
+    int64_t sparse_trees;       /* sparse 1-trees built                                                                     */
+    int64_t sparse_rounds;      /* over all sparse trees                                                                    */
+    int64_t completion_rounds;  /* over all sparse trees                                                                    */
+    int64_t candidate_entries;  /* n * K                                                                                    */
+    int64_t components;         /* of C on nodes 1 .. n-1 (0: no sparse tree was built)                                     */
+    int64_t weights_executed;   /* edge weights the sparse scans evaluated: n * K per executed round over C                 */
+    double sparse_best;         /* best_C (-inf: no sparse tree was built)                                                  */
+    double lambda_sparse_final;
+    double sparse_device_ms;    /* device time of the sparse phase, entry distances included                                */
+} tsp_lb_sparse_stats;
+/* One T_C(pi) (pi NULL = zeros).  Outputs as tsp_dev_one_tree's, *value = W_C(pi); stats (may be NULL): the sparse fields of the
+ * one tree; of the dense counters dists_executed alone (the completion's scans; 0 for connected lists).  Penalties that are not
+ * finite or n < 3: TSP_DEV_E_ARG. */
+int tsp_dev_one_tree_sparse(tsp_dev_inst *inst, const double *pi, int *edges, int *deg, double *value, tsp_lb_sparse_stats *stats);
+/* sparse_iters >= 0, dense_iters >= 1; ub, lambda0, patience, time_limit_s, pi, bound as tsp_dev_held_karp.  Bad arguments:
+ * TSP_DEV_E_ARG with the reason in tsp_dev_last_error(); the caller's pi and the handle's lists are untouched. */
+int tsp_dev_held_karp_sparse(tsp_dev_inst *inst, double ub, int sparse_iters, int dense_iters, double lambda0, int patience,
+                             double time_limit_s, double *pi, double *bound, tsp_lb_sparse_stats *stats);
+
 /* ---- alpha-nearness candidate lists (extension; Helsgaun's LKH): what the minimum 1-tree says about an edge ------------------
  * (DESIGN.md 4.13 has the kernels and times.)  d, pi, the edge weight w, the edge order (w, lo, hi) and the minimum 1-tree T(pi)
  * with special node 0 are those of the Held-Karp section above.  For two nodes i != j:

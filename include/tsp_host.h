@@ -144,6 +144,11 @@ int HEU_nl_extramileage(instance *inst);  /* HEU_extramileage + alg_nl_opt */
  * tsp_dev_held_karp(ub = inst->solution.obj_best, ascent_iters, TSP_HK_DEFAULT_LAMBDA, default patience, no time limit, from
  * zeros).  Anything else (also ascent_iters != 0 with K = 0): TSP_DEV_E_ARG, and the setting stays. */
 int tsp_host_set_alpha(int K, int ascent_iters);
+/* Where that ascent begins (include/tsp_hip.h, tsp_dev_held_karp_sparse).  0 (the default): as above.  sparse_iters > 0, with
+ * tsp_host_set_alpha(K, ascent_iters > 0): the penalties come from tsp_dev_held_karp_sparse(ub, sparse_iters, dense_iters =
+ * ascent_iters, TSP_HK_DEFAULT_LAMBDA, default patience, no time limit, from zeros) over the nearest-neighbour lists of
+ * tsp_host_set_knn, built first; the alpha lists then replace them.  A negative value: TSP_DEV_E_ARG, and the setting stays. */
+int tsp_host_set_alpha_ascent(int sparse_iters);
 /* The list descent with the 3-opt kind (include/tsp_hip.h, tsp_dev_nl_3opt).  Library entry points only, as above. */
 int alg_3opt(instance *inst);         /* 2-opt + Or-opt + 3-opt on inst->solution over the lists tsp_host_set_knn /
                                          tsp_host_set_alpha select; obj_best receives the recomputed cost                    */
@@ -176,6 +181,9 @@ int tsp_host_set_batch(int max_arc, int rounds);
  * default patience; ub = the cost of any tour (inst->solution.obj_best after a heuristic), max_iters <= 0 =
  * TSP_HK_DEFAULT_ITERS, time_lim <= 0 = unlimited.  Returns the bound (valid also when the time limit ended the ascent). */
 double tsp_host_lower_bound(instance *inst, double ub, int max_iters, double time_lim);
+/* The same through tsp_dev_held_karp_sparse: sparse_iters >= 0 iterations over the nearest-neighbour lists of tsp_host_set_knn's
+ * K (built if the handle has none of that length), then dense_iters (<= 0 = 1) dense iterations, whose bound is returned. */
+double tsp_host_lower_bound_sparse(instance *inst, double ub, int sparse_iters, int dense_iters, double time_lim);
 
 /* ---- greedy-edge construction (extension; include/tsp_hip.h, tsp_dev_greedy_edge).  Library entry points only: no
  * solver_type, no -method row. */
@@ -315,6 +323,8 @@ void tsp_host_last_ils_stats(tsp_ils_stats *out);
 void tsp_host_last_dlb_stats(int64_t *active_nodes, int64_t *closing_scans);
 /* Counters of the last tsp_host_lower_bound call of this thread. */
 void tsp_host_last_lb_stats(tsp_lb_stats *out);
+/* Counters of the last tsp_host_lower_bound_sparse call of this thread. */
+void tsp_host_last_lb_sparse_stats(tsp_lb_sparse_stats *out);
 /* Counters of the last HEU_greedy_edge call of this thread (also through HEU_2opt_ / HEU_nl_ / HEU_ils_greedy_edge). */
 void tsp_host_last_greedy_edge_stats(tsp_greedy_edge_stats *out);
 /* Counters of the last alg_seg_ils call of this thread (also through HEU_seg_ils_greedy_edge). */

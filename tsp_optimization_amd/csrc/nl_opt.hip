@@ -408,6 +408,17 @@ int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr) {
     return TSP_OK;
 }
 
+// The handle's lists where they lie on the device, built as tsp_dev_nl_opt builds them when it has none (held_karp_sparse.hip).
+int tsp_nl_lists(tsp_dev_inst *inst, int *K, const int **d_nbr) {
+    NlData *x = nl_data(inst);
+    if (x->K == 0) {
+        const int rc = tsp_dev_inst_knn_build(inst, std::min(TSP_NL_DEFAULT_K, inst->n - 1), nullptr);
+        if (rc) return rc;
+    }
+    *K = x->K; *d_nbr = x->d_nbr;
+    return TSP_OK;
+}
+
 // One whole decision of every tour that is not done, queued on the engine's stream: k_nl_prep, k_nl_scan when kinds has one of
 // its two (candidates in the first B x nparts entries of d_part), k_nl3_scan when it has the third (in the second), the pick.
 void tsp_nl_launch_decision(tsp_dev_tours *t, NlData *x, int kinds, int dlb_mode) {

@@ -285,6 +285,7 @@ struct TabuRide {
 }
 int tsp_hk_tree(tsp_dev_inst *inst, const double *pi, tsp::HkTree *out, tsp_lb_stats *stats);   // held_karp.hip
 int tsp_nl_adopt_lists(tsp_dev_inst *inst, int K, int *d_nbr);                                  // nl_opt.hip: takes d_nbr over
+int tsp_nl_lists(tsp_dev_inst *inst, int *K, const int **d_nbr);                                 // nl_opt.hip: built if there are none
 tsp_dev_tours *tsp_scratch_tours(tsp_dev_inst *inst, int B, bool *owned, int *rc);             // api.hip
 int tsp_perm_cost_device(tsp_dev_inst *inst, const int *d_perm, long long stride, int B, double *d_out, size_t out_stride_bytes);   // api.hip
 void tsp_or_scratch_free(void *p);   // or_opt.hip

@@ -86,6 +86,13 @@ class LbStats(_Stats):
                 ("tour_found", C.c_int), ("lambda_final", C.c_double), ("seconds", C.c_double), ("device_ms", C.c_double)]
 
 
+class LbSparseStats(_Stats):
+    _fields_ = LbStats._fields_ + [("sparse_iterations", C.c_int64), ("sparse_trees", C.c_int64), ("sparse_rounds", C.c_int64),
+                                   ("completion_rounds", C.c_int64), ("candidate_entries", C.c_int64), ("components", C.c_int64),
+                                   ("weights_executed", C.c_int64), ("sparse_best", C.c_double),
+                                   ("lambda_sparse_final", C.c_double), ("sparse_device_ms", C.c_double)]
+
+
 class AlphaStats(_Stats):
     _fields_ = [("trees", C.c_int64), ("rounds", C.c_int64), ("pairs_executed", C.c_int64), ("tree_value", C.c_double),
                 ("seconds", C.c_double), ("device_ms", C.c_double)]
@@ -197,6 +204,9 @@ def lib():
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
+        lsp = C.POINTER(LbSparseStats)
+        L.tsp_dev_one_tree_sparse.argtypes = [vp, dp, ip, ip, dp, lsp]
+        L.tsp_dev_held_karp_sparse.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lsp]
         L.tsp_dev_inst_alpha_build.argtypes = [vp, C.c_int, dp, dp, C.POINTER(AlphaStats)]
         L.tsp_dev_alpha_rows.argtypes = [vp, dp, C.c_int, ip, dp]
         L.tsp_dev_greedy_edge.argtypes = [vp, ip, C.c_int, dp, ip, C.POINTER(GreedyEdgeStats)]
@@ -222,6 +232,7 @@ EXPORTED = [
     "tsp_dev_inst_knn_build", "tsp_dev_inst_knn_set", "tsp_dev_inst_knn_get", "tsp_dev_nl_opt", "tsp_dev_nl_3opt",
     "tsp_dev_ils", "tsp_dev_ils_kick", "tsp_dev_nl_3opt_dlb", "tsp_dev_ils_dlb",
     "tsp_dev_one_tree", "tsp_dev_held_karp",
+    "tsp_dev_one_tree_sparse", "tsp_dev_held_karp_sparse",
     "tsp_dev_inst_alpha_build", "tsp_dev_alpha_rows",
     "tsp_dev_greedy_edge",
     "tsp_dev_nl_3opt_batch",
@@ -570,6 +581,37 @@ class Instance:
         st = LbStats()
         rc = lib().tsp_dev_held_karp(self._h, float(ub), int(max_iters), float(lambda0), int(patience), float(time_limit), _d(pi),
                                      C.byref(bound), C.byref(st))
+        _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
+        stats = st.as_dict()
+        stats["status"] = rc
+        return bound.value, pi, stats
+
+    def one_tree_sparse(self, pi=None, want_stats=False):
+        """The 1-tree over the candidate graph of the handle's lists, completed over all edges where the lists leave several
+        components (tsp_dev_one_tree_sparse) -> (edges [n,2] sorted (lo, hi), deg [n], value W_C(pi)) (+ stats dict with
+        want_stats).  W_C is not a lower bound."""
+        pi = self._pi(pi)
+        edges = np.zeros((self.n, 2), dtype=np.int32)
+        deg = np.zeros(self.n, dtype=np.int32)
+        val = C.c_double(0)
+        st = LbSparseStats()
+        _check(lib().tsp_dev_one_tree_sparse(self._h, _d(pi) if pi is not None else None, _i(edges), _i(deg), C.byref(val),
+                                             C.byref(st)))
+        if want_stats:
+            return edges, deg, val.value, st.as_dict()
+        return edges, deg, val.value
+
+    def held_karp_sparse(self, ub, sparse_iters, dense_iters=1, lambda0=HK_DEFAULT_LAMBDA, patience=0, time_limit=-1.0, pi=None):
+        """The ascent over the candidate graph for sparse_iters iterations, then dense_iters iterations of held_karp from its
+        pi_best and lambda (tsp_dev_held_karp_sparse) -> (bound, pi_best [n], stats dict); the bound comes from dense 1-trees
+        and is valid; stats["status"] is OK or TIME_LIMIT_EXCEEDED."""
+        pi = self._pi(pi)
+        if pi is None:
+            pi = np.zeros(self.n, dtype=np.float64)
+        bound = C.c_double(0)
+        st = LbSparseStats()
+        rc = lib().tsp_dev_held_karp_sparse(self._h, float(ub), int(sparse_iters), int(dense_iters), float(lambda0), int(patience),
+                                            float(time_limit), _d(pi), C.byref(bound), C.byref(st))
         _check(rc, allow=(OK, TIME_LIMIT_EXCEEDED))
         stats = st.as_dict()
         stats["status"] = rc

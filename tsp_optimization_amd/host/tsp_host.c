@@ -147,6 +147,7 @@ static int g_dlb = TSP_DLB_OFF;                /* don't-look bits of alg_3opt an
 static int g_batch_arc = -1, g_batch_rounds;   /* the batched rule of alg_nl_opt and alg_3opt (tsp_host_set_batch); < 0: off */
 static int g_knn_k = TSP_NL_DEFAULT_K;         /* list length of alg_nl_opt (tsp_host_set_knn) */
 static int g_alpha_k = 0, g_alpha_iters = 0;   /* alpha lists instead (tsp_host_set_alpha); 0 = nearest-neighbour lists */
+static int g_alpha_sparse_iters = 0;           /* their ascent begins over the candidate graph (tsp_host_set_alpha_ascent) */
 
 static void dev_fail(const char *what, int rc) {
     LOG_E("%s failed with %d %s (this build has no CPU path: an MI355X and libtsp_hip.so are required)", what, rc,
@@ -551,14 +552,39 @@ int tsp_host_set_alpha(int K, int ascent_iters) {
     return 0;
 }
 
-/* the alpha lists of the cached handle, from zero penalties or from the ascent's pi_best (ub = the cost of the tour) */
+int tsp_host_set_alpha_ascent(int sparse_iters) {
+    if (sparse_iters < 0) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_alpha_sparse_iters = sparse_iters;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+/* nearest-neighbour lists of tsp_host_set_knn's K in the handle, built unless it holds lists of that length */
+static int knn_lists_locked(tsp_dev_inst *dev, int n) {
+    const int want = g_knn_k < n - 1 ? g_knn_k : n - 1;
+    int have = 0;
+    int rc = tsp_dev_inst_knn_get(dev, &have, NULL);
+    if (rc == 0 && have != want) rc = tsp_dev_inst_knn_build(dev, want, NULL);
+    return rc;
+}
+
+/* the alpha lists of the cached handle, from zero penalties or from the ascent's pi_best (ub = the cost of the tour); with
+ * tsp_host_set_alpha_ascent the ascent begins over the nearest-neighbour lists, which the alpha lists then replace */
 static int alpha_lists_locked(tsp_dev_inst *dev, int n, double ub) {
     const int K = g_alpha_k < n - 1 ? g_alpha_k : n - 1;
     if (g_alpha_iters == 0) return tsp_dev_inst_alpha_build(dev, K, NULL, NULL, NULL);
     double *pi = (double *)calloc((size_t)n, sizeof *pi);
     if (!pi) LOG_E("out of memory");
     double bound = 0.0;
-    int rc = tsp_dev_held_karp(dev, ub, g_alpha_iters, TSP_HK_DEFAULT_LAMBDA, 0, -1.0, pi, &bound, NULL);
+    int rc;
+    if (g_alpha_sparse_iters > 0) {
+        rc = tsp_dev_inst_knn_build(dev, g_knn_k < n - 1 ? g_knn_k : n - 1, NULL);   /* the handle may hold the last call's alpha lists */
+        if (rc == 0)
+            rc = tsp_dev_held_karp_sparse(dev, ub, g_alpha_sparse_iters, g_alpha_iters, TSP_HK_DEFAULT_LAMBDA, 0, -1.0, pi, &bound, NULL);
+    } else {
+        rc = tsp_dev_held_karp(dev, ub, g_alpha_iters, TSP_HK_DEFAULT_LAMBDA, 0, -1.0, pi, &bound, NULL);
+    }
     if (rc == 0) rc = tsp_dev_inst_alpha_build(dev, K, pi, NULL, NULL);
     free(pi);
     return rc;
@@ -853,6 +879,38 @@ double tsp_host_lower_bound(instance *inst, double ub, int max_iters, double tim
     pthread_mutex_unlock(&g_lock);
     if (rc < 0) dev_fail("tsp_dev_held_karp", rc);
     t_lb_stats = st;
+    if (rc == TIME_LIMIT_EXCEEDED) LOG_I("lower bound time exceeded");
+    return bound;
+}
+
+static __thread tsp_lb_sparse_stats t_lb_sparse_stats;
+
+void tsp_host_last_lb_sparse_stats(tsp_lb_sparse_stats *out) {
+    if (out) *out = t_lb_sparse_stats;
+}
+
+double tsp_host_lower_bound_sparse(instance *inst, double ub, int sparse_iters, int dense_iters, double time_lim) {
+    tsp_lb_sparse_stats st;
+    memset(&st, 0, sizeof st);
+    double bound = 0.0;
+    pthread_mutex_lock(&g_lock);
+    tsp_dev_inst *dev = dev_inst_locked(inst);
+    cache_slot *slot = NULL;
+    for (int k = 0; k < CACHE_SLOTS; k++)
+        if (g_cache[k].dev == dev) slot = &g_cache[k];
+    int rc = 0;
+    if (slot && slot->lists_alpha) {   /* nearest-neighbour lists, not what a list descent left */
+        rc = tsp_dev_inst_knn_build(dev, g_knn_k < inst->num_nodes - 1 ? g_knn_k : inst->num_nodes - 1, NULL);
+        if (rc == 0) slot->lists_alpha = 0;
+    } else {
+        rc = knn_lists_locked(dev, inst->num_nodes);
+    }
+    if (rc == 0)
+        rc = tsp_dev_held_karp_sparse(dev, ub, sparse_iters, dense_iters > 0 ? dense_iters : 1, TSP_HK_DEFAULT_LAMBDA, 0, time_lim,
+                                      NULL, &bound, &st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc < 0) dev_fail("tsp_dev_held_karp_sparse", rc);
+    t_lb_sparse_stats = st;
     if (rc == TIME_LIMIT_EXCEEDED) LOG_I("lower bound time exceeded");
     return bound;
 }
