@@ -35,6 +35,7 @@ def _run(seed, cases, ctx, verbose, max_n):
     from tsp_optimization_amd import engine as E
     from helpers import random_tour
     from oracle import oracle as O
+    from tabu_ref import replay as tabu_replay, upos
     own = ctx is None
     if own: ctx = E.Context(0)
     rng = np.random.default_rng(seed)
@@ -113,6 +114,7 @@ def _run(seed, cases, ctx, verbose, max_n):
             # a chain of tabu() iterations INSIDE one launch (tsp_dev_tours_tabu_iterations_ex) from a dense random tabu list: random
             # tenures (one per iteration), random kick pairs with rejected ones among them (a == b, neighbours, tabu edges), against
             # the oracle's alg_2opt_tabu + a restatement of the kick's trials (tabusearch.c:262-309) iteration by iteration
+            # (tests/tabu_ref.py)
             it0, K = int(rng.integers(1, 30)), int(rng.integers(2, 9))
             tens = [int(rng.integers(0, 12)) for _ in range(K)]
             P = K + int(rng.integers(0, 6))
@@ -121,44 +123,17 @@ def _run(seed, cases, ctx, verbose, max_n):
                 r = rng.random()
                 if r < 0.15: ab[q, 1] = ab[q, 0]
             stamps = np.zeros(n * (n - 1) // 2, dtype=np.int32)
-            up = lambda a, b: min(a, b) * n + max(a, b) - (min(a, b) + 1) * (min(a, b) + 2) // 2
+            up = lambda a, b: upos(a, b, n)
             for _ in range(int(rng.choice([0, n // 2, 2 * n]))):
                 a, b = int(rng.integers(0, n)), int(rng.integers(0, n))
                 if rng.random() < 0.4: b = int(tour[a])
                 if a != b: stamps[up(a, b)] = int(rng.integers(1, it0 + 1))
-            exp = stamps.copy()
-            cur, curo = np.array(tour, dtype=np.int32), float(cost)
-            best, objs, trials, p, stopped = float("inf"), [], [], 0, False
-
-            def is_tabu(a, b, itn, ten):      # check_tenure, :83-92
-                v = exp[up(a, b)]
-                if v == 0: return False
-                if itn - v > ten: exp[up(a, b)] = 0; return False
-                return True
-            for k in range(K):
-                itn, ten = it0 + k, tens[k]
-                _, cur, curo, _, _, _ = O.two_opt_best(xy, wt, cur, integer_cost=ic, tabu=exp, iter_=itn, tenure=ten)
-                cur = np.array(cur, dtype=np.int32)
-                best = min(best, curo)
-                objs.append(curo)
-                used, acc = 0, False
-                while p < P and not acc:
-                    a, b = int(ab[p, 0]), int(ab[p, 1]); p += 1; used += 1
-                    a1, b1 = int(cur[a]), int(cur[b])
-                    if a == b or a1 == b or b1 == a: continue
-                    if not is_tabu(a, a1, itn, ten) and not is_tabu(b, b1, itn, ten) and not is_tabu(a, b, itn, ten) and not is_tabu(a1, b1, itn, ten):
-                        acc = True
-                        path, v = [], a1                       # a1 ... b along the tour, reversed (utility.c:708-717)
-                        while True:
-                            path.append(v)
-                            if v == b: break
-                            v = int(cur[v])
-                        cur[a] = b
-                        for q in range(len(path) - 1, 0, -1): cur[path[q]] = path[q - 1]
-                        cur[a1] = b1
-                        exp[up(a, a1)] = itn; exp[up(b, b1)] = itn
-                trials.append(used)
-                if not acc: stopped = True; break
+            ref = tabu_replay(xy, wt, ic, tour, float(cost), stamps, it0, tens, ab)
+            exp, cur, objs, trials, best, stopped = ref.stamps, ref.tour, ref.obj, ref.trials, ref.inc_cost, not ref.accepted
+            # the chain on a cluster size of its own (by default these sizes get at most four workgroups), drawn from a generator
+            # of its own so that the cases keep their inputs
+            os.environ["TSP_CLUSTER_BLOCKS"] = str(int(np.random.default_rng([seed, c]).choice([2, 3, 5, 8, 17, 64, 256])))
+            inst.reload_switches()
             t, tb = E.Tours(inst, 1), E.Tabu(inst)
             t.upload(np.array(tour, dtype=np.int32), float(cost))
             tb.upload(stamps)
@@ -174,6 +149,8 @@ def _run(seed, cases, ctx, verbose, max_n):
                           % (len(w), w[0], got[w[0]], exp[w[0]], stamps[w[0]], it0, tens, trials))
                 ok = _chk(ok, 134, (got == exp).all())
             t.close(); tb.close()
+            del os.environ["TSP_CLUSTER_BLOCKS"]
+            inst.reload_switches()
         if c % 3 == 0 and n >= 8:
             # a batch of three or eight tours through the engine the library picks, and one GRASP tour on the oracle's URAND stream
             nt = 8 if n <= 200 else 3   # eight tours: the grid divides by XCD (a tour's workgroups from one XCD)
