@@ -202,10 +202,10 @@ def effective_kinds(kinds, n):
     return low | (NL_3OPT if kinds & NL_3OPT and n >= 5 else 0)
 
 
-def _decide(D, succ, nbr, kinds, three):
+def _decide(D, succ, nbr, kinds, three, low=None):
     n = len(succ)
     kinds = effective_kinds(kinds, n)
-    best = NL.decide(D, succ, nbr, kinds & 3) if kinds & 3 else None
+    best = (low or NL.decide)(D, succ, nbr, kinds & 3) if kinds & 3 else None
     if kinds & NL_3OPT:
         c = three(D, succ, nbr)
         if c is not None and NL._better(c, best):
@@ -218,9 +218,10 @@ def decide(D, succ, nbr, kinds):
     return _decide(D, succ, nbr, kinds, decide3)
 
 
-def decide_sparse(D, succ, nbr, kinds):
-    """decide() with the 3-opt kind generated from the list entries, as the kernel walks them."""
-    return _decide(D, succ, nbr, kinds, decide3_sparse)
+def decide_sparse(D, succ, nbr, kinds, low=None):
+    """decide() with the 3-opt kind generated from the list entries, as the kernel walks them.  low(D, succ, nbr, kinds): the
+    decision of the 2-opt and Or-opt kinds, nl_opt_ref.decide over the masked n x n matrices unless given."""
+    return _decide(D, succ, nbr, kinds, decide3_sparse, low)
 
 
 def apply_three_opt(succ, a, b, c, T):
@@ -258,13 +259,15 @@ def apply_decision(succ, d, c):
     return apply_three_opt(succ, a, b, cc, T)
 
 
-def descent(D, succ, nbr, kinds, max_moves=-1, sparse=True, trace=None):
-    """-> (succ', counters as tsp_nl3_opt_stats without deltas_executed and the times); trace: a list that receives the decisions"""
+def descent(D, succ, nbr, kinds, max_moves=-1, sparse=True, trace=None, low=None):
+    """-> (succ', counters as tsp_nl3_opt_stats without deltas_executed and the times); trace: a list that receives the decisions;
+    low: see decide_sparse (for sizes at which the masked matrices take seconds per decision)"""
     succ = np.array(succ, dtype=np.int32, copy=True)
     c = new_counters()
     if effective_kinds(kinds, len(succ)) == 0:
         return succ, c
-    fn = decide_sparse if sparse else decide
+    assert sparse or low is None
+    fn = (lambda *a: decide_sparse(*a, low=low)) if sparse else decide
     while max_moves < 0 or c["moves"] < max_moves:
         c["decisions"] += 1
         d = fn(D, succ, nbr, kinds)

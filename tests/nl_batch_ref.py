@@ -67,39 +67,64 @@ def removed_ends(move, succ, pred, n):
     return [int(pred[f]), f, l, int(succ[l]), a, int(succ[a])]
 
 
-def improving_moves(D, succ, nbr, kinds):
-    """every improving move as the lanes of the scans reach it -> list of (owner, (delta, kind, key)), a move as often as reached"""
+def arc_lens(kind, key, pos, n):
+    """arc(...)[1] for arrays of moves"""
+    ln = np.empty(len(key), dtype=np.int64)
+    two, three, oro = kind == 0, kind == 2, kind == 1
+    k = key[two]
+    ln[two] = (pos[k % n] - pos[k // n]) % n + 2
+    k = key[three] >> 2
+    ln[three] = (pos[k % n] - pos[k // (n * n)]) % n + 2
+    t = key[oro] >> 1
+    fl = t // n
+    L = fl % 3 + 1
+    m1 = (pos[t % n] - (pos[fl // 3] + L)) % n + 1
+    ln[oro] = np.minimum(m1, n - L - m1) + L + 2
+    return np.minimum(ln, n)
+
+
+def improving_arrays(D, succ, nbr, kinds):
+    """every improving move as the lanes of the scans reach it -> arrays (owner, delta, kind, key), a move as often as reached"""
     succ, order, pos, pred = tour(succ)
     n = len(succ)
     kinds = N3.effective_kinds(kinds, n)
     nbr = np.asarray(nbr, dtype=np.int64)
-    out = []
+    out = [(np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))]
     v = np.repeat(np.arange(n, dtype=np.int64), nbr.shape[1])
     u = nbr.reshape(-1)
     v, u = v[v != u], u[v != u]
     d = lambda a, b: D[np.minimum(a, b), np.maximum(a, b)]   # noqa: E731
+    found = []
     for kind in (0, 1):
         if kinds & (1, 2)[kind]:
-            for own, delta, key in NL.entry_moves(v, u, succ, order, pos, pred, d, kind):
-                for q in np.nonzero(delta < 0.0)[0]:
-                    out.append((int(own[q]), (float(delta[q]), kind, int(key[q]))))
+            found += [(kind,) + m for m in NL.entry_moves(v, u, succ, order, pos, pred, d, kind)]
     if kinds & 4:
-        own, delta, key = N3.sparse_moves(D, succ, nbr, with_owner=True)
-        for q in np.nonzero(delta < 0.0)[0]:
-            out.append((int(own[q]), (float(delta[q]), 2, int(key[q]))))
-    return out
+        found.append((2,) + N3.sparse_moves(D, succ, nbr, with_owner=True))
+    for kind, own, delta, key in found:
+        q = np.nonzero(delta < 0.0)[0]
+        out.append((np.asarray(own)[q], np.asarray(delta, dtype=np.float64)[q], np.full(len(q), kind), np.asarray(key)[q]))
+    return tuple(np.concatenate(col) for col in zip(*out))
+
+
+def improving_moves(D, succ, nbr, kinds):
+    """improving_arrays as a list of (owner, (delta, kind, key))"""
+    own, delta, kind, key = improving_arrays(D, succ, nbr, kinds)
+    return [(int(o), (float(d), int(t), int(k))) for o, d, t, k in zip(own, delta, kind, key)]
 
 
 def candidates(D, succ, nbr, kinds, max_arc):
     """-> ({node: its best move of an arc of at most max_arc positions}, the overall best move or None)"""
     _, _, pos, _ = tour(succ)
     n = len(succ)
-    cand, best = {}, None
-    for own, m in improving_moves(D, succ, nbr, kinds):
-        if best is None or m < best:
-            best = m
-        if arc(m, pos, n)[1] <= max_arc and (own not in cand or m < cand[own]):
-            cand[own] = m
+    own, delta, kind, key = improving_arrays(D, succ, nbr, kinds)
+    if len(own) == 0:
+        return {}, None
+    at = np.lexsort((key, kind, delta))          # by (delta, kind, key), as the tuples compare
+    best = (float(delta[at[0]]), int(kind[at[0]]), int(key[at[0]]))
+    at = at[arc_lens(kind, key, pos, n)[at] <= max_arc]
+    cand = {}
+    for o, d, t, k in zip(own[at], delta[at], kind[at], key[at]):
+        cand.setdefault(int(o), (float(d), int(t), int(k)))    # sorted: a node's first move is its best
     return cand, best
 
 

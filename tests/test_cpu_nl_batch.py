@@ -61,6 +61,26 @@ def test_without_candidates_the_reference_is_the_plain_descent_move_for_move(kin
             assert (got == ref).all() and cb == c
 
 
+def test_the_candidates_are_each_nodes_best_move_of_a_short_arc():
+    """candidates() sorts arrays; here the rule as stated, one move at a time with the scalar arc()"""
+    seen = 0
+    for n, seed in itertools.product((9, 30, 60), range(3)):
+        xy, D, succ = _instance(n, 300 * n + seed)
+        nbr = NL.knn(D, min(6, n - 1))
+        _, _, pos, _ = NB.tour(succ)
+        for kinds, max_arc in itertools.product((1, 2, 4, 7), (3, 4, 8, n // 2, n)):
+            cand, best = {}, None
+            for own, m in NB.improving_moves(D, succ, nbr, kinds):
+                if best is None or m < best:
+                    best = m
+                if NB.arc(m, pos, n)[1] <= max_arc and (own not in cand or m < cand[own]):
+                    cand[own] = m
+            assert NB.candidates(D, succ, nbr, kinds, max_arc) == (cand, best)
+            assert max_arc > 3 or not cand
+            seen += len(cand)
+    assert seen > 100
+
+
 def test_n_rounds_are_the_sequential_greedy_selection():
     fewer = 0
     for n, seed in itertools.product((12, 30, 60), range(4)):
@@ -162,6 +182,15 @@ def test_every_rewritten_position_and_every_removed_end_lies_inside_the_arc(arc_
             v = int(new[v])
         assert changed <= inside - {start, (start + ln - 1) % n}, m
     assert kinds == {0, 1, 2} and clipped > 0
+
+
+def test_the_arc_lengths_of_arrays_of_moves_are_the_arcs(arc_cases):
+    by_tour = {}
+    for n, succ, pos, m in arc_cases:
+        by_tour.setdefault(n, (pos, []))[1].append(m)
+    for n, (pos, moves) in by_tour.items():
+        got = NB.arc_lens(np.array([m[1] for m in moves]), np.array([m[2] for m in moves], dtype=np.int64), pos, n)
+        assert got.tolist() == [NB.arc(m, pos, n)[1] for m in moves]
 
 
 @pytest.fixture(scope="module")

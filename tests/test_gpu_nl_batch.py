@@ -1,7 +1,9 @@
 """The batched list descent on the device (tsp_dev_nl_3opt_batch) against the CPU reference of the rule in include/tsp_hip.h
 (tests/nl_batch_ref.py): tour, cost and every counter the reference keeps, over arc limits, claim rounds, metrics, sizes from 5
-nodes up, batches of tours, caps that cut a batch, both kind masks; every result is a local optimum of the plain descent and two
-runs return the same bits; a property run at a size without a trajectory reference; the host library's switch."""
+nodes up, batches of tours, caps that cut a batch, both kind masks; every metric with integer and non-integer costs, list widths
+at the edges of the per-node scan's lane deal, a grid of tied deltas; arcs too short for any move give the plain descent; every
+result is a local optimum of the plain descent and two runs return the same bits; a property run at a size without a trajectory
+reference; the host library's switch.  Recorded trajectories at larger sizes: tests/test_gpu_nl_batch_golden.py."""
 import ctypes as C
 
 import numpy as np
@@ -163,6 +165,122 @@ def test_two_hundred_nodes(eng, ctx, max_arc, rounds):
     st = _follows(eng, inst, D, inst.knn(), s0, 7, max_arc, rounds, trace=trace)
     inst.close()
     assert max(len(t) for t in trace) >= 8
+
+
+# ---- 1b. every per-node scan form: metrics, cost types, list widths, ties -----------------------------------------------------------
+
+def _metric_case(eng, ctx, xy, wt, ic, K, settings, kinds_of=(1, 7), seed=0, max_moves=-1, start=None):
+    """the device's matrix and lists against the oracle's first, then the descents from `start` (default: a random tour)"""
+    n = len(xy)
+    D = O.dist_matrix(xy, wt, ic)
+    inst = eng.Instance(ctx, xy, wt, ic)
+    try:
+        assert (inst.dist_matrix()[0] == D).all(), "the distance matrix differs from the oracle's"
+        inst.knn_build(K)
+        nbr = inst.knn()
+        assert (nbr == NL.knn(D, K)).all(), "the lists differ from the reference's"
+        s0 = random_tour(n, np.random.default_rng(seed)) if start is None else start
+        moves = 0
+        for max_arc, rounds in settings:
+            for kinds in kinds_of:
+                moves += _follows(eng, inst, D, nbr, s0, kinds, max_arc, rounds, max_moves=max_moves)["moves"]
+        assert moves > 0
+    finally:
+        inst.close()
+
+
+@pytest.mark.parametrize("ic", [1, 0])
+@pytest.mark.parametrize("wt", ["MAN_2D", "MAX_2D", "CEIL_2D", "EUC_2D", "ATT"])
+def test_every_metric_and_cost_type_follows_the_reference(eng, ctx, wt, ic):
+    """Coordinates with one decimal take the general variants of the per-node scans; with non-integer costs the claim rounds
+    order deltas that differ in their last bits.  CEIL_2D with non-integer costs has an integer-root variant of its own.
+
+    MAN_2D and MAX_2D are |dx| alone (calc_dist's y term is yj - yj), so with non-integer costs nearly every move of this
+    instance has a delta of exactly zero in real arithmetic and of a few 1e-15 either way in fp64.  The rule (delta < 0) then
+    has no end: the reference, batched or plain, runs into a cycle of two tours after 154 to 375 moves and would never return.
+    These two cases are therefore held to the reference over their first 150 moves, through max_moves, instead of to the end."""
+    n = 257
+    rng = np.random.default_rng(257)
+    xy = np.round(rng.uniform(0, 1000, (n, 2)), 1)
+    assert (xy != np.floor(xy)).any()
+    settings = ((16, 2), (n // 2, n))
+    cap = 150 if wt in ("MAN_2D", "MAX_2D") and ic == 0 else -1
+    _metric_case(eng, ctx, xy, O.WTYPE_NAMES[wt], ic, 6, settings, max_moves=cap)
+    if wt == "CEIL_2D" and ic == 0:
+        _metric_case(eng, ctx, rng.integers(0, 1000, (n, 2)).astype(np.float64), O.CEIL_2D, 0, 6, settings)
+
+
+@pytest.mark.parametrize("K", [1, 3, 7, 16])
+def test_list_widths_at_the_edges_of_the_lane_deal(eng, ctx, K):
+    """256 % K lanes of a workgroup idle, K lanes folded per node: 256, 85, 36 and 16 nodes per workgroup, the last one partly
+    filled at n = 257.  The reference's walk over the 3-opt entries costs K * K per decision: the wide lists start from the greedy
+    tour (some 40 moves in 10 to 30 decisions), the narrow ones from a random tour (some 400 in up to 260)."""
+    n = 257
+    assert n % (256 // K) != 0
+    xy = rand_instance(n, seed=257, hi=10000)
+    start = O.greedy(xy, O.EUC_2D)[1] if K >= 7 else None
+    _metric_case(eng, ctx, xy, O.EUC_2D, 1, K, ((0, 0), (16, n)), kinds_of=(7,), seed=K, start=start)
+
+
+def _tied_meeting_candidates(D, start, nbr, kinds, max_arc, trace):
+    """decisions of the trace in which two candidates of equal delta have arcs that meet: the key decides their positions"""
+    succ = np.array(start, dtype=np.int32, copy=True)
+    n = len(succ)
+    hits = 0
+    for moves in trace:
+        cand, _ = NB.candidates(D, succ, nbr, kinds, max_arc)
+        _, _, pos, _ = NB.tour(succ)
+        by_delta = {}
+        for m in set(cand.values()):
+            by_delta.setdefault(m[0], []).append(NB.arc(m, pos, n))
+        hits += any(not NB.disjoint(x, y, n) for arcs in by_delta.values() for q, x in enumerate(arcs) for y in arcs[q + 1:])
+        for m in moves:
+            succ = N3.apply_decision(succ, m, N3.new_counters())
+    return hits
+
+
+def test_tied_deltas_are_claimed_by_key(eng, ctx):
+    n = 200
+    rng = np.random.default_rng(12)
+    xy = rng.integers(0, 12, (n, 2)).astype(np.float64)
+    assert len(np.unique(xy, axis=0)) < n                 # coincident nodes
+    D = O.dist_matrix(xy, O.EUC_2D, 1)
+    inst = eng.Instance(ctx, xy, O.EUC_2D, 1)
+    inst.knn_build(8)
+    nbr = inst.knn()
+    assert (nbr == NL.knn(D, 8)).all()
+    s0 = random_tour(n, rng)
+    tied = 0
+    for rounds in (1, 2, n):
+        trace = []
+        _follows(eng, inst, D, nbr, s0, 7, 0, rounds, trace=trace)
+        tied += _tied_meeting_candidates(D, s0, nbr, 7, n // 2, trace)
+    inst.close()
+    assert tied > 0
+
+
+# ---- 1c. arcs too short for any move ------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("max_arc,rounds", [(1, 1), (2, 2), (3, 5)])
+@pytest.mark.parametrize("name", ["kroA100", "rand2600"])
+def test_arcs_too_short_for_any_move_are_the_plain_descent(eng, ctx, name, max_arc, rounds):
+    """every arc has at least 4 positions: no node has a candidate, every decision is the overall best move"""
+    xy, wt = load_instance(name)
+    n = len(xy)
+    cap = 40 if name == "rand2600" else -1
+    inst = eng.Instance(ctx, xy, wt, 1)
+    inst.knn_build(8)
+    s0 = random_tour(n, np.random.default_rng(n))
+    rc, s, o, st = _run(inst, s0, max_arc=max_arc, rounds=rounds, max_moves=cap)
+    rc1, s1, o1, st1 = inst.nl_3opt(s0, max_moves=cap, time_limit=300.0)
+    inst.close()
+    assert rc == 0 and rc1 == 0
+    assert (s == s1).all() and o == o1 == O.succ_cost(xy, wt, s)
+    for k in COUNTERS:
+        assert st[k] == st1[k], (k, st[k], st1[k])
+    assert st["moves"] > 0 and st["decisions"] == st["moves"] + (0 if cap >= 0 else 1)
+    if cap >= 0:
+        assert st["moves"] == cap
 
 
 # ---- 2. batches of tours, caps, determinism ------------------------------------------------------------------------------------------
