@@ -640,6 +640,45 @@ int tsp_dev_seg_ils3(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_s
                      uint64_t seed, int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial,
                      double time_limit_s, tsp_seg_ils3_stats *stats);
 
+/* ---- windowed iterated local search with groups (extension): several trial groups per window, disjoint commits ---------------
+ * (DESIGN.md 4.22 has the kernels.)  A new rule behind a new entry point: tsp_dev_seg_ils and tsp_dev_seg_ils3 keep their
+ * trajectories.  kinds, windows, anchor, base, kick, A, the repair, the window cost, the accept test, n < 10, the time limit,
+ * the lists and the argument checks are those of tsp_dev_seg_ils3.
+ * Groups G.  1 <= groups <= TSP_SEG_ILS_MAX_GROUPS; groups <= 0: max(1, min(TSP_SEG_ILS_MAX_GROUPS, 1024 / M)), a function of n
+ * and W only (1024 = 256 CUs x the kernel's four resident workgroups), 1 where n < 10; more than TSP_SEG_ILS_MAX_GROUPS:
+ * TSP_DEV_E_ARG, the caller's tours untouched.
+ * Group g, 0 <= g < G, of window w in iteration `it` starts from seq_w as the iteration found it and runs T trials one after
+ * the other, steps 1 - 5 of a trial, with bw = mix(base + 8 + (w G + g) T + t).  What it accepts carries into its own next trial;
+ * no group sees another group.  At the end fin_g is its incumbent window, c_start the window cost of seq_w and c_g that of fin_g.
+ * Offer.  g offers iff it accepted at least one trial; then fin_g != seq_w and c_g < c_start.  lo_g and hi_g are the lowest and
+ * the highest slot at which fin_g differs from seq_w (1 <= lo_g <= hi_g <= W - 2) and gain_g = c_g - c_start, one fp64
+ * subtraction.  The edges g changed are those of the slots lo_g - 1 .. hi_g.
+ * Conflict and commit.  Two offers g and h conflict iff lo_h - 1 <= hi_g and lo_g - 1 <= hi_h.  g loses to h iff they conflict
+ * and (gain_h, h) < (gain_g, g) lexicographically.  g commits iff it offers and loses to no group: the best offer of a window
+ * always commits, and committed groups never conflict pairwise.
+ * New window.  seq_w with, for every committed g, the slots lo_g .. hi_g replaced by those of fin_g; each such interval is a
+ * permutation of itself.  Slots 0 and W - 1 and every successor outside the window stay.  The combined cost is not checked again
+ * (the committed groups share no edge, so every gain is kept).  obj is the recomputed cost of the final tour.
+ * Counters.  Every counter of tsp_seg_ils3_stats, `accepted` included, is the sum over all groups, committed or not;
+ * trials = iterations * M * G * T.  iterations counts the completed iterations (two launches each).
+ * G = 1: the call returns the bits of tsp_dev_seg_ils3 in the tour, the cost and every shared counter, and with kinds inside
+ * TSP_NL_2OPT | TSP_NL_OROPT those of tsp_dev_seg_ils.  Two runs return the same bits, a time-limited run equals a run without a
+ * limit of its completed iterations, and chain b of a batch equals a single call with stream b. */
+#define TSP_SEG_ILS_MAX_GROUPS 64
+typedef struct {
+    int64_t decisions, moves, moves_2opt, moves_oropt, moves_by_len[3], moves_reversed, reversed, deltas_executed;
+    double seconds, device_ms;
+    int64_t iterations, windows, trials, accepted, active_nodes;
+    double start_cost;
+    int64_t moves_3opt, moves_by_type[4]; /* tsp_seg_ils3_stats, in its layout                                                 */
+    int64_t groups;                       /* G                                                                                  */
+    int64_t offers;                       /* groups that ended an iteration with a changed window                               */
+    int64_t commits;                      /* offers written to the tour                                                         */
+} tsp_seg_ils_groups_stats;
+int tsp_dev_seg_ils_groups(tsp_dev_inst *inst, int kinds, int groups, int B, int *succ, int succ_stride, int64_t tour_stride,
+                           double *obj, uint64_t seed, int64_t iterations, int window, int span, int trials,
+                           int64_t max_moves_per_trial, double time_limit_s, tsp_seg_ils_groups_stats *stats);
+
 /* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
  * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
  * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.

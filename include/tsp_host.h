@@ -209,6 +209,10 @@ int HEU_seg_ils_greedy_edge(instance *inst);  /* HEU_greedy_edge, the batched 2-
  * else TSP_DEV_E_ARG and the setting stays.  With TSP_NL_3OPT alg_seg_ils calls tsp_dev_seg_ils3 and the batched descent of
  * HEU_seg_ils_greedy_edge runs over the same kinds; without it alg_seg_ils calls tsp_dev_seg_ils over `kinds`. */
 int tsp_host_set_seg_ils_kinds(int kinds);
+/* Trial groups per window of the two functions above (include/tsp_hip.h, tsp_dev_seg_ils_groups).  1 (the default): alg_seg_ils
+ * makes the calls described above.  0: tsp_dev_seg_ils_groups with the device's default, as many groups as fill the device.
+ * 2 .. TSP_SEG_ILS_MAX_GROUPS: tsp_dev_seg_ils_groups with that many.  Else TSP_DEV_E_ARG and the setting stays. */
+int tsp_host_set_seg_ils_groups(int groups);
 
 /* ---- src/tabusearch.c (externally linked there, not in its header) --------------------------- */
 int alg_2opt_tabu(instance *inst, int *skip_edge, int *stored_prev, const int iter, const int tenure); /* :107 */
@@ -331,6 +335,8 @@ void tsp_host_last_greedy_edge_stats(tsp_greedy_edge_stats *out);
 void tsp_host_last_seg_ils_stats(tsp_seg_ils_stats *out);
 /* ... with the counters of the 3-opt kind behind them (all 0 when the call ran without it). */
 void tsp_host_last_seg_ils3_stats(tsp_seg_ils3_stats *out);
+/* ... and groups, offers and commits behind those (all 0 when the call ran under tsp_host_set_seg_ils_groups(1)). */
+void tsp_host_last_seg_ils_groups_stats(tsp_seg_ils_groups_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */
 void tsp_host_shutdown(void);
 

@@ -205,9 +205,13 @@ struct NlData {
     int bparts = 0;
     // windowed iterated local search (seg_ils.hip), allocated by its first call at this B: accepted trials per chain
     u64 *d_seg_acc = nullptr;
+    // ... with groups: offers and commits per chain (2 x B), and the groups' records, grown to what a call needs (seg_rec_len ints)
+    u64 *d_seg_grp = nullptr;
+    int *d_seg_rec = nullptr;
+    size_t seg_rec_len = 0;
     void free_scratch() {
-        (void)hipFree(d_seg_acc);
-        d_seg_acc = nullptr;
+        (void)hipFree(d_seg_acc); (void)hipFree(d_seg_grp); (void)hipFree(d_seg_rec);
+        d_seg_acc = d_seg_grp = nullptr; d_seg_rec = nullptr; seg_rec_len = 0;
         (void)hipFree(d_st); (void)hipHostFree(h_st); (void)hipFree(d_E); (void)hipFree(d_rem); (void)hipFree(d_cost);
         (void)hipFree(d_part); (void)hipFree(d_inc); (void)hipFree(d_ils); (void)hipHostFree(h_ils);
         d_st = nullptr; h_st = nullptr; d_E = d_rem = d_cost = nullptr; d_part = nullptr; B = 0;

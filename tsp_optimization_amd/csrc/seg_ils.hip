@@ -1,4 +1,5 @@
-// seg_ils.hip -- windowed iterated local search (tsp_dev_seg_ils, tsp_dev_seg_ils3).  The definitions are in include/tsp_hip.h.
+// seg_ils.hip -- windowed iterated local search (tsp_dev_seg_ils, tsp_dev_seg_ils3, tsp_dev_seg_ils_groups).
+// The definitions are in include/tsp_hip.h.
 //
 // Launch   k_seg_ils, one per iteration: grid (windows, chains), one workgroup = the T trials of one window of W consecutive tour
 //          nodes.  The window lives in LDS under "home" ids, the slot a node had when the kernel loaded it: seq (home id per slot),
@@ -10,10 +11,15 @@
 //          rem of an Or-opt segment is taken from E and one distance, in k_nl_prep's order, rather than kept per slot.
 //          With the 3-opt kind (k_seg_ils<.., true>) a decision also deals one lane per (p, u, w) of the active nodes p, and a
 //          3-opt move is the slot permutation of seg_move3.hpp.
+//          With groups (k_seg_ils<.., .., true>, tsp_dev_seg_ils_groups) the grid is (windows * G, chains): workgroup w * G + g runs
+//          the T trials of group g of window w on stream index w * G + g and writes no order / pos.  It leaves a record {offer,
+//          lo, hi, gain; the node ids of slots lo .. hi} in scratch, and k_seg_commit, one workgroup per (window, chain) behind it
+//          on the stream, copies the intervals that commit by the rule of seg_groups.hpp.  No workgroup waits for another.
 // Host     Descent::run queues the launches and looks at the clock between its batches; nothing is read per launch.
 #include "descent.hpp"
 #include "ils_common.hpp"
 #include "nl_common.hpp"
+#include "seg_groups.hpp"
 #include "seg_move3.hpp"
 
 #include <cstddef>
@@ -27,6 +33,9 @@ namespace {
 constexpr int kSegThreads = 256;
 using u16 = unsigned short;
 static_assert(TSP_SEG_ILS_MAX_WINDOW <= 65536, "slots and home ids are 16-bit");
+static_assert(TSP_SEG_ILS_MAX_GROUPS <= 64, "one lane of one wave per group decides a window's commits");
+// a group's record: ints 0 .. 2 = offer, lo, hi, ints 4 .. 5 = gain (fp64), then the node id of slot k at int kSegRecHead + k
+constexpr int kSegRecHead = 8;
 
 __host__ __device__ __forceinline__ int seg_round8(int W) { return (W + 7) & ~7; }
 // entries of the cost tree behind its first level: P / 2, P the next power of two >= W - 1; its bytes also stage a permutation
@@ -216,10 +225,13 @@ struct SegArgs {
     long long cap;   // < 0: none
     u64 seed;
     long long it;
+    int G;      // groups per window (k_seg_ils<.., .., true> and k_seg_commit)
+    int *rec;   // their records: (chain, window, group) major, seg_round8(W) + kSegRecHead ints each
 };
 
 // K3: with the 3-opt kind (tsp_dev_seg_ils3 when kinds has TSP_NL_3OPT); without it no 3-opt code is compiled.
-template <int WT, bool INT, bool K3>
+// GR: a workgroup is one group of a window (tsp_dev_seg_ils_groups): it ends with a record in place of order / pos.
+template <int WT, bool INT, bool K3, bool GR = false>
 __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restrict__ coord, int *__restrict__ orders,
                                                          int *__restrict__ poss, const int *__restrict__ nbr,
                                                          NlState *__restrict__ st, u64 *__restrict__ acc, SegArgs g) {
@@ -227,7 +239,9 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
     __shared__ double s_d[kSegThreads / 64];
     __shared__ u64 s_k[kSegThreads / 64];
     __shared__ int s_na, s_cnt;
-    const int tid = threadIdx.x, wi = blockIdx.x, b = blockIdx.y;
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int sx = blockIdx.x;                 // the index of the workgroup's draws: w, with groups w * G + g
+    const int wi = GR ? sx / g.G : sx;
     const int n = g.n, W = g.W, S = g.S, K = g.K, W8 = seg_round8(W);
     int *order = orders + (size_t)b * n, *pos = poss + (size_t)b * n;
     SegWin w;
@@ -249,6 +263,7 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
     __syncthreads();
     seg_edges<WT, INT>(coord, w, W, 0, W - 2);
     double c0 = seg_cost(w, W);
+    const double c_start = c0;
 
     SegView<WT, INT> view;
     view.coord = coord; view.w = w; view.n = n; view.W = W; view.cnt = 0;
@@ -259,7 +274,7 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
     auto slot_of = [&](int v) { return (int)w.lpos[ahead(pos[v], p0, n)]; };
 
     for (int t = 0; t < g.T; ++t) {
-        const u64 bw = ils_mix(base + 8 + (u64)wi * (u64)g.T + (u64)t);
+        const u64 bw = ils_mix(base + 8 + (u64)sx * (u64)g.T + (u64)t);
         const int off = (int)(ils_mix(bw) % (u64)(W - S));
         const IlsCuts c = ils_cuts_from(0, S, ils_mix(bw + 1), ils_mix(bw + 2), ils_mix(bw + 3), ils_mix(bw + 4));
         const int o[4] = {c.o1, c.o2, c.o3, c.o4};
@@ -417,11 +432,32 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
             seg_edges<WT, INT>(coord, w, W, tlo - 1, thi);
         }
     }
-    if (accepted)
+    if constexpr (GR) {
+        int *rec = g.rec + ((size_t)b * gridDim.x + (size_t)sx) * (size_t)(W8 + kSegRecHead);
+        if (accepted) {
+            // an accepted trial made the window cheaper, so some slot holds another home id than its own
+            if (tid == 0) { s_na = W; s_cnt = -1; }
+            __syncthreads();
+            int lo = W, hi = -1;
+            for (int k = tid; k < W; k += kSegThreads)
+                if (w.inc[k] != k) { lo = min(lo, k); hi = max(hi, k); }
+            if (hi >= 0) { atomicMin(&s_na, lo); atomicMax(&s_cnt, hi); }
+            __syncthreads();
+            lo = s_na; hi = s_cnt;   // 1 <= lo <= hi <= W - 2: no trial permutes slot 0 or W - 1
+            for (int k = lo + tid; k <= hi; k += kSegThreads) rec[kSegRecHead + k] = w.node[w.inc[k]];
+            if (tid == 0) {
+                rec[0] = 1; rec[1] = lo; rec[2] = hi;
+                *reinterpret_cast<double *>(rec + 4) = c0 - c_start;
+            }
+        } else if (tid == 0) {
+            rec[0] = 0;
+        }
+    } else if (accepted) {
         for (int k = tid; k < W; k += kSegThreads) {
             const int v = w.node[w.inc[k]], p = or_wrap(p0 + k, n);
             order[p] = v; pos[v] = p;
         }
+    }
     NlState &Z = st[b];
     auto add = [](long long &to, long long x) { if (x) atomicAdd((unsigned long long *)&to, (unsigned long long)x); };
     if (tid == 0) {
@@ -439,6 +475,47 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
     if ((tid & 63) == 0) add(Z.deltas, (long long)cnt);
 }
 
+// Behind k_seg_ils<.., .., true> on the stream: grid (windows, chains).  One lane per group reads the G headers of the window and
+// decides by seg_groups.hpp; the intervals of the committing groups, pairwise disjoint and each a permutation of itself, go to
+// order / pos.  grp[2 b], grp[2 b + 1]: the chain's offers and commits.
+__global__ __launch_bounds__(kSegThreads) void k_seg_commit(int *__restrict__ orders, int *__restrict__ poss,
+                                                            u64 *__restrict__ grp, SegArgs g) {
+    __shared__ SegOffer s_o[TSP_SEG_ILS_MAX_GROUPS];
+    __shared__ int s_c[TSP_SEG_ILS_MAX_GROUPS];
+    const int tid = threadIdx.x, wi = blockIdx.x, b = blockIdx.y;
+    const int n = g.n, W = g.W, G = g.G;
+    const size_t stride = (size_t)(seg_round8(W) + kSegRecHead);
+    int *order = orders + (size_t)b * n, *pos = poss + (size_t)b * n;
+    const int *recs = g.rec + ((size_t)b * gridDim.x + (size_t)wi) * (size_t)G * stride;
+    if (tid < G) {
+        const int *h = recs + (size_t)tid * stride;
+        SegOffer o;
+        o.offer = h[0]; o.lo = h[1]; o.hi = h[2];
+        o.gain = *reinterpret_cast<const double *>(h + 4);
+        s_o[tid] = o;
+    }
+    __syncthreads();
+    if (tid < G) s_c[tid] = segg_commits(s_o, G, tid) ? 1 : 0;
+    __syncthreads();
+    const int s = (int)(ils_mix(ils_base(g.seed, b, g.it)) % (u64)n);
+    const int p0 = (int)(((long long)pos[s] + (long long)wi * W) % n);   // the anchor is slot 0 of window 0: nobody writes its pos
+    int offers = 0, commits = 0;
+    for (int q = 0; q < G; ++q) {
+        offers += s_o[q].offer;
+        if (!s_c[q]) continue;
+        commits += 1;
+        const int *ids = recs + (size_t)q * stride + kSegRecHead;
+        for (int k = s_o[q].lo + tid; k <= s_o[q].hi; k += kSegThreads) {
+            const int v = ids[k], p = or_wrap(p0 + k, n);
+            order[p] = v; pos[v] = p;
+        }
+    }
+    if (tid == 0) {
+        if (offers) atomicAdd(&grp[2 * b], (u64)offers);
+        if (commits) atomicAdd(&grp[2 * b + 1], (u64)commits);
+    }
+}
+
 // Descent::run ends when every iteration has been queued (and, behind its poll, carried out).
 struct SegHooks : DescentPlain {
     const long long *queued;
@@ -451,14 +528,19 @@ struct SegHooks : DescentPlain {
 static_assert(offsetof(tsp_seg_ils_stats, iterations) == sizeof(tsp_nl_opt_stats), "tsp_seg_ils_stats starts as tsp_nl_opt_stats");
 static_assert(offsetof(tsp_seg_ils3_stats, moves_3opt) == sizeof(tsp_seg_ils_stats), "tsp_seg_ils3_stats starts as tsp_seg_ils_stats");
 
-// What the two entry points do.  `allowed` is the kinds mask the entry point takes; the B records are `stride` bytes apart and
-// start as tsp_seg_ils_stats, with3: they are tsp_seg_ils3_stats.
+static_assert(offsetof(tsp_seg_ils_groups_stats, groups) == sizeof(tsp_seg_ils3_stats),
+              "tsp_seg_ils_groups_stats starts as tsp_seg_ils3_stats");
+
+// What the entry points do.  `allowed` is the kinds mask the entry point takes; the B records are `stride` bytes apart and
+// start as tsp_seg_ils_stats, with3: they are tsp_seg_ils3_stats.  grouped: tsp_dev_seg_ils_groups with its `groups`, the records
+// are tsp_seg_ils_groups_stats.
 static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
                    uint64_t seed, int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial,
-                   double time_limit_s, void *stats, size_t stride, bool with3) {
+                   double time_limit_s, void *stats, size_t stride, bool with3, bool grouped = false, int groups = 1) {
     int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
     if (iterations < 0 || trials < 1) return TSP_DEV_E_ARG;
+    if (grouped && groups > TSP_SEG_ILS_MAX_GROUPS) return TSP_DEV_E_ARG;
     const int n = inst->n;
     const bool none = n < 10;   // no window
     int W = 0, S = 0;
@@ -470,6 +552,8 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
         if (S < 8 || S > W - 1) return TSP_DEV_E_ARG;
     }
     const long long I = none ? 0 : iterations, M = none ? 0 : n / W;
+    // the default fills the 256 CUs x 4 resident workgroups of the kernel; a function of n and W only
+    const long long G = !grouped ? 1 : (groups >= 1 ? groups : (none ? 1 : std::max(1LL, std::min((long long)TSP_SEG_ILS_MAX_GROUPS, 1024 / M))));
     Descent run;
     rc = run.open(inst, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
@@ -480,6 +564,17 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
     tsp_dev_tours *t = run.t;
     if (!x->d_seg_acc) TSP_HIP_TRY(hipMalloc(&x->d_seg_acc, sizeof(u64) * B));
     TSP_HIP_TRY(hipMemsetAsync(x->d_seg_acc, 0, sizeof(u64) * B, s));
+    const size_t rec_len = grouped ? (size_t)B * (size_t)M * (size_t)G * (size_t)(seg_round8(W) + kSegRecHead) : 0;
+    if (grouped) {
+        if (!x->d_seg_grp) TSP_HIP_TRY(hipMalloc(&x->d_seg_grp, sizeof(u64) * 2 * B));
+        TSP_HIP_TRY(hipMemsetAsync(x->d_seg_grp, 0, sizeof(u64) * 2 * B, s));
+        if (rec_len > x->seg_rec_len) {
+            (void)hipFree(x->d_seg_rec);
+            x->d_seg_rec = nullptr; x->seg_rec_len = 0;
+            TSP_HIP_TRY(hipMalloc(&x->d_seg_rec, sizeof(int) * rec_len));
+            x->seg_rec_len = rec_len;
+        }
+    }
     std::vector<double> start((size_t)B);
     if (int e = tsp_grid_tour_cost(t, x->d_cost)) return e;
     TSP_HIP_TRY(hipMemcpyAsync(start.data(), x->d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, s));
@@ -487,6 +582,7 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
     SegArgs g;
     g.n = n; g.K = x->K; g.kinds = kinds; g.W = W; g.S = S; g.T = trials;
     g.cap = max_moves_per_trial < 0 ? -1 : max_moves_per_trial; g.seed = seed; g.it = 0;
+    g.G = (int)G; g.rec = grouped ? x->d_seg_rec : nullptr;
     long long queued = 0;
     SegHooks hooks;
     hooks.queued = &queued; hooks.iterations = I;
@@ -496,28 +592,45 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
                                    if (queued >= I) return;
                                    g.it = queued++;
                                    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-                                       if (kinds & TSP_NL_3OPT)
+                                       if (grouped && (kinds & TSP_NL_3OPT))
+                                           hipLaunchKernelGGL((k_seg_ils<WTC, INTC, true, true>), dim3((unsigned)(M * G), B),
+                                                              dim3(kSegThreads), lds, s, inst->d_coord, t->d_order, t->d_pos, x->d_nbr,
+                                                              x->d_st, x->d_seg_acc, g);
+                                       else if (grouped)
+                                           hipLaunchKernelGGL((k_seg_ils<WTC, INTC, false, true>), dim3((unsigned)(M * G), B),
+                                                              dim3(kSegThreads), lds, s, inst->d_coord, t->d_order, t->d_pos, x->d_nbr,
+                                                              x->d_st, x->d_seg_acc, g);
+                                       else if (kinds & TSP_NL_3OPT)
                                            hipLaunchKernelGGL((k_seg_ils<WTC, INTC, true>), dim3((unsigned)M, B), dim3(kSegThreads), lds,
                                                               s, inst->d_coord, t->d_order, t->d_pos, x->d_nbr, x->d_st, x->d_seg_acc, g);
                                        else
                                            hipLaunchKernelGGL((k_seg_ils<WTC, INTC, false>), dim3((unsigned)M, B), dim3(kSegThreads), lds,
                                                               s, inst->d_coord, t->d_order, t->d_pos, x->d_nbr, x->d_st, x->d_seg_acc, g);
                                    });
+                                   if (grouped)
+                                       hipLaunchKernelGGL(k_seg_commit, dim3((unsigned)M, B), dim3(kSegThreads), 0, s, t->d_order,
+                                                          t->d_pos, x->d_seg_grp, g);
                                },
                                hooks);
     if (status != TSP_OK && status != TSP_TIME_LIMIT_EXCEEDED) return status;
     std::vector<u64> acc((size_t)B, 0);
     TSP_HIP_TRY(hipMemcpy(acc.data(), x->d_seg_acc, sizeof(u64) * B, hipMemcpyDeviceToHost));
+    std::vector<u64> grp((size_t)2 * B, 0);
+    if (grouped) TSP_HIP_TRY(hipMemcpy(grp.data(), x->d_seg_grp, sizeof(u64) * 2 * B, hipMemcpyDeviceToHost));
     const double seconds = wall_s() - run.t0;
     for (int b = 0; b < B && stats; ++b) {
         tsp_seg_ils_stats &o = *reinterpret_cast<tsp_seg_ils_stats *>(static_cast<char *>(stats) + (size_t)b * stride);
         tsp_nl_write_stats(NlStatsOut{&o, sizeof o, 0}, 0, x->h_st[b], nullptr, 0.0, seconds, run.device_ms);
-        o.iterations = queued; o.windows = M; o.trials = queued * M * trials; o.accepted = (int64_t)acc[b];
+        o.iterations = queued; o.windows = M; o.trials = queued * M * G * trials; o.accepted = (int64_t)acc[b];
         o.active_nodes = x->h_st[b].active_nodes; o.start_cost = start[b];
         if (with3) {
             tsp_seg_ils3_stats &o3 = reinterpret_cast<tsp_seg_ils3_stats &>(o);
             o3.moves_3opt = x->h_st[b].moves_3opt;
             for (int k = 0; k < 4; ++k) o3.moves_by_type[k] = x->h_st[b].moves_type[k];
+        }
+        if (grouped) {
+            tsp_seg_ils_groups_stats &og = reinterpret_cast<tsp_seg_ils_groups_stats &>(o);
+            og.groups = G; og.offers = (int64_t)grp[2 * b]; og.commits = (int64_t)grp[2 * b + 1];
         }
     }
     return status;
@@ -537,6 +650,13 @@ int tsp_dev_seg_ils3(tsp_dev_inst *inst, int kinds, int B, int *succ, int succ_s
                      tsp_seg_ils3_stats *stats) {
     return seg_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj, seed, iterations,
                    window, span, trials, max_moves_per_trial, time_limit_s, stats, sizeof *stats, true);
+}
+
+int tsp_dev_seg_ils_groups(tsp_dev_inst *inst, int kinds, int groups, int B, int *succ, int succ_stride, int64_t tour_stride,
+                           double *obj, uint64_t seed, int64_t iterations, int window, int span, int trials,
+                           int64_t max_moves_per_trial, double time_limit_s, tsp_seg_ils_groups_stats *stats) {
+    return seg_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj, seed, iterations,
+                   window, span, trials, max_moves_per_trial, time_limit_s, stats, sizeof *stats, true, true, groups);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ DLB_OFF, DLB_ON, DLB_CLOSE = 0, 1, 2   # don't-look bits of nl_3opt and ils
 NL_BATCH_DEFAULT_ROUNDS = 2            # claim rounds of nl_3opt_batch (TSP_NL_BATCH_DEFAULT_ROUNDS)
 NL_MAX_K, NL_DEFAULT_K = 16, 10
 SEG_ILS_MAX_WINDOW, SEG_ILS_DEFAULT_WINDOW = 2048, 1024   # windows of seg_ils (TSP_SEG_ILS_MAX_WINDOW, _DEFAULT_WINDOW)
+SEG_ILS_MAX_GROUPS = 64                                   # groups per window of seg_ils_groups (TSP_SEG_ILS_MAX_GROUPS)
 HK_DEFAULT_ITERS, HK_DEFAULT_LAMBDA = 300, 2.0
 ALPHA_DEFAULT_K = 5
 
@@ -79,6 +80,10 @@ class SegIlsStats(_Stats):
 
 class SegIls3Stats(_Stats):
     _fields_ = SegIlsStats._fields_ + [("moves_3opt", C.c_int64), ("moves_by_type", C.c_int64 * 4)]
+
+
+class SegIlsGroupsStats(_Stats):
+    _fields_ = SegIls3Stats._fields_ + [("groups", C.c_int64), ("offers", C.c_int64), ("commits", C.c_int64)]
 
 
 class LbStats(_Stats):
@@ -201,6 +206,8 @@ def lib():
         L.tsp_dev_seg_ils.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int64, dp, C.c_uint64, C.c_int64, C.c_int, C.c_int,
                                       C.c_int, C.c_int64, C.c_double, C.POINTER(SegIlsStats)]
         L.tsp_dev_seg_ils3.argtypes = L.tsp_dev_seg_ils.argtypes[:-1] + [C.POINTER(SegIls3Stats)]
+        L.tsp_dev_seg_ils_groups.argtypes = ([vp, C.c_int, C.c_int] + L.tsp_dev_seg_ils.argtypes[2:-1]
+                                             + [C.POINTER(SegIlsGroupsStats)])
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
@@ -238,6 +245,7 @@ EXPORTED = [
     "tsp_dev_nl_3opt_batch",
     "tsp_dev_seg_ils",
     "tsp_dev_seg_ils3",
+    "tsp_dev_seg_ils_groups",
 ]
 
 COMM_ID_BYTES = 128
@@ -547,6 +555,22 @@ class Instance:
         st = (SegIls3Stats * B)()
         rc = lib().tsp_dev_seg_ils3(self._h, int(kinds), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1), int(iterations),
                                     int(window), int(span), int(trials), int(max_moves_per_trial), time_limit, st)
+        return _result(rc, single, succ2, o, st)
+
+    def seg_ils_groups(self, succ, iterations, groups=0, window=0, span=0, trials=1, seed=0, kinds=NL_2OPT | NL_OROPT | NL_3OPT,
+                       max_moves_per_trial=-1, time_limit=-1.0, obj=None):
+        """seg_ils3 with `groups` independent trial groups per window (tsp_dev_seg_ils_groups): every group runs its `trials`
+        trials from the window as the iteration found it, with draws of its own, and the groups whose changed slot intervals
+        do not meet a better one's are all written to the tour.  groups 1 .. SEG_ILS_MAX_GROUPS, 0: as many as fill the device,
+        max(1, min(SEG_ILS_MAX_GROUPS, 1024 / windows)).  Everything else as seg_ils3, the stats with groups, offers and commits
+        behind them and every other counter summed over all groups.  With groups=1 it returns the bits of seg_ils3"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = _obj(obj, B)
+        st = (SegIlsGroupsStats * B)()
+        rc = lib().tsp_dev_seg_ils_groups(self._h, int(kinds), int(groups), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1),
+                                          int(iterations), int(window), int(span), int(trials), int(max_moves_per_trial),
+                                          time_limit, st)
         return _result(rc, single, succ2, o, st)
 
     # -- Held-Karp lower bound (extension) ---------------------------------------------------
