@@ -267,6 +267,13 @@ int tsp_dev_tours_device_ms(tsp_dev_tours *t, double *ms);
 /* Diagnostics: the kernels one GRID-engine step of `mode` launches for this handle, as text (bench.py names the kernel its
  * roofline describes from this; tests check that a switch selected the path they mean to test). */
 int tsp_dev_tours_describe(tsp_dev_tours *t, int mode, char *buf, int cap);
+/* Diagnostics: the LDS engine's kernel body for this instance and `mode`, as one line of text such as
+ *   k_lds_two_opt<EUC_2D_ICOORD, FIRST, cache=1, f32=1> lds=63120 of 163840
+ * -- the metric variant, the rule, whether the edge-length cache and the fp32 first tier are compiled in (TSP_LDS_EDGE_CACHE,
+ * TSP_LDS_F32_MIN_N and the fit of the cache decide, as they stood when the handle was created), the dynamic LDS a launch asks
+ * for and the LDS a workgroup may be granted.  TSP_DEV_E_ARG when the instance does not fit the LDS engine at all.  Tests check
+ * with it that a switch selected the body they mean to test. */
+int tsp_dev_inst_lds_variant(tsp_dev_inst *inst, int mode, char *buf, int cap);
 /* min over tours of (cost, tour index) packed as (int64(cost) << 24 | index); the value the
  * multi-start all-reduce(min) combines across ranks.  true_cost != 0 recomputes the cost from
  * the tour (GRASP's reported value carries an offset).  Written to *packed. */

@@ -12,6 +12,7 @@
 // block and evaluate it against the row records (LDS broadcast).  The winner is a block arg-min;
 // the move is a parallel swap loop on the LDS arrays.
 #include "two_opt_common.hpp"
+#include "lds_layout.hpp"
 
 #include <algorithm>
 
@@ -30,12 +31,11 @@ __device__ unsigned long long g_lds_scan[8];   // tour 0, thread 0: cycles deriv
 constexpr int kLdsThreads = 512;
 constexpr int kLdsRows = 32;
 using idx_t = unsigned short;
+static_assert(kLdsRows == kLdsLayoutRows && sizeof(NodeRec) == kLdsRowRecBytes && sizeof(double2) == kLdsCoordBytes && sizeof(idx_t) == kLdsIdxBytes &&
+              sizeof(float) == kLdsEdgeBytes && sizeof(float4) == kLdsRowFloatBytes, "lds_layout.hpp describes these types");
 
-__host__ __device__ inline size_t lds_bytes_needed(int n, bool edge_cache = false) {
-    // rows | coord | order | pos | (edge lengths by position) | reduction scratch
-    return sizeof(NodeRec) * kLdsRows + sizeof(double2) * (size_t)n + 2 * sizeof(idx_t) * (size_t)n +
-           (edge_cache ? sizeof(float) * (size_t)n + 16 : 0) + 1024 + 512;   // + the rows' float records (fp32 first tier)
-}
+// what a launch asks for: the total of the layout the kernel takes its pointers from (lds_layout.hpp)
+inline size_t lds_bytes_needed(int n, bool edge_cache = false) { return lds_layout(n, edge_cache).total; }
 
 // Node record from the LDS arrays.  CACHE: d(v, succ v) is dsp[pos v] -- the tour's edge lengths by position, kept
 // as floats (integer costs < 2^24 on the integer-coordinate variants, exact), so that a step derives thousands of
@@ -63,17 +63,13 @@ __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__re
                                                              int rmax, int max_iters, double margin, double prune,
                                                              int probe, double org_x, double org_y) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    NodeRec *s_rows = reinterpret_cast<NodeRec *>(smem);
-    double2 *coord = reinterpret_cast<double2 *>(smem + sizeof(NodeRec) * kLdsRows);
-    idx_t *order = reinterpret_cast<idx_t *>(coord + n);
-    idx_t *pos = order + n;
-    char *scratch = reinterpret_cast<char *>(pos + n);
-    scratch += (16 - (reinterpret_cast<size_t>(scratch) & 15)) & 15;
-    float *dsp = reinterpret_cast<float *>(scratch);   // CACHE: edge length leaving tour position p
-    if constexpr (CACHE) {
-        scratch += sizeof(float) * (size_t)n;
-        scratch += (16 - (reinterpret_cast<size_t>(scratch) & 15)) & 15;
-    }
+    const LdsLayout lay = lds_layout(n, CACHE);   // the same carve-up the launch sized (lds_bytes_needed)
+    NodeRec *s_rows = reinterpret_cast<NodeRec *>(smem + lay.rows);
+    double2 *coord = reinterpret_cast<double2 *>(smem + lay.coord);
+    idx_t *order = reinterpret_cast<idx_t *>(smem + lay.order);
+    idx_t *pos = reinterpret_cast<idx_t *>(smem + lay.pos);
+    float *dsp = reinterpret_cast<float *>(smem + lay.dsp);   // CACHE: edge length leaving tour position p
+    char *scratch = smem + lay.scratch;
     double *s_d = reinterpret_cast<double *>(scratch);            // 16
     u64 *s_k = reinterpret_cast<u64 *>(scratch + 128);            // 16
     long long *s_ll = reinterpret_cast<long long *>(scratch + 256);  // 16
@@ -81,7 +77,7 @@ __global__ __launch_bounds__(kLdsThreads) void k_lds_two_opt(const double2 *__re
     int4 *s_win = reinterpret_cast<int4 *>(scratch + 384);        // 8 (FIRST, the probe's vote): shares the chunk, which only BEST uses
     int *s_flag = reinterpret_cast<int *>(scratch + 384 + 384);   // FIRST: second probe round
     int *s_vote = reinterpret_cast<int *>(scratch + 384 + 384 + 8);   // FIRST, scan: two words, the stamp of the last vote (by parity) that saw a hit in the block's first row
-    float4 *s_rowsf = reinterpret_cast<float4 *>(scratch + 1024);  // x, y (relative to the instance corner), edge length of the block's rows as floats
+    float4 *s_rowsf = reinterpret_cast<float4 *>(smem + lay.rowsf);  // x, y (relative to the instance corner), edge length of the block's rows as floats
     // Integer coordinates of bounded span are exact as floats relative to the instance corner: the new-edge bound runs in fp32
     // first (its rounding paid for in slack: s may come out 2^-22 low, T -- below 2^23 -- is taken 2 units high), four rows per
     // trip, before the row's full record and the fp64 tiers are looked at -- as in the CLUSTER engine's tiles scan
@@ -649,20 +645,31 @@ hipError_t launch_lds_k(tsp_dev_tours *t, int rmin, int rmax, int max_iters) {
     return hipGetLastError();
 }
 
+// Which kernel body a handle's instance gets (per rule: FIRST or BEST): the one place that decides it.  The integer-coordinate
+// variants (integer edge lengths < 2^21, exact as floats) may keep the edge-length cache, while its layout fits the CU's LDS and
+// TSP_LDS_EDGE_CACHE does not turn it off, and run the fp32 first tier of the rows x columns scan from TSP_LDS_F32_MIN_N nodes on.
+constexpr bool lds_can_cache(int wt) { return wt == WT_EUC_2D_ICOORD || wt == WT_CEIL_2D_ICOORD || wt == WT_ATT_ICOORD; }
+struct LdsVariant { bool cache, f32; };
+LdsVariant lds_variant(const tsp_dev_inst *inst) {
+    LdsVariant v{false, false};
+    if (!lds_can_cache(inst->wtype)) return v;
+    v.f32 = inst->n >= TSP_SW(inst, LDS_F32_MIN_N, 2500);
+    v.cache = lds_bytes_needed(inst->n, true) <= (size_t)inst->ctx->lds_bytes && TSP_SW(inst, LDS_EDGE_CACHE, 1);
+    return v;
+}
+
 template <int WT, bool INT>
 hipError_t launch_lds(tsp_dev_tours *t, int mode, int rmin, int rmax, int max_iters) {
-    // integer-coordinate variants: integer edge lengths < 2^21, exact as floats
-    constexpr bool CAN_CACHE = WT == WT_EUC_2D_ICOORD || WT == WT_CEIL_2D_ICOORD || WT == WT_ATT_ICOORD;
-    if constexpr (CAN_CACHE) {
-        const bool f32 = t->n >= TSP_SW(t->inst, LDS_F32_MIN_N, 2500);   // the fp32 first tier of the rows x columns scan
-        if (lds_bytes_needed(t->n, true) <= (size_t)t->inst->ctx->lds_bytes && TSP_SW(t->inst, LDS_EDGE_CACHE, 1)) {
-            if (f32) return mode == TSP_2OPT_FIRST ? launch_lds_k<WT, INT, TSP_2OPT_FIRST, true, true>(t, rmin, rmax, max_iters)
-                                                   : launch_lds_k<WT, INT, TSP_2OPT_BEST, true, true>(t, rmin, rmax, max_iters);
+    if constexpr (lds_can_cache(WT)) {
+        const LdsVariant v = lds_variant(t->inst);
+        if (v.cache) {
+            if (v.f32) return mode == TSP_2OPT_FIRST ? launch_lds_k<WT, INT, TSP_2OPT_FIRST, true, true>(t, rmin, rmax, max_iters)
+                                                     : launch_lds_k<WT, INT, TSP_2OPT_BEST, true, true>(t, rmin, rmax, max_iters);
             return mode == TSP_2OPT_FIRST ? launch_lds_k<WT, INT, TSP_2OPT_FIRST, true, false>(t, rmin, rmax, max_iters)
                                           : launch_lds_k<WT, INT, TSP_2OPT_BEST, true, false>(t, rmin, rmax, max_iters);
         }
-        if (f32) return mode == TSP_2OPT_FIRST ? launch_lds_k<WT, INT, TSP_2OPT_FIRST, false, true>(t, rmin, rmax, max_iters)
-                                               : launch_lds_k<WT, INT, TSP_2OPT_BEST, false, true>(t, rmin, rmax, max_iters);
+        if (v.f32) return mode == TSP_2OPT_FIRST ? launch_lds_k<WT, INT, TSP_2OPT_FIRST, false, true>(t, rmin, rmax, max_iters)
+                                                 : launch_lds_k<WT, INT, TSP_2OPT_BEST, false, true>(t, rmin, rmax, max_iters);
     }
     return mode == TSP_2OPT_FIRST ? launch_lds_k<WT, INT, TSP_2OPT_FIRST, false, false>(t, rmin, rmax, max_iters)
                                   : launch_lds_k<WT, INT, TSP_2OPT_BEST, false, false>(t, rmin, rmax, max_iters);
@@ -686,6 +693,15 @@ extern "C" int tsp_dev_debug_lds_scan(unsigned long long *out8) {
 
 bool tsp_lds_fits(const tsp_dev_inst *inst) {
     return inst && inst->n <= 65535 && lds_bytes_needed(inst->n) <= (size_t)inst->ctx->lds_bytes;
+}
+
+int tsp_dev_inst_lds_variant(tsp_dev_inst *inst, int mode, char *buf, int cap) {
+    if (!inst || !buf || cap < 1 || (mode != TSP_2OPT_FIRST && mode != TSP_2OPT_BEST) || !tsp_lds_fits(inst)) return TSP_DEV_E_ARG;
+    static const char *const names[] = {"EUC_2D", "MAX_2D", "MAN_2D", "CEIL_2D", "GEO", "ATT", "EUC_2D_ICOORD", "CEIL_2D_ICOORD", "ATT_ICOORD"};
+    const LdsVariant v = lds_variant(inst);
+    snprintf(buf, (size_t)cap, "k_lds_two_opt<%s, %s, cache=%d, f32=%d> lds=%zu of %d", names[inst->wtype],
+             mode == TSP_2OPT_FIRST ? "FIRST" : "BEST", v.cache ? 1 : 0, v.f32 ? 1 : 0, lds_bytes_needed(inst->n, v.cache), inst->ctx->lds_bytes);
+    return TSP_OK;
 }
 
 // Runs the tours of `t` to their local optima with the LDS engine (launches of bounded length so

@@ -170,6 +170,7 @@ def lib():
         L.tsp_dev_tours_restore.argtypes = [vp]
         L.tsp_dev_tours_time_scan.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
         L.tsp_dev_tours_describe.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
+        L.tsp_dev_inst_lds_variant.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
         L.tsp_dev_tours_device_ms.argtypes = [vp, C.POINTER(C.c_double)]
         L.tsp_dev_tours_best.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
         L.tsp_dev_comm_last_error.restype = C.c_char_p
@@ -246,6 +247,7 @@ EXPORTED = [
     "tsp_dev_seg_ils",
     "tsp_dev_seg_ils3",
     "tsp_dev_seg_ils_groups",
+    "tsp_dev_inst_lds_variant",
 ]
 
 COMM_ID_BYTES = 128
@@ -382,6 +384,12 @@ class Instance:
         """The kernel and variant that construct(kind, ...) launches for this instance, as text"""
         buf = C.create_string_buffer(256)
         _check(lib().tsp_dev_construct_describe(self._h, kind, buf, 256))
+        return buf.value.decode()
+
+    def lds_variant(self, mode):
+        """The LDS engine's kernel body for this instance and `mode`, as text; TspDeviceError when the instance does not fit it"""
+        buf = C.create_string_buffer(256)
+        _check(lib().tsp_dev_inst_lds_variant(self._h, mode, buf, 256))
         return buf.value.decode()
 
     def extramileage(self):
