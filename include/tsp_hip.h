@@ -686,6 +686,55 @@ int tsp_dev_seg_ils_groups(tsp_dev_inst *inst, int kinds, int groups, int B, int
                            double *obj, uint64_t seed, int64_t iterations, int window, int span, int trials,
                            int64_t max_moves_per_trial, double time_limit_s, tsp_seg_ils_groups_stats *stats);
 
+/* ---- windowed iterated local search with Lin-Kernighan chains (extension): a fourth kind of the window repair ------------------
+ * (DESIGN.md 4.23 has the kernel.)  A new kind behind a new entry point: tsp_dev_seg_ils, tsp_dev_seg_ils3, tsp_dev_seg_ils_groups
+ * and tsp_host_set_seg_ils_kinds keep refusing TSP_NL_LK and keep their trajectories.  kinds: any non-empty subset of TSP_NL_2OPT |
+ * TSP_NL_OROPT | TSP_NL_3OPT | TSP_NL_LK.  lk_depth D: 1 <= D <= TSP_SEG_LK_MAX_DEPTH; lk_depth <= 0: TSP_SEG_LK_DEFAULT_DEPTH; more
+ * than TSP_SEG_LK_MAX_DEPTH: TSP_DEV_E_ARG, the caller's tours untouched.  Everything else -- windows, anchor, draws, kick, A, the
+ * accept test, the window cost, groups / offers / commits, the time limit, n < 10, the lists, the argument checks -- is the text of
+ * tsp_dev_seg_ils_groups.  Without TSP_NL_LK the call returns the bits of tsp_dev_seg_ils_groups in the tour, the cost and every
+ * shared counter.
+ * Chain.  For a window node t1 at slot i and a side s in {0, 1}; written for s = 0, side 1 is the same text on the window read
+ * backwards (slot k <-> W - 1 - k).  It needs i <= W - 2.  It works on a private image cur of the window path and touches nothing
+ * else.  Start with G = +0.0, best = +0.0, h* = 0, used = {}.  Step h = 1 .. D:
+ *   e = cur[i + 1], and x = d(t1, e).
+ *   A list entry y = nbr[e][k], k = 0 .. K - 1, is admissible when all of these hold: y != e; y is a window node at slot j of cur
+ *   with i + 3 <= j <= W - 1; y is not in used; g1 = (G + x) - d(e, y) > best.
+ *   For an admissible entry, p = cur[j - 1] and g2 = g1 + d(p, y).
+ *   The step takes the admissible entry of largest g2, lowest k on ties.  Without one the chain ends.
+ *   It reverses slots i + 1 .. j - 1 of cur.  used gains e and y, and e_h, y_h, p_h = e, y, p.
+ *   G = g2 - d(p, t1).  If G > best, then best = G and h* = h.
+ * Every d takes the lower node id first.  All sums are fp64 in the written order, with contraction off.
+ * The chain offers iff h* >= 1.  Then the move is the first h* reversals; delta = -best; its kind index is 3, the last in the order
+ * (delta, kind, key), so a chain loses ties to every other kind; key = 2 t1 + s; ends(m) = {t1} and e_h, y_h, p_h for h <= h*.
+ * All removed edges are window edges and only slots inside 1 .. W - 2 move, so the move is a window move.  Its hull lo .. hi is
+ * that of its reversals.
+ * Decision.  With TSP_NL_LK every v in A also runs chain(v, 0) and chain(v, 1) on the window as the decision found it.  v gets a
+ * hit if either chain offers.  The decision applies the best (delta, kind, key) over all kinds.  A becomes the nodes with a hit
+ * plus ends(m), as before.  An applied chain counts as one move against max_moves_per_trial.
+ * Counters.  tsp_seg_ils_lk_stats is tsp_seg_ils_groups_stats in its layout followed by lk_depth and four counters summed over
+ * all trials and groups like the others.  An applied chain adds to moves, moves_lk and lk_flips and to nothing else: `reversed`
+ * stays the count of the 2-opt moves. */
+enum { TSP_NL_LK = 8 }; /* kinds mask of tsp_dev_seg_ils_lk, beside TSP_NL_2OPT, TSP_NL_OROPT and TSP_NL_3OPT */
+#define TSP_SEG_LK_MAX_DEPTH 16    /* steps of a chain at most: what a chain's record in LDS holds                              */
+#define TSP_SEG_LK_DEFAULT_DEPTH 16 /* the lowest cost after 10 s at n = 100 003, W = 1024                   */
+typedef struct {
+    int64_t decisions, moves, moves_2opt, moves_oropt, moves_by_len[3], moves_reversed, reversed, deltas_executed;
+    double seconds, device_ms;
+    int64_t iterations, windows, trials, accepted, active_nodes;
+    double start_cost;
+    int64_t moves_3opt, moves_by_type[4];
+    int64_t groups, offers, commits; /* tsp_seg_ils_groups_stats, in its layout                                                */
+    int64_t lk_depth;                /* the D used                                                                             */
+    int64_t moves_lk;                /* applied chains                                                                         */
+    int64_t lk_flips;                /* the sum of h* over the applied chains                                                  */
+    int64_t lk_chains;               /* pairs (v, s), v in A, that have a first edge                                           */
+    int64_t lk_steps;                /* reversals made by all chains, kept or not                                              */
+} tsp_seg_ils_lk_stats;
+int tsp_dev_seg_ils_lk(tsp_dev_inst *inst, int kinds, int lk_depth, int groups, int B, int *succ, int succ_stride,
+                       int64_t tour_stride, double *obj, uint64_t seed, int64_t iterations, int window, int span, int trials,
+                       int64_t max_moves_per_trial, double time_limit_s, tsp_seg_ils_lk_stats *stats);
+
 /* ---- Held-Karp lower bound (extension): minimum 1-trees under node penalties, driven by subgradient ascent -------------------
  * (The reference bounds its tours with CPLEX models, which are out of scope here; DESIGN.md 4.12 has the kernels and times.)
  * d(i,j) is the value tsp_dev_dist_pairs returns; the penalties are pi[0 .. n-1], fp64.

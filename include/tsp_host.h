@@ -213,6 +213,11 @@ int tsp_host_set_seg_ils_kinds(int kinds);
  * makes the calls described above.  0: tsp_dev_seg_ils_groups with the device's default, as many groups as fill the device.
  * 2 .. TSP_SEG_ILS_MAX_GROUPS: tsp_dev_seg_ils_groups with that many.  Else TSP_DEV_E_ARG and the setting stays. */
 int tsp_host_set_seg_ils_groups(int groups);
+/* Lin-Kernighan chains in the repair of the two functions above (include/tsp_hip.h, tsp_dev_seg_ils_lk).  0 (the default): off,
+ * alg_seg_ils makes the calls described above.  1 .. TSP_SEG_LK_MAX_DEPTH: alg_seg_ils calls tsp_dev_seg_ils_lk with the kinds set
+ * above plus TSP_NL_LK, that depth and the groups set above.  -1: the same with TSP_SEG_LK_DEFAULT_DEPTH.  Else TSP_DEV_E_ARG and the
+ * setting stays.  The batched descent of HEU_seg_ils_greedy_edge is not changed by it. */
+int tsp_host_set_seg_ils_lk(int depth);
 
 /* ---- src/tabusearch.c (externally linked there, not in its header) --------------------------- */
 int alg_2opt_tabu(instance *inst, int *skip_edge, int *stored_prev, const int iter, const int tenure); /* :107 */
@@ -337,6 +342,8 @@ void tsp_host_last_seg_ils_stats(tsp_seg_ils_stats *out);
 void tsp_host_last_seg_ils3_stats(tsp_seg_ils3_stats *out);
 /* ... and groups, offers and commits behind those (all 0 when the call ran under tsp_host_set_seg_ils_groups(1)). */
 void tsp_host_last_seg_ils_groups_stats(tsp_seg_ils_groups_stats *out);
+/* ... and the chain counters behind those (all 0 when the call ran under tsp_host_set_seg_ils_lk(0)). */
+void tsp_host_last_seg_ils_lk_stats(tsp_seg_ils_lk_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */
 void tsp_host_shutdown(void);
 

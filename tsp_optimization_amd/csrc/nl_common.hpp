@@ -209,9 +209,11 @@ struct NlData {
     u64 *d_seg_grp = nullptr;
     int *d_seg_rec = nullptr;
     size_t seg_rec_len = 0;
+    // ... with the chain kind: its four counters per chain (4 x B)
+    u64 *d_seg_lk = nullptr;
     void free_scratch() {
-        (void)hipFree(d_seg_acc); (void)hipFree(d_seg_grp); (void)hipFree(d_seg_rec);
-        d_seg_acc = d_seg_grp = nullptr; d_seg_rec = nullptr; seg_rec_len = 0;
+        (void)hipFree(d_seg_acc); (void)hipFree(d_seg_grp); (void)hipFree(d_seg_rec); (void)hipFree(d_seg_lk);
+        d_seg_acc = d_seg_grp = d_seg_lk = nullptr; d_seg_rec = nullptr; seg_rec_len = 0;
         (void)hipFree(d_st); (void)hipHostFree(h_st); (void)hipFree(d_E); (void)hipFree(d_rem); (void)hipFree(d_cost);
         (void)hipFree(d_part); (void)hipFree(d_inc); (void)hipFree(d_ils); (void)hipHostFree(h_ils);
         d_st = nullptr; h_st = nullptr; d_E = d_rem = d_cost = nullptr; d_part = nullptr; B = 0;

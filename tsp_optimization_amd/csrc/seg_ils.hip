@@ -1,4 +1,5 @@
-// seg_ils.hip -- windowed iterated local search (tsp_dev_seg_ils, tsp_dev_seg_ils3, tsp_dev_seg_ils_groups).
+// seg_ils.hip -- windowed iterated local search (tsp_dev_seg_ils, tsp_dev_seg_ils3, tsp_dev_seg_ils_groups, tsp_dev_seg_ils_lk;
+// DESIGN.md 4.20 - 4.23).
 // The definitions are in include/tsp_hip.h.
 //
 // Launch   k_seg_ils, one per iteration: grid (windows, chains), one workgroup = the T trials of one window of W consecutive tour
@@ -15,11 +16,15 @@
 //          the T trials of group g of window w on stream index w * G + g and writes no order / pos.  It leaves a record {offer,
 //          lo, hi, gain; the node ids of slots lo .. hi} in scratch, and k_seg_commit, one workgroup per (window, chain) behind it
 //          on the stream, copies the intervals that commit by the rule of seg_groups.hpp.  No workgroup waits for another.
+//          With the chain kind (k_seg_ils<.., true, true, true>, tsp_dev_seg_ils_lk when kinds has TSP_NL_LK) a decision also runs
+//          the two chains of every active node, one chain per group of 16 lanes and 16 chains side by side; a chain is the list
+//          of its reversals (seg_lk.hpp) in 128 bytes of LDS, and the chain that wins is one slot permutation of its hull.
 // Host     Descent::run queues the launches and looks at the clock between its batches; nothing is read per launch.
 #include "descent.hpp"
 #include "ils_common.hpp"
 #include "nl_common.hpp"
 #include "seg_groups.hpp"
+#include "seg_lk.hpp"
 #include "seg_move3.hpp"
 
 #include <cstddef>
@@ -36,6 +41,11 @@ static_assert(TSP_SEG_ILS_MAX_WINDOW <= 65536, "slots and home ids are 16-bit");
 static_assert(TSP_SEG_ILS_MAX_GROUPS <= 64, "one lane of one wave per group decides a window's commits");
 // a group's record: ints 0 .. 2 = offer, lo, hi, ints 4 .. 5 = gain (fp64), then the node id of slot k at int kSegRecHead + k
 constexpr int kSegRecHead = 8;
+// a chain's key: both kind bits above 2 t1 + s, so that a chain is the last kind in the order (delta, kind, key)
+constexpr u64 kSegLkBits = kNlOrBit | kNl3Bit;
+constexpr int kSegLkGroups = kSegThreads / kSegLkLanes;          // chains side by side
+constexpr int kSegLkRec = kSegLkMaxDepth + 3 * kSegLkMaxDepth;   // a chain in LDS: its j, then e, y, p of every step (home ids)
+static_assert(kSegLkMaxDepth == TSP_SEG_LK_MAX_DEPTH && kSegLkLanes == TSP_NL_MAX_K, "seg_lk.hpp follows include/tsp_hip.h");
 
 __host__ __device__ __forceinline__ int seg_round8(int W) { return (W + 7) & ~7; }
 // entries of the cost tree behind its first level: P / 2, P the next power of two >= W - 1; its bytes also stage a permutation
@@ -178,6 +188,52 @@ struct SegView {
     }
 };
 
+// What a chain (seg_lk.hpp) reads the window through, in home ids.
+template <int WT, bool INT>
+struct SegLkView {
+    const double2 *coord;
+    const int *nbr, *pos;
+    SegWin w;
+    int n, W, K, p0;
+
+    __device__ __forceinline__ int entry(int e, int k) const {
+        const int hu = ahead(pos[nbr[(size_t)w.node[e] * K + k]], p0, n);
+        return hu < W ? hu : -1;
+    }
+    __device__ __forceinline__ int slot(int id) const { return w.lpos[id]; }
+    __device__ __forceinline__ int at(int p) const { return w.seq[p]; }
+    __device__ __forceinline__ double d(int a, int b) const { return dsym<WT, INT>(coord, w.node[a], w.node[b]); }
+};
+
+// chain(r, s) of at most D steps by the kSegLkLanes lanes of a group: lane gl tests entry gl of a step, the group folds by
+// (g2, k), and every lane carries the chain on.  rec: the group's kSegLkRec ids, written by all its lanes with the same values.
+// -> false: r has no first edge on this side.
+template <typename V>
+__device__ __forceinline__ bool seg_lk_chain(const V &v, int r, int s, int D, u16 *rec, int gl, SegLkChain &c) {
+    const int i = seglk_side(s, v.W, v.slot(r));
+    seglk_begin(c, 0);
+    if (i > v.W - 2) return false;
+    c.e = v.at(seglk_side(s, v.W, i + 1));
+    u16 *js = rec, *es = rec + kSegLkMaxDepth;
+    while (c.h < D) {
+        const double x = v.d(r, c.e);
+        SegLkPick pk;
+        pk.g2 = -INFINITY; pk.k = kSegLkLanes; pk.j = 0; pk.y = 0; pk.p = 0;
+        if (gl < v.K) pk = seglk_entry(v, s, i, js, es, c, x, gl);
+        SegLkPick win = pk;
+#pragma unroll
+        for (int m = kSegLkLanes / 2; m >= 1; m >>= 1) {
+            const double og = __shfl_xor(win.g2, m, kSegLkLanes);
+            const int ok = __shfl_xor(win.k, m, kSegLkLanes);
+            if (seglk_beats(og, ok, win.g2, win.k)) { win.g2 = og; win.k = ok; }
+        }
+        if (win.k >= kSegLkLanes) break;
+        win.j = __shfl(pk.j, win.k, kSegLkLanes); win.y = __shfl(pk.y, win.k, kSegLkLanes); win.p = __shfl(pk.p, win.k, kSegLkLanes);
+        seglk_take(c, win, v.d(win.p, r), js, es);
+    }
+    return true;
+}
+
 // Slots lo .. hi take the home ids of the slots src(k), a permutation of lo .. hi.  By every thread; `stage` holds hi - lo + 1 ids.
 template <typename Src>
 __device__ __forceinline__ void seg_permute(const SegWin &w, u16 *stage, int lo, int hi, Src src) {
@@ -226,12 +282,15 @@ struct SegArgs {
     u64 seed;
     long long it;
     int G;      // groups per window (k_seg_ils<.., .., true> and k_seg_commit)
+    int D;      // steps of a chain at most (k_seg_ils<.., .., .., true>)
     int *rec;   // their records: (chain, window, group) major, seg_round8(W) + kSegRecHead ints each
+    u64 *lk;    // the chain kind's counters, four per tsp chain: moves, flips, chains, steps
 };
 
 // K3: with the 3-opt kind (tsp_dev_seg_ils3 when kinds has TSP_NL_3OPT); without it no 3-opt code is compiled.
 // GR: a workgroup is one group of a window (tsp_dev_seg_ils_groups): it ends with a record in place of order / pos.
-template <int WT, bool INT, bool K3, bool GR = false>
+// LK: with the chain kind (tsp_dev_seg_ils_lk when kinds has TSP_NL_LK); without it no chain code is compiled.
+template <int WT, bool INT, bool K3, bool GR = false, bool LK = false>
 __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restrict__ coord, int *__restrict__ orders,
                                                          int *__restrict__ poss, const int *__restrict__ nbr,
                                                          NlState *__restrict__ st, u64 *__restrict__ acc, SegArgs g) {
@@ -251,6 +310,13 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
     w.alist = w.lpos + W8;
     w.act = reinterpret_cast<unsigned char *>(w.alist + 2 * W8); w.hit = w.act + W8;
     u16 *stage = reinterpret_cast<u16 *>(w.tree);
+    u16 *lk_rec = nullptr;   // LK: kSegLkRec ids per group of lanes; the chain that is applied is worked out again into the first
+    int *lk_h = nullptr;     // LK: its best prefix
+    if constexpr (LK) {
+        __shared__ u16 s_lk[kSegLkGroups * kSegLkRec];
+        __shared__ int s_lkh;
+        lk_rec = s_lk; lk_h = &s_lkh;
+    }
 
     const u64 base = ils_base(g.seed, b, g.it);
     const int s = (int)(ils_mix(base) % (u64)n);
@@ -270,6 +336,10 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
     // the same values in every thread; thread 0 adds them to the chain's
     long long decisions = 0, moves_all = 0, m2 = 0, mor = 0, ml1 = 0, ml2 = 0, ml3 = 0, mrev = 0, reversed = 0, active = 0, accepted = 0;
     long long m3 = 0, mt[4] = {0, 0, 0, 0};   // K3
+    long long mlk = 0, flips = 0;             // LK
+    unsigned lk_chains = 0, lk_steps = 0;     // LK: of the chains this thread led
+    SegLkView<WT, INT> lkv;
+    if constexpr (LK) { lkv.coord = coord; lkv.nbr = nbr; lkv.pos = pos; lkv.w = w; lkv.n = n; lkv.W = W; lkv.K = K; lkv.p0 = p0; }
     // the slot of a window node
     auto slot_of = [&](int v) { return (int)w.lpos[ahead(pos[v], p0, n)]; };
 
@@ -344,6 +414,23 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
                         if (view.found) w.hit[r] = 1;
                     }
             }
+            if constexpr (LK) {
+                // chain 2 q + s is chain(list[q], s); kSegLkGroups of them at a time, the leader of a group reports
+                if (g.kinds & TSP_NL_LK)
+                    for (int c = tid / kSegLkLanes; c < 2 * na; c += kSegLkGroups) {
+                        const int r = list[c >> 1], s = c & 1;
+                        SegLkChain ch;
+                        const bool first = seg_lk_chain(lkv, r, s, g.D, lk_rec + (tid / kSegLkLanes) * kSegLkRec, tid % kSegLkLanes, ch);
+                        if (tid % kSegLkLanes == 0 && first) {
+                            lk_chains += 1; lk_steps += (unsigned)ch.h;
+                            if (ch.hstar >= 1) {
+                                w.hit[r] = 1;
+                                const u64 key = kSegLkBits | (2 * (u64)w.node[r] + (u64)s);
+                                if (better(-ch.best, key, view.bd, view.bk)) { view.bd = -ch.best; view.bk = key; }
+                            }
+                        }
+                    }
+            }
             double bd = view.bd;
             u64 bk = view.bk;
             block_argmin<true>(bd, bk, s_d, s_k);   // (its barriers also stand between the hit flags and their readers)
@@ -352,8 +439,31 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
             int lo, hi;
             bool is3 = false;
             SegMove3 mv3 = {0, 0, 0, 0};
-            if constexpr (K3) is3 = (bk & kNl3Bit) != 0;
-            if (is3) {
+            bool isLK = false;
+            int lkS = 0, lkI = 0, lkH = 0, lkR = 0;   // LK: the side, t1's chain slot, the best prefix, t1's home id
+            if constexpr (LK) isLK = (bk & kSegLkBits) == kSegLkBits;
+            if constexpr (K3) is3 = (bk & kNl3Bit) != 0 && !isLK;
+            if constexpr (LK) {
+                if (isLK) {
+                    lkS = (int)(bk & 1);
+                    lkR = ahead(pos[(int)((bk & (kNlOrBit - 1)) >> 1)], p0, n);
+                    if (tid < kSegLkLanes) {
+                        SegLkChain ch;
+                        seg_lk_chain(lkv, lkR, lkS, g.D, lk_rec, tid, ch);
+                        if (tid == 0) *lk_h = ch.hstar;
+                    }
+                    __syncthreads();
+                    lkH = *lk_h;
+                    lkI = seglk_side(lkS, W, w.lpos[lkR]);
+                    const int top = seglk_hull_hi(lk_rec, lkH);   // the hull in chain slots: lkI + 1 .. top
+                    lo = lkS ? W - 1 - top : lkI + 1; hi = lkS ? W - 2 - lkI : top;
+                    ne = 0;
+                    mlk += 1; flips += lkH;
+                }
+            }
+            if (isLK) {
+                // lo, hi and the ends are set above, behind the barrier of the chain worked out again
+            } else if (is3) {
                 const Nl3Move m = nl3_unkey(bk & (kNl3Bit - 1), n);
                 const int type = m.type();
                 mv3 = seg3_make(slot_of(m.a()), slot_of(m.b()), slot_of(m.c()), type);
@@ -392,9 +502,25 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
 #pragma unroll
                 for (int q = 0; q < 6; ++q)
                     if (q < ne && !w.act[e[q]]) { w.act[e[q]] = 1; next[cnt++] = (u16)e[q]; }
+                if constexpr (LK) {
+                    if (isLK) {   // t1, then e, y, p of the steps kept
+                        if (!w.act[lkR]) { w.act[lkR] = 1; next[cnt++] = (u16)lkR; }
+                        for (int q = 0; q < 3 * lkH; ++q) {
+                            const u16 x = lk_rec[kSegLkMaxDepth + q];
+                            if (!w.act[x]) { w.act[x] = 1; next[cnt++] = x; }
+                        }
+                    }
+                }
                 s_na = cnt;
             }
-            if (is3) {
+            if (isLK) {
+                if constexpr (LK) {
+                    const u16 *js = lk_rec;
+                    seg_permute(w, stage, lo, hi, [=](int k) {
+                        return seglk_side(lkS, W, seglk_inv(lkI, js, lkH, seglk_side(lkS, W, k)));
+                    });
+                }
+            } else if (is3) {
                 seg_permute(w, stage, lo, hi, [=](int k) { return seg3_src(mv3, k); });
             } else if (!(bk & kNlOrBit)) {
                 const int sum = lo + hi;
@@ -469,6 +595,12 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_ils(const double2 *__restri
             for (int q = 0; q < 4; ++q) add(Z.moves_type[q], mt[q]);
         }
         if (accepted) atomicAdd(&acc[b], (u64)accepted);
+        if constexpr (LK) {
+            if (mlk) { atomicAdd(&g.lk[4 * b], (u64)mlk); atomicAdd(&g.lk[4 * b + 1], (u64)flips); }
+        }
+    }
+    if constexpr (LK) {
+        if (lk_chains) { atomicAdd(&g.lk[4 * b + 2], (u64)lk_chains); atomicAdd(&g.lk[4 * b + 3], (u64)lk_steps); }
     }
     unsigned long long cnt = view.cnt;
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
@@ -530,13 +662,18 @@ static_assert(offsetof(tsp_seg_ils3_stats, moves_3opt) == sizeof(tsp_seg_ils_sta
 
 static_assert(offsetof(tsp_seg_ils_groups_stats, groups) == sizeof(tsp_seg_ils3_stats),
               "tsp_seg_ils_groups_stats starts as tsp_seg_ils3_stats");
+static_assert(offsetof(tsp_seg_ils_lk_stats, lk_depth) == sizeof(tsp_seg_ils_groups_stats) &&
+                  sizeof(tsp_seg_ils_lk_stats) == sizeof(tsp_seg_ils_groups_stats) + 40,
+              "tsp_seg_ils_lk_stats starts as tsp_seg_ils_groups_stats");
 
 // What the entry points do.  `allowed` is the kinds mask the entry point takes; the B records are `stride` bytes apart and
 // start as tsp_seg_ils_stats, with3: they are tsp_seg_ils3_stats.  grouped: tsp_dev_seg_ils_groups with its `groups`, the records
-// are tsp_seg_ils_groups_stats.
+// are tsp_seg_ils_groups_stats.  lk_depth > 0: tsp_dev_seg_ils_lk with that D, the records are tsp_seg_ils_lk_stats; the chain kernel
+// runs only when kinds has TSP_NL_LK, else the launches are those of tsp_dev_seg_ils_groups.
 static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ, int succ_stride, int64_t tour_stride, double *obj,
                    uint64_t seed, int64_t iterations, int window, int span, int trials, int64_t max_moves_per_trial,
-                   double time_limit_s, void *stats, size_t stride, bool with3, bool grouped = false, int groups = 1) {
+                   double time_limit_s, void *stats, size_t stride, bool with3, bool grouped = false, int groups = 1,
+                   int lk_depth = 0) {
     int rc = tsp_nl_check(inst, &kinds, allowed, B, succ, succ_stride, tour_stride, obj);
     if (rc) return rc;
     if (iterations < 0 || trials < 1) return TSP_DEV_E_ARG;
@@ -575,6 +712,11 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
             x->seg_rec_len = rec_len;
         }
     }
+    const bool chains = lk_depth > 0 && (kinds & TSP_NL_LK);
+    if (chains) {
+        if (!x->d_seg_lk) TSP_HIP_TRY(hipMalloc(&x->d_seg_lk, sizeof(u64) * 4 * B));
+        TSP_HIP_TRY(hipMemsetAsync(x->d_seg_lk, 0, sizeof(u64) * 4 * B, s));
+    }
     std::vector<double> start((size_t)B);
     if (int e = tsp_grid_tour_cost(t, x->d_cost)) return e;
     TSP_HIP_TRY(hipMemcpyAsync(start.data(), x->d_cost, sizeof(double) * B, hipMemcpyDeviceToHost, s));
@@ -583,6 +725,7 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
     g.n = n; g.K = x->K; g.kinds = kinds; g.W = W; g.S = S; g.T = trials;
     g.cap = max_moves_per_trial < 0 ? -1 : max_moves_per_trial; g.seed = seed; g.it = 0;
     g.G = (int)G; g.rec = grouped ? x->d_seg_rec : nullptr;
+    g.D = lk_depth; g.lk = chains ? x->d_seg_lk : nullptr;
     long long queued = 0;
     SegHooks hooks;
     hooks.queued = &queued; hooks.iterations = I;
@@ -592,7 +735,11 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
                                    if (queued >= I) return;
                                    g.it = queued++;
                                    TSP_DISPATCH_METRIC(inst->wtype, inst->integer_cost, {
-                                       if (grouped && (kinds & TSP_NL_3OPT))
+                                       if (chains)
+                                           hipLaunchKernelGGL((k_seg_ils<WTC, INTC, true, true, true>), dim3((unsigned)(M * G), B),
+                                                              dim3(kSegThreads), lds, s, inst->d_coord, t->d_order, t->d_pos, x->d_nbr,
+                                                              x->d_st, x->d_seg_acc, g);
+                                       else if (grouped && (kinds & TSP_NL_3OPT))
                                            hipLaunchKernelGGL((k_seg_ils<WTC, INTC, true, true>), dim3((unsigned)(M * G), B),
                                                               dim3(kSegThreads), lds, s, inst->d_coord, t->d_order, t->d_pos, x->d_nbr,
                                                               x->d_st, x->d_seg_acc, g);
@@ -617,6 +764,8 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
     TSP_HIP_TRY(hipMemcpy(acc.data(), x->d_seg_acc, sizeof(u64) * B, hipMemcpyDeviceToHost));
     std::vector<u64> grp((size_t)2 * B, 0);
     if (grouped) TSP_HIP_TRY(hipMemcpy(grp.data(), x->d_seg_grp, sizeof(u64) * 2 * B, hipMemcpyDeviceToHost));
+    std::vector<u64> lk((size_t)4 * B, 0);
+    if (chains) TSP_HIP_TRY(hipMemcpy(lk.data(), x->d_seg_lk, sizeof(u64) * 4 * B, hipMemcpyDeviceToHost));
     const double seconds = wall_s() - run.t0;
     for (int b = 0; b < B && stats; ++b) {
         tsp_seg_ils_stats &o = *reinterpret_cast<tsp_seg_ils_stats *>(static_cast<char *>(stats) + (size_t)b * stride);
@@ -631,6 +780,11 @@ static int seg_run(tsp_dev_inst *inst, int kinds, int allowed, int B, int *succ,
         if (grouped) {
             tsp_seg_ils_groups_stats &og = reinterpret_cast<tsp_seg_ils_groups_stats &>(o);
             og.groups = G; og.offers = (int64_t)grp[2 * b]; og.commits = (int64_t)grp[2 * b + 1];
+        }
+        if (lk_depth > 0) {
+            tsp_seg_ils_lk_stats &ol = reinterpret_cast<tsp_seg_ils_lk_stats &>(o);
+            ol.lk_depth = lk_depth; ol.moves_lk = (int64_t)lk[4 * b]; ol.lk_flips = (int64_t)lk[4 * b + 1];
+            ol.lk_chains = (int64_t)lk[4 * b + 2]; ol.lk_steps = (int64_t)lk[4 * b + 3];
         }
     }
     return status;
@@ -657,6 +811,15 @@ int tsp_dev_seg_ils_groups(tsp_dev_inst *inst, int kinds, int groups, int B, int
                            int64_t max_moves_per_trial, double time_limit_s, tsp_seg_ils_groups_stats *stats) {
     return seg_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT, B, succ, succ_stride, tour_stride, obj, seed, iterations,
                    window, span, trials, max_moves_per_trial, time_limit_s, stats, sizeof *stats, true, true, groups);
+}
+
+int tsp_dev_seg_ils_lk(tsp_dev_inst *inst, int kinds, int lk_depth, int groups, int B, int *succ, int succ_stride, int64_t tour_stride,
+                       double *obj, uint64_t seed, int64_t iterations, int window, int span, int trials,
+                       int64_t max_moves_per_trial, double time_limit_s, tsp_seg_ils_lk_stats *stats) {
+    if (lk_depth > TSP_SEG_LK_MAX_DEPTH) return TSP_DEV_E_ARG;
+    return seg_run(inst, kinds, TSP_NL_2OPT | TSP_NL_OROPT | TSP_NL_3OPT | TSP_NL_LK, B, succ, succ_stride, tour_stride, obj, seed,
+                   iterations, window, span, trials, max_moves_per_trial, time_limit_s, stats, sizeof *stats, true, true, groups,
+                   lk_depth <= 0 ? TSP_SEG_LK_DEFAULT_DEPTH : lk_depth);
 }
 
 }  // extern "C"

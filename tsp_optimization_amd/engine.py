@@ -20,6 +20,8 @@ NL_BATCH_DEFAULT_ROUNDS = 2            # claim rounds of nl_3opt_batch (TSP_NL_B
 NL_MAX_K, NL_DEFAULT_K = 16, 10
 SEG_ILS_MAX_WINDOW, SEG_ILS_DEFAULT_WINDOW = 2048, 1024   # windows of seg_ils (TSP_SEG_ILS_MAX_WINDOW, _DEFAULT_WINDOW)
 SEG_ILS_MAX_GROUPS = 64                                   # groups per window of seg_ils_groups (TSP_SEG_ILS_MAX_GROUPS)
+NL_LK = 8                                                 # the chain kind of seg_ils_lk (TSP_NL_LK)
+SEG_LK_MAX_DEPTH, SEG_LK_DEFAULT_DEPTH = 16, 16           # steps of a chain (TSP_SEG_LK_MAX_DEPTH, _DEFAULT_DEPTH)
 HK_DEFAULT_ITERS, HK_DEFAULT_LAMBDA = 300, 2.0
 ALPHA_DEFAULT_K = 5
 
@@ -84,6 +86,11 @@ class SegIls3Stats(_Stats):
 
 class SegIlsGroupsStats(_Stats):
     _fields_ = SegIls3Stats._fields_ + [("groups", C.c_int64), ("offers", C.c_int64), ("commits", C.c_int64)]
+
+
+class SegIlsLkStats(_Stats):
+    _fields_ = SegIlsGroupsStats._fields_ + [("lk_depth", C.c_int64), ("moves_lk", C.c_int64), ("lk_flips", C.c_int64),
+                                             ("lk_chains", C.c_int64), ("lk_steps", C.c_int64)]
 
 
 class LbStats(_Stats):
@@ -209,6 +216,8 @@ def lib():
         L.tsp_dev_seg_ils3.argtypes = L.tsp_dev_seg_ils.argtypes[:-1] + [C.POINTER(SegIls3Stats)]
         L.tsp_dev_seg_ils_groups.argtypes = ([vp, C.c_int, C.c_int] + L.tsp_dev_seg_ils.argtypes[2:-1]
                                              + [C.POINTER(SegIlsGroupsStats)])
+        L.tsp_dev_seg_ils_lk.argtypes = ([vp, C.c_int, C.c_int, C.c_int] + L.tsp_dev_seg_ils.argtypes[2:-1]
+                                         + [C.POINTER(SegIlsLkStats)])
         lbp = C.POINTER(LbStats)
         L.tsp_dev_one_tree.argtypes = [vp, dp, ip, ip, dp, lbp]
         L.tsp_dev_held_karp.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, dp, dp, lbp]
@@ -247,6 +256,7 @@ EXPORTED = [
     "tsp_dev_seg_ils",
     "tsp_dev_seg_ils3",
     "tsp_dev_seg_ils_groups",
+    "tsp_dev_seg_ils_lk",
     "tsp_dev_inst_lds_variant",
 ]
 
@@ -579,6 +589,23 @@ class Instance:
         rc = lib().tsp_dev_seg_ils_groups(self._h, int(kinds), int(groups), B, _i(succ2), 1, n, _d(o), int(seed) & (2 ** 64 - 1),
                                           int(iterations), int(window), int(span), int(trials), int(max_moves_per_trial),
                                           time_limit, st)
+        return _result(rc, single, succ2, o, st)
+
+    def seg_ils_lk(self, succ, iterations, kinds=NL_2OPT | NL_OROPT | NL_3OPT | NL_LK, depth=0, groups=1, window=0, span=0,
+                   trials=1, seed=0, max_moves=-1, time_limit=-1.0, obj=None):
+        """seg_ils_groups with Lin-Kernighan chains as a fourth kind of the repair (tsp_dev_seg_ils_lk): kinds is any non-empty
+        subset of NL_2OPT | NL_OROPT | NL_3OPT | NL_LK.  With NL_LK every active node also runs two chains per decision, one to
+        each side along the window: up to `depth` reversals (1 .. SEG_LK_MAX_DEPTH, 0: SEG_LK_DEFAULT_DEPTH) under the gain
+        criterion, kept up to the best prefix.  Everything else as seg_ils_groups (max_moves is its max_moves_per_trial), the stats
+        with lk_depth, moves_lk, lk_flips, lk_chains and lk_steps behind them.  Without NL_LK it returns the bits of
+        seg_ils_groups"""
+        single, succ2 = self._tours(succ)
+        B, n = succ2.shape
+        o = _obj(obj, B)
+        st = (SegIlsLkStats * B)()
+        rc = lib().tsp_dev_seg_ils_lk(self._h, int(kinds), int(depth), int(groups), B, _i(succ2), 1, n, _d(o),
+                                      int(seed) & (2 ** 64 - 1), int(iterations), int(window), int(span), int(trials),
+                                      int(max_moves), time_limit, st)
         return _result(rc, single, succ2, o, st)
 
     # -- Held-Karp lower bound (extension) ---------------------------------------------------

@@ -778,10 +778,12 @@ int HEU_ils_greedy_edge(instance *inst) { (void)HEU_greedy_edge(inst); return al
 
 /* ---- windowed iterated local search (extension) -------------------------------------------------------------- */
 
-static __thread tsp_seg_ils_groups_stats t_seg_stats;   /* starts as tsp_seg_ils3_stats, which starts as tsp_seg_ils_stats */
+static __thread tsp_seg_ils_lk_stats t_seg_stats;   /* starts as tsp_seg_ils_groups_stats, that as tsp_seg_ils3_stats, that as
+                                                       tsp_seg_ils_stats */
 static int g_seg_iters = 100, g_seg_window = 0, g_seg_span = 50, g_seg_trials = 1;   /* tsp_host_set_seg_ils */
 static int g_seg_kinds = TSP_NL_2OPT | TSP_NL_OROPT;                                 /* tsp_host_set_seg_ils_kinds */
 static int g_seg_groups = 1;                                                         /* tsp_host_set_seg_ils_groups */
+static int g_seg_lk = 0;                                                             /* tsp_host_set_seg_ils_lk */
 
 int tsp_host_set_seg_ils(int iterations, int window, int span, int trials) {
     if (iterations < 0 || trials < 1 || (span >= 1 && span <= 7)) return TSP_DEV_E_ARG;
@@ -811,6 +813,14 @@ int tsp_host_set_seg_ils_groups(int groups) {
     return 0;
 }
 
+int tsp_host_set_seg_ils_lk(int depth) {
+    if (depth < -1 || depth > TSP_SEG_LK_MAX_DEPTH) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_seg_lk = depth;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
 void tsp_host_last_seg_ils_stats(tsp_seg_ils_stats *out) {
     if (out) memcpy(out, &t_seg_stats, sizeof *out);
 }
@@ -820,15 +830,20 @@ void tsp_host_last_seg_ils3_stats(tsp_seg_ils3_stats *out) {
 }
 
 void tsp_host_last_seg_ils_groups_stats(tsp_seg_ils_groups_stats *out) {
+    if (out) memcpy(out, &t_seg_stats, sizeof *out);
+}
+
+void tsp_host_last_seg_ils_lk_stats(tsp_seg_ils_lk_stats *out) {
     if (out) *out = t_seg_stats;
 }
 
 /* tsp_dev_seg_ils, or with the 3-opt kind set tsp_dev_seg_ils3, or with another groups setting than 1 tsp_dev_seg_ils_groups
- * (whose counters groups, offers and commits stay 0 otherwise), over the lists alg_nl_opt would use, one chain from
+ * (whose counters groups, offers and commits stay 0 otherwise), or under tsp_host_set_seg_ils_lk tsp_dev_seg_ils_lk with the chain
+ * kind beside the kinds set (the chain counters stay 0 otherwise), over the lists alg_nl_opt would use, one chain from
  * inst->solution */
 int alg_seg_ils(instance *inst) {
     const int n = inst->num_nodes;
-    tsp_seg_ils_groups_stats st;   /* without the 3-opt kind its first part is written and the 3-opt counters stay 0 */
+    tsp_seg_ils_lk_stats st;   /* without the 3-opt kind its first part is written and the 3-opt counters stay 0 */
     memset(&st, 0, sizeof st);
     double obj = inst->solution.obj_best;
     pthread_mutex_lock(&g_lock);
@@ -837,11 +852,15 @@ int alg_seg_ils(instance *inst) {
     const int span = g_seg_span > W - 1 ? W - 1 : g_seg_span;
     tsp_dev_inst *dev = dev_inst_locked(inst);
     int rc = lists_locked(inst, dev, obj);
-    const int three = (g_seg_kinds & TSP_NL_3OPT) != 0, grouped = g_seg_groups != 1;
-    if (rc == 0 && grouped)
+    const int three = (g_seg_kinds & TSP_NL_3OPT) != 0, grouped = g_seg_groups != 1, lk = g_seg_lk != 0;
+    if (rc == 0 && lk)
+        rc = tsp_dev_seg_ils_lk(dev, g_seg_kinds | TSP_NL_LK, g_seg_lk < 0 ? 0 : g_seg_lk, g_seg_groups, 1, &inst->solution.edges[0].j,
+                                2, 2 * (int64_t)n, &obj, (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span,
+                                g_seg_trials, -1, limit_of(inst), &st);
+    else if (rc == 0 && grouped)
         rc = tsp_dev_seg_ils_groups(dev, g_seg_kinds, g_seg_groups, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
                                     (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
-                                    limit_of(inst), &st);
+                                    limit_of(inst), (tsp_seg_ils_groups_stats *)&st);
     else if (rc == 0 && three)
         rc = tsp_dev_seg_ils3(dev, g_seg_kinds, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
                               (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
@@ -851,7 +870,8 @@ int alg_seg_ils(instance *inst) {
                              (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
                              limit_of(inst), (tsp_seg_ils_stats *)&st);
     pthread_mutex_unlock(&g_lock);
-    if (rc < 0) dev_fail(grouped ? "tsp_dev_seg_ils_groups" : (three ? "tsp_dev_seg_ils3" : "tsp_dev_seg_ils"), rc);
+    if (rc < 0)
+        dev_fail(lk ? "tsp_dev_seg_ils_lk" : (grouped ? "tsp_dev_seg_ils_groups" : (three ? "tsp_dev_seg_ils3" : "tsp_dev_seg_ils")), rc);
     inst->solution.obj_best = obj;
     t_seg_stats = st;
     if (rc == TIME_LIMIT_EXCEEDED) LOG_I("windowed iterated local search time exceeded");
