@@ -45,7 +45,8 @@ enum {
     TSP_DEV_E_ARG = -3,           /* bad argument (NULL, n < 3, unknown mode ...) */
     TSP_DEV_E_NOT_A_TOUR = -4,    /* a successor list is not one Hamiltonian cycle */
     TSP_DEV_E_NOMEM = -5,
-    TSP_DEV_E_COMM = -6           /* RCCL could not be opened or a collective failed (tsp_dev_comm_last_error()) */
+    TSP_DEV_E_COMM = -6,          /* RCCL could not be opened or a collective failed (tsp_dev_comm_last_error()) */
+    TSP_DEV_E_INTERNAL = -7       /* a device loop ran into its hard cap or a result failed its own check: a defect, not an input */
 };
 
 /* 2-opt move selection */
@@ -881,6 +882,61 @@ typedef struct {
 /* succ: n ints, succ_stride ints apart; edges: 2(n - 1) ints; each output may be NULL.  No instance, n < 3 or a stride below 1:
  * TSP_DEV_E_ARG, and the outputs are untouched.  There is no CPU fallback. */
 int tsp_dev_greedy_edge(tsp_dev_inst *inst, int *succ, int succ_stride, double *obj, int *edges, tsp_greedy_edge_stats *stats);
+
+/* ---- partition crossover (extension; Whitley's GPX, the merging step of LKH's multi-trial runs) -------------------------------
+ * (DESIGN.md 4.24 has the kernels.)  Inputs are two tours A and B on the same instance, as successor lists, n >= 3.  d(i,j) is
+ * the value tsp_dev_dist_pairs returns, lower id first.
+ * Fixed-point length.  q(e) = llrint(ldexp(d(e), 20)), an int64.  All sums below are sums of q, so they do not depend on the order
+ *   of summation: integer atomics, and two runs return the same bits.  A parent whose sum of q would reach 2^62: TSP_DEV_E_ARG,
+ *   tours untouched.
+ * Base.  The parent with the smaller sum of q is the base, A on ties.  Below, "A" means the base and "B" the other; stats.base
+ *   says which one it was (0: the caller's A, 1: the caller's B).  The child is oriented like the base.
+ * Common edges.  An edge is common when it is in both tours, undirected; common_edges counts them.
+ * Degenerate cases.  If all n edges or no edge is common, the child is the base; components is 0 or 1 respectively, and
+ *   exchangeable = taken = 0.
+ * Graph H.  Its nodes are all nodes, its edges the non-common edges of A and of B.  At every node the two tours have equally many
+ *   non-common edges: 0, 1 or 2.  c(v) is the smallest node id in v's component of H.  A component is a component of H with at
+ *   least one edge.  A portal is a node with exactly one non-common edge per tour.
+ * Common runs.  A common run is a maximal path of common edges; both its ends are portals.  It is internal when c of its two ends
+ *   is equal, otherwise external.
+ * Stretches.  Cut A's cycle at its external common runs.  The maximal pieces that remain are the A-stretches; they are made of
+ *   non-common edges and internal common runs.  Each is a contiguous interval of A's order from one portal to another and lies in
+ *   exactly one component.  The B-stretches are the same construction on B's order.  With no external run there are no stretches.
+ *   stats.stretches counts the A-stretches (there are as many B-stretches: one per external run).
+ * Exchangeable.  A component is exchangeable when it has at least one stretch and, for every A-stretch with ends {x, y}, there is a
+ *   B-stretch with ends {x, y}.  The stretches of such a component cover the same node set in both tours, so replacing all its
+ *   A-stretches by the B-stretches of the same ends leaves a Hamiltonian cycle; components are node-disjoint, so any subset of
+ *   them can be exchanged at once.  (Exactly two external runs at a component is GPX's classic case and always qualifies.)
+ * Taken.  qA(C) and qB(C) are the sums of q over the non-common edges of A and of B in C.  C is taken iff it is exchangeable and
+ *   qB(C) < qA(C), strictly; ties keep A.
+ * Child.  A's order with every stretch of a taken component replaced by the B-stretch of the same ends, read from the A-stretch's
+ *   first node to its last (in B's order that may run backwards, and may wrap past position n - 1).  The call returns the child's
+ *   successor list in A's direction and obj, the recomputed cost of the child (the tour-cost kernel of tsp_dev_perm_cost over the
+ *   child's order).  gain_q is the sum of qA - qB over the taken components.  With integer costs obj = cost(base) - gain_q / 2^20
+ *   exactly, and obj <= min(cost A, cost B).
+ * Components are found by hook-and-jump rounds whose number is O(log n) and capped at 8 ceil(log2 n) + 16; a run into the cap is
+ * TSP_DEV_E_INTERNAL.  rounds counts them, the one that found nothing left to do included; it is the one field that may differ
+ * from run to run. */
+typedef struct {
+    int64_t common_edges;
+    int64_t components;    /* components of H                                                                            */
+    int64_t exchangeable;  /* ... that are exchangeable                                                                  */
+    int64_t taken;         /* ... that the child takes from the other parent                                             */
+    int64_t stretches;     /* A-stretches = external common runs                                                         */
+    int64_t gain_q;        /* sum of q the child lies below the base                                                     */
+    int64_t rounds;        /* component rounds the device carried out for this pair                                      */
+    int base;              /* 0: the caller's succ_a was the base, 1: succ_b                                             */
+    double cost_a, cost_b; /* the caller's two parents, from the tour-cost kernel                                        */
+    double cost_child;     /* = obj                                                                                      */
+    double seconds;        /* wall time of the call, host clock                                                          */
+    double device_ms;      /* device time of the call, HIP events on the engine's stream                                 */
+} tsp_gpx_stats;
+/* P >= 1 pairs at once: pair k is succ_a + k tour_stride and succ_b + k tour_stride, n ints each, succ_stride ints apart; its child
+ * goes to succ_child + k tour_stride in the same layout.  succ_child may alias succ_a (or succ_b).  obj (P doubles) and stats (P
+ * entries) may be NULL.  No instance, P < 1, a NULL tour or a stride below 1: TSP_DEV_E_ARG; a successor list that is not one
+ * Hamiltonian cycle: TSP_DEV_E_NOT_A_TOUR.  On any error the caller's arrays are untouched.  There is no CPU fallback. */
+int tsp_dev_gpx(tsp_dev_inst *inst, int P, const int *succ_a, const int *succ_b, int succ_stride, int64_t tour_stride, int *succ_child,
+                double *obj, tsp_gpx_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -218,6 +218,17 @@ int tsp_host_set_seg_ils_groups(int groups);
  * above plus TSP_NL_LK, that depth and the groups set above.  -1: the same with TSP_SEG_LK_DEFAULT_DEPTH.  Else TSP_DEV_E_ARG and the
  * setting stays.  The batched descent of HEU_seg_ils_greedy_edge is not changed by it. */
 int tsp_host_set_seg_ils_lk(int depth);
+/* Chains of the two functions above, merged by partition crossover (include/tsp_hip.h, tsp_dev_gpx).  1 (the default): alg_seg_ils
+ * makes exactly the calls described above.  C = 2 .. TSP_HOST_MAX_SEG_ILS_CHAINS: the same device call with B = C chains, all from
+ * inst->solution under params.seed, chain c with the device's stream c of that seed; then rounds of pairwise tsp_dev_gpx over the C
+ * results -- pairs (0,1), (2,3), ... in one device call a round, an odd last one passes through -- until one tour is left, which
+ * goes to inst->solution with its recomputed cost.  The windowed search's counters are chain 0's.  Else TSP_DEV_E_ARG and the
+ * setting stays. */
+#define TSP_HOST_MAX_SEG_ILS_CHAINS 64
+int tsp_host_set_seg_ils_chains(int chains);
+/* Partition crossover of two successor lists of the instance (n ints each, 1 apart) into succ_child, which may be one of them.
+ * Returns tsp_dev_gpx's status; on an error nothing is written. */
+int tsp_host_gpx(instance *inst, const int *succ_a, const int *succ_b, int *succ_child);
 
 /* ---- src/tabusearch.c (externally linked there, not in its header) --------------------------- */
 int alg_2opt_tabu(instance *inst, int *skip_edge, int *stored_prev, const int iter, const int tenure); /* :107 */
@@ -344,6 +355,8 @@ void tsp_host_last_seg_ils3_stats(tsp_seg_ils3_stats *out);
 void tsp_host_last_seg_ils_groups_stats(tsp_seg_ils_groups_stats *out);
 /* ... and the chain counters behind those (all 0 when the call ran under tsp_host_set_seg_ils_lk(0)). */
 void tsp_host_last_seg_ils_lk_stats(tsp_seg_ils_lk_stats *out);
+/* Counters of this thread's last merge: tsp_host_gpx, or the last round of an alg_seg_ils call with more than one chain. */
+void tsp_host_last_gpx_stats(tsp_gpx_stats *out);
 /* Releases the cached device context / instances (optional; also done at exit). */
 void tsp_host_shutdown(void);
 

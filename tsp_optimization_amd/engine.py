@@ -13,6 +13,7 @@ GREEDY, GRASP = 0, 1
 ENGINE_AUTO, ENGINE_GRID, ENGINE_LDS, ENGINE_CLUSTER = 0, 1, 2, 3
 OK, WRONG_STARTING_NODE, TIME_LIMIT_EXCEEDED = 0, 1, 2
 E_ARG = -3
+E_NOT_A_TOUR, E_INTERNAL = -4, -7
 NL_2OPT, NL_OROPT = 1, 2
 NL_3OPT = 4   # tsp_dev_nl_3opt and what builds on it, and seg_ils3
 DLB_OFF, DLB_ON, DLB_CLOSE = 0, 1, 2   # don't-look bits of nl_3opt and ils
@@ -113,6 +114,13 @@ class AlphaStats(_Stats):
 class GreedyEdgeStats(_Stats):
     _fields_ = [("rounds", C.c_int64), ("edges", C.c_int64), ("rows_scanned", C.c_int64), ("dists_executed", C.c_int64),
                 ("max_edges_in_round", C.c_int64), ("seconds", C.c_double), ("device_ms", C.c_double)]
+
+
+class GpxStats(_Stats):
+    _fields_ = [("common_edges", C.c_int64), ("components", C.c_int64), ("exchangeable", C.c_int64), ("taken", C.c_int64),
+                ("stretches", C.c_int64), ("gain_q", C.c_int64), ("rounds", C.c_int64), ("base", C.c_int),
+                ("cost_a", C.c_double), ("cost_b", C.c_double), ("cost_child", C.c_double),
+                ("seconds", C.c_double), ("device_ms", C.c_double)]
 
 
 _lib = None
@@ -227,6 +235,7 @@ def lib():
         L.tsp_dev_inst_alpha_build.argtypes = [vp, C.c_int, dp, dp, C.POINTER(AlphaStats)]
         L.tsp_dev_alpha_rows.argtypes = [vp, dp, C.c_int, ip, dp]
         L.tsp_dev_greedy_edge.argtypes = [vp, ip, C.c_int, dp, ip, C.POINTER(GreedyEdgeStats)]
+        L.tsp_dev_gpx.argtypes = [vp, C.c_int, ip, ip, C.c_int, C.c_int64, ip, dp, C.POINTER(GpxStats)]
         _lib = L
     return _lib
 
@@ -258,6 +267,7 @@ EXPORTED = [
     "tsp_dev_seg_ils_groups",
     "tsp_dev_seg_ils_lk",
     "tsp_dev_inst_lds_variant",
+    "tsp_dev_gpx",
 ]
 
 COMM_ID_BYTES = 128
@@ -717,6 +727,51 @@ class Instance:
         if want_stats:
             out += (st.as_dict(),)
         return out
+
+    # -- partition crossover (extension) --------------------------------------------------------
+    def gpx(self, succ_a, succ_b, want_stats=False):
+        """Partition crossover of two tours (tsp_dev_gpx): succ_a, succ_b [n] or [P,n], pair k merged from row k of each, all P
+        pairs in one device call.  The child is the cheaper parent (succ_a on ties of the fixed-point lengths) with every
+        exchangeable component of the parents' differences taken from the other parent where that is strictly shorter: never
+        longer than either parent.  -> (child [n] or [P,n] int32, obj float or [P]) (+ a stats dict, or a list of P, with
+        want_stats)"""
+        single, a2 = self._tours(succ_a)
+        single_b, b2 = self._tours(succ_b)
+        assert single == single_b and a2.shape == b2.shape
+        P, n = a2.shape
+        child = np.zeros_like(a2)
+        obj = np.zeros(P, dtype=np.float64)
+        st = (GpxStats * P)()
+        _check(lib().tsp_dev_gpx(self._h, P, _i(a2), _i(b2), 1, n, _i(child), _d(obj), st))
+        out = (child[0], float(obj[0])) if single else (child, obj)
+        if want_stats:
+            dicts = [x.as_dict() for x in st]
+            out += (dicts[0] if single else dicts,)
+        return out
+
+    def gpx_tournament(self, tours):
+        """Rounds of pairwise gpx over tours [T,n]: pairs (0,1), (2,3), ... in one device call per round, an odd last tour passes
+        through, until one tour is left.  -> (succ [n] int32, its cost, one list of per-pair stats dicts per round).  T = 1: the
+        tour itself, its cost from perm_cost's kernel, no rounds."""
+        tours = np.array(tours, dtype=np.int32, copy=True, order="C")
+        assert tours.ndim == 2 and tours.shape[0] >= 1 and tours.shape[1] == self.n
+        rounds = []
+        cost = None
+        while tours.shape[0] > 1:
+            P = tours.shape[0] // 2
+            child, obj, st = self.gpx(tours[0:2 * P:2], tours[1:2 * P:2], want_stats=True)
+            rounds.append(st)
+            tours = np.concatenate([child, tours[-1:]]) if tours.shape[0] % 2 else child
+            if tours.shape[0] == 1:   # the last round had one pair
+                cost = float(obj[0])
+        if cost is None:
+            order = np.zeros(self.n, dtype=np.int32)
+            v = 0
+            for k in range(self.n):
+                order[k] = v
+                v = int(tours[0][v])
+            cost = float(self.perm_cost(order)[0])
+        return tours[0], cost, rounds
 
     def perm_cost(self, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

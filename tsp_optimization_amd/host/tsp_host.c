@@ -784,6 +784,8 @@ static int g_seg_iters = 100, g_seg_window = 0, g_seg_span = 50, g_seg_trials = 
 static int g_seg_kinds = TSP_NL_2OPT | TSP_NL_OROPT;                                 /* tsp_host_set_seg_ils_kinds */
 static int g_seg_groups = 1;                                                         /* tsp_host_set_seg_ils_groups */
 static int g_seg_lk = 0;                                                             /* tsp_host_set_seg_ils_lk */
+static int g_seg_chains = 1;                                                         /* tsp_host_set_seg_ils_chains */
+static __thread tsp_gpx_stats t_gpx_stats;   /* the last merge of this thread: tsp_host_gpx, or the last round of a chained alg_seg_ils */
 
 int tsp_host_set_seg_ils(int iterations, int window, int span, int trials) {
     if (iterations < 0 || trials < 1 || (span >= 1 && span <= 7)) return TSP_DEV_E_ARG;
@@ -821,6 +823,48 @@ int tsp_host_set_seg_ils_lk(int depth) {
     return 0;
 }
 
+int tsp_host_set_seg_ils_chains(int chains) {
+    if (chains < 1 || chains > TSP_HOST_MAX_SEG_ILS_CHAINS) return TSP_DEV_E_ARG;
+    pthread_mutex_lock(&g_lock);
+    g_seg_chains = chains;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+void tsp_host_last_gpx_stats(tsp_gpx_stats *out) {
+    if (out) *out = t_gpx_stats;
+}
+
+int tsp_host_gpx(instance *inst, const int *succ_a, const int *succ_b, int *succ_child) {
+    tsp_gpx_stats st;
+    memset(&st, 0, sizeof st);
+    double obj = 0.0;
+    pthread_mutex_lock(&g_lock);
+    int rc = tsp_dev_gpx(dev_inst_locked(inst), 1, succ_a, succ_b, 1, inst->num_nodes, succ_child, &obj, &st);
+    pthread_mutex_unlock(&g_lock);
+    if (rc == 0) t_gpx_stats = st;
+    return rc;
+}
+
+/* T tours of n successors each, one after the other in `tours`: rounds of pairwise tsp_dev_gpx -- pairs (0,1), (2,3), ... in one
+ * device call, the child written over the pair's first tour, an odd last tour passes through -- until tours[0 .. n-1] is the one
+ * left.  *obj and *st are the last merge's.  g_lock is held. */
+static int gpx_tournament_locked(tsp_dev_inst *dev, int n, int T, int *tours, double *obj, tsp_gpx_stats *st) {
+    double o[TSP_HOST_MAX_SEG_ILS_CHAINS / 2];
+    tsp_gpx_stats ps[TSP_HOST_MAX_SEG_ILS_CHAINS / 2];
+    while (T > 1) {
+        const int P = T / 2;
+        int rc = tsp_dev_gpx(dev, P, tours, tours + n, 1, 2 * (int64_t)n, tours, o, ps);
+        if (rc) return rc;
+        for (int k = 1; k < P; k++) memcpy(tours + (size_t)k * n, tours + (size_t)2 * k * n, sizeof(int) * (size_t)n);
+        if (T % 2) memcpy(tours + (size_t)P * n, tours + (size_t)(T - 1) * n, sizeof(int) * (size_t)n);
+        T = P + T % 2;
+        *obj = o[0];
+        *st = ps[0];
+    }
+    return 0;
+}
+
 void tsp_host_last_seg_ils_stats(tsp_seg_ils_stats *out) {
     if (out) memcpy(out, &t_seg_stats, sizeof *out);
 }
@@ -853,23 +897,62 @@ int alg_seg_ils(instance *inst) {
     tsp_dev_inst *dev = dev_inst_locked(inst);
     int rc = lists_locked(inst, dev, obj);
     const int three = (g_seg_kinds & TSP_NL_3OPT) != 0, grouped = g_seg_groups != 1, lk = g_seg_lk != 0;
+    /* one chain from inst->solution, or C of them (chain c: stream c of the seed) into a block of their own */
+    const int C = g_seg_chains;
+    int *tours = NULL, *succ = &inst->solution.edges[0].j, stride = 2;
+    int64_t tstride = 2 * (int64_t)n;
+    double objs[TSP_HOST_MAX_SEG_ILS_CHAINS];
+    tsp_seg_ils_lk_stats *sts = &st;
+    double *po = &obj;
+    if (C > 1) {
+        tours = (int *)malloc(sizeof(int) * (size_t)C * (size_t)n);
+        sts = (tsp_seg_ils_lk_stats *)calloc((size_t)C, sizeof *sts);
+        if (!tours || !sts) {   /* LOG_E ends the process; what it must not find is the lock or half of the pair */
+            free(tours);
+            free(sts);
+            pthread_mutex_unlock(&g_lock);
+            LOG_E("out of memory");
+        }
+        for (int c = 0; c < C; c++) {
+            for (int v = 0; v < n; v++) tours[(size_t)c * n + v] = inst->solution.edges[v].j;
+            objs[c] = obj;
+        }
+        succ = tours; stride = 1; tstride = n; po = objs;
+    }
     if (rc == 0 && lk)
-        rc = tsp_dev_seg_ils_lk(dev, g_seg_kinds | TSP_NL_LK, g_seg_lk < 0 ? 0 : g_seg_lk, g_seg_groups, 1, &inst->solution.edges[0].j,
-                                2, 2 * (int64_t)n, &obj, (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span,
-                                g_seg_trials, -1, limit_of(inst), &st);
+        rc = tsp_dev_seg_ils_lk(dev, g_seg_kinds | TSP_NL_LK, g_seg_lk < 0 ? 0 : g_seg_lk, g_seg_groups, C, succ,
+                                stride, tstride, po, (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span,
+                                g_seg_trials, -1, limit_of(inst), sts);
     else if (rc == 0 && grouped)
-        rc = tsp_dev_seg_ils_groups(dev, g_seg_kinds, g_seg_groups, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
+        rc = tsp_dev_seg_ils_groups(dev, g_seg_kinds, g_seg_groups, C, succ, stride, tstride, po,
                                     (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
-                                    limit_of(inst), (tsp_seg_ils_groups_stats *)&st);
+                                    limit_of(inst), (tsp_seg_ils_groups_stats *)sts);
     else if (rc == 0 && three)
-        rc = tsp_dev_seg_ils3(dev, g_seg_kinds, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
+        rc = tsp_dev_seg_ils3(dev, g_seg_kinds, C, succ, stride, tstride, po,
                               (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
-                              limit_of(inst), (tsp_seg_ils3_stats *)&st);
+                              limit_of(inst), (tsp_seg_ils3_stats *)sts);
     else if (rc == 0)
-        rc = tsp_dev_seg_ils(dev, g_seg_kinds, 1, &inst->solution.edges[0].j, 2, 2 * (int64_t)n, &obj,
+        rc = tsp_dev_seg_ils(dev, g_seg_kinds, C, succ, stride, tstride, po,
                              (uint64_t)(unsigned)inst->params.seed, g_seg_iters, g_seg_window, span, g_seg_trials, -1,
-                             limit_of(inst), (tsp_seg_ils_stats *)&st);
+                             limit_of(inst), (tsp_seg_ils_stats *)sts);
+    int rc_gpx = 0;
+    if (C > 1) {
+        /* the chains' records lie one behind the other in the size of the call's own stats type; chain 0's is reported */
+        memcpy(&st, sts, sizeof st);
+        if (rc >= 0) {
+            tsp_gpx_stats gs;
+            memset(&gs, 0, sizeof gs);
+            rc_gpx = gpx_tournament_locked(dev, n, C, tours, &obj, &gs);
+            if (rc_gpx == 0) {
+                for (int v = 0; v < n; v++) inst->solution.edges[v].j = tours[v];
+                t_gpx_stats = gs;
+            }
+        }
+        free(tours);
+        free(sts);
+    }
     pthread_mutex_unlock(&g_lock);
+    if (rc_gpx < 0) dev_fail("tsp_dev_gpx", rc_gpx);
     if (rc < 0)
         dev_fail(lk ? "tsp_dev_seg_ils_lk" : (grouped ? "tsp_dev_seg_ils_groups" : (three ? "tsp_dev_seg_ils3" : "tsp_dev_seg_ils")), rc);
     inst->solution.obj_best = obj;
